@@ -8,12 +8,16 @@ slice updates of theta (E-SS+RD-SS.ipynb protocol, w=1, max_steps_out=0), Approx
 estimator with N_imp=256, `--chains` independent chains per GPU advanced in lockstep.
 A step = one MCMC transition (u-update + theta-update) of every chain on every GPU.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 Rank 0 prints one JSON line (contract in the task statement); `roofline` is the dominant kernel
 (the f64-MFMA Cholesky trailing update) timed with HIP events on the context's stream over the
-timed region; `cpu_baseline` times the CPU restatement of the reference (oracle/) on this host.
+timed region. A plain run sets up, warms up, times the region and prints the line; `--full` adds
+what takes work of its own after the timed region: the in-run ESS sample (untimed extension of
+the chains), the same workload from prior draws, `cpu_baseline` (the CPU restatement of the
+reference, oracle/, timed on this host) and the parity check - their keys are null in a plain
+run's line. The timed region is the same in both.
 """
 import argparse
 import json
@@ -49,6 +53,13 @@ def parse():
     ap.add_argument('--seed', type=int, default=20151009)
     ap.add_argument('--schedule', choices=('async',), default='async',
                     help='chain scheduling of the batched sampler (auxpm/batched.py)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region also run what the headline does not need: the '
+                         'untimed ESS extension of the chains, the prior-initialised run, the CPU '
+                         'baseline and the parity check (--cpu-baseline, --cpu-budget, --parity, '
+                         '--ess-min and --ess-burn act only with --full)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed region returned (dump_outputs) as DIR/<name>.npy')
     ap.add_argument('--cpu-baseline', type=int, default=1)
     ap.add_argument('--cpu-budget', type=float, default=30.0,
                     help='approximate seconds of CPU work for the baseline sample')
@@ -804,12 +815,40 @@ def run_chains(a, dist, dev, X, y, theta_init, measure):
     transitions = dist.sum(local_tr)
     call_ops = list(smp.call_ops)
     rec = {'elapsed': elapsed, 'done': done, 'local_tr': local_tr, 'transitions': transitions,
-           'value': transitions / elapsed, 'series': series,
+           'value': transitions / elapsed, 'series': series, 'traces': res['traces'],
            'n_th': (smp.n_theta_calls - th0) / max(1, local_tr),
            'n_u': (smp.n_u_calls - u0) / max(1, local_tr),
            'call_ops': call_ops, 'wall': dict(smp.wall), 'batch_hist': smp.batch_hist(),
            'theta_call_ms_mean': 1e3 * smp.wall['theta_call'] / max(1, len(call_ops))}
     return smp, rec
+
+
+DUMP_MAX_BYTES = 48 << 20  # of the theta array (the dump stays below 64 MB)
+
+
+def dump_outputs(dirname, dist, a, run, P):
+    """--dump-outputs: what the timed region's call (run_async(--steps, keep_going=True))
+    returned on this rank, as float64 .npy files:
+      thetas            (chains, K, P)  each chain's theta after each of its first --steps timed
+                                        transitions (every live chain completes that many; what
+                                        chains that were ahead did beyond them is left out). K =
+                                        --steps, or the last K of them where --steps of them
+                                        would pass DUMP_MAX_BYTES. A failed chain's rows are NaN.
+      transitions_done  (chains,)       completed timed transitions per chain (0: failed)
+    Data, start states and every chain's random streams follow from the arguments alone and the
+    schedule does not depend on the clock, so two runs with the same arguments write the same
+    arrays. With --gpus N > 1 every rank writes its own chains as <name>_rank<r>.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    keep = min(a.steps, max(1, DUMP_MAX_BYTES // (8 * a.chains * P)))
+    first = a.steps - keep
+    th = np.full((a.chains, keep, P), np.nan)
+    for c in range(a.chains):
+        if run['done'][c] >= a.steps:
+            th[c] = np.array(run['traces'][c][first:a.steps])
+    suffix = '' if dist.world == 1 else '_rank{0}'.format(dist.rank)
+    np.save(os.path.join(dirname, 'thetas' + suffix + '.npy'), th)
+    np.save(os.path.join(dirname, 'transitions_done' + suffix + '.npy'),
+            np.asarray(run['done'], dtype=np.float64))
 
 
 def main():
@@ -834,6 +873,8 @@ def main():
     transitions, value = run['transitions'], run['value']
     n_th, n_u, call_ops, wall = run['n_th'], run['n_u'], run['call_ops'], run['wall']
     series = run['series']
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, dist, a, run, P)
 
     prof = {}
     for k, name in ((_native.PROF_GRAM, 'gram'), (_native.PROF_CHOL_UPDATE_OUTER, 'chol_update'),
@@ -936,24 +977,27 @@ def main():
         if mf:
             extra['roofline_lu']['mfma_busy'] = mf
 
-    # ESS: extend the same chains (untimed) until each has >= ess-min transitions after the
-    # burn-in, then ESS per transition x the timed transitions/s (ess_block)
-    burn = max(a.ess_burn, a.warmup)
-    need = np.array([0 if smp.failed[c] else max(0, burn + a.ess_min - len(series[c]))
-                     for c in range(a.chains)], dtype=np.int64)
-    t_ext = time.perf_counter()
-    if need.max() > 0:
-        etr, _ = smp.run_async(need)
-        for c in range(a.chains):
-            series[c].extend(etr[c])
-    t_ext = time.perf_counter() - t_ext
+    # ESS (--full): extend the same chains (untimed) until each has >= ess-min transitions after
+    # the burn-in, then ESS per transition x the timed transitions/s (ess_block)
+    ess = {'ess_per_sec': None, 'ess_mean_per_sec': None, 'rhat': None, 'sample': None}
+    if a.full:
+        burn = max(a.ess_burn, a.warmup)
+        need = np.array([0 if smp.failed[c] else max(0, burn + a.ess_min - len(series[c]))
+                         for c in range(a.chains)], dtype=np.int64)
+        t_ext = time.perf_counter()
+        if need.max() > 0:
+            etr, _ = smp.run_async(need)
+            for c in range(a.chains):
+                series[c].extend(etr[c])
+        t_ext = time.perf_counter() - t_ext
+        failed_mask = smp.failed
+        ess = ess_block(dist, types.SimpleNamespace(n_chains=a.chains, failed=failed_mask),
+                        series, done, burn, elapsed, P)
+        ess['sample']['untimed_extension_s_rank0'] = t_ext
+        ess["sample"]["timed_transitions_per_chain_min"] = int(-dist.max(
+            -(done[~failed_mask].min() if (~failed_mask).any() else 0)))
+        ess['sample']['timed_transitions_per_chain_max'] = int(dist.max(done.max()))
     failed_mask = smp.failed
-    ess = ess_block(dist, types.SimpleNamespace(n_chains=a.chains, failed=failed_mask), series,
-                    done, burn, elapsed, P)
-    ess['sample']['untimed_extension_s_rank0'] = t_ext
-    ess["sample"]["timed_transitions_per_chain_min"] = int(-dist.max(
-        -(done[~failed_mask].min() if (~failed_mask).any() else 0)))
-    ess['sample']['timed_transitions_per_chain_max'] = int(dist.max(done.max()))
     failed = int(dist.sum(int(failed_mask.sum())))
     local_failed = int(failed_mask.sum())
     smp.close()  # frees the chains' workspaces before the next context
@@ -962,7 +1006,7 @@ def main():
     # E-SS+RD-SS.ipynb:198-201): its first transitions need ~4 Newton iterations per theta-call
     # against 7-8 at stationarity, so it runs faster than the chains a long run is made of
     prior_init = None
-    if th_stat is not None:
+    if a.full and th_stat is not None:
         smp2, run2 = run_chains(a, dist, dev, X, y, None, measure=False)
         prior_init = {'value': run2['value'], 'transitions_timed': int(run2['transitions']),
                       'ms_per_step': 1e3 * run2['elapsed'] / a.steps,
@@ -975,19 +1019,21 @@ def main():
                       'failed_chains': int(dist.sum(int(smp2.failed.sum())))}
         smp2.close()
 
-    sys.path.insert(0, os.path.join(REPO, 'oracle'))
-    cpu, first = None, None
-    thetas_par, fix_rows, U1, U2 = parity_inputs(a.n, a.d, a.n_imp)
-    if a.cpu_baseline and dist.rank == 0 and dist.world == 1:
-        # (N = 1 only, as the bench contract asks; rank 0 alone: a failure here must not strand
-        # the others in the parity check)
-        try:
-            cpu, first = cpu_baseline(X, y, a.n_imp, thetas_par[0], n_th, n_u, a.cpu_budget,
-                                      U1, U2)
-            cpu['gpu_over_cpu_per_chain'] = (value / (a.chains * dist.world)) / cpu['value']
-        except Exception as e:  # noqa: BLE001
-            cpu, first = {'error': repr(e)}, None
-    parity = parity_check(dist, X, y, a, thetas_par, fix_rows, U1, U2, first) if a.parity else None
+    cpu, first, parity = None, None, None
+    if a.full:
+        sys.path.insert(0, os.path.join(REPO, 'oracle'))
+        thetas_par, fix_rows, U1, U2 = parity_inputs(a.n, a.d, a.n_imp)
+        if a.cpu_baseline and dist.rank == 0 and dist.world == 1:
+            # (N = 1 only, as the bench contract asks; rank 0 alone: a failure here must not
+            # strand the others in the parity check)
+            try:
+                cpu, first = cpu_baseline(X, y, a.n_imp, thetas_par[0], n_th, n_u, a.cpu_budget,
+                                          U1, U2)
+                cpu['gpu_over_cpu_per_chain'] = (value / (a.chains * dist.world)) / cpu['value']
+            except Exception as e:  # noqa: BLE001
+                cpu, first = {'error': repr(e)}, None
+        if a.parity:
+            parity = parity_check(dist, X, y, a, thetas_par, fix_rows, U1, U2, first)
 
     # per-rank record: device, chains, transitions, elapsed, failures and the device counters of
     # the timed run (8 distinct devices, even load, no silent spin exits)
@@ -1003,7 +1049,7 @@ def main():
     stationary = th_stat is not None
     line = {
         'metric': METRIC, 'value': value, 'unit': 'transitions/s (all chains, all GPUs)',
-        'n_gpus': dist.world, 'steps': a.steps, 'warmup': a.warmup,
+        'n_gpus': dist.world, 'steps': a.steps, 'warmup': a.warmup, 'full': a.full,
         'ms_per_step': 1e3 * elapsed / a.steps,
         'ms_per_step_note': 'timed wall time / --steps; under the asynchronous schedule every '
                             'chain completes >= --steps transitions (chains ahead keep working), '
@@ -1032,7 +1078,8 @@ def main():
                                    'prior draws (E-SS+RD-SS.ipynb:198-201): {0}'.format(stat_src))},
         'value_prior_init': prior_init,
         'ess_per_sec': ess['ess_per_sec'], 'ess_mean_per_sec': ess['ess_mean_per_sec'],
-        'ess_per_sec_source': 'in-run sample of this run\'s chains (ess_sample)',
+        'ess_per_sec_source': ('in-run sample of this run\'s chains (ess_sample)' if a.full else
+                               'none: the in-run sample is taken with --full'),
         'ess_per_sec_in_run': ess['ess_per_sec'], 'ess_mean_per_sec_in_run': ess['ess_mean_per_sec'],
         'rhat': ess['rhat'], 'ess_sample': ess['sample'],
         'parity': parity,

@@ -56,6 +56,30 @@ def test_long_chain_record_and_provenance():
     assert prov['this_csrc_sha16'] == sha and prov['stale'] == (prov['profiled_csrc_sha16'] != sha)
 
 
+def test_dump_outputs_first_steps_of_every_chain(tmp_path, monkeypatch):
+    """--dump-outputs: float64 thetas (chains, --steps, P) = each chain's first --steps timed
+    transitions (what chains ahead did beyond them is left out, a failed chain's rows are NaN)
+    and transitions_done; a trace too long for the size cap keeps its last transitions."""
+    bench = _bench()
+    C, K, P = 3, 4, 2
+    traces = [[np.full(P, 10. * c + t) for t in range(K + c)] for c in range(C)]
+    traces[1] = traces[1][:2]  # chain 1 failed after two transitions
+    run = {'traces': traces, 'done': np.array([K, 0, K + 2])}
+    a = types.SimpleNamespace(chains=C, steps=K)
+    bench.dump_outputs(str(tmp_path / 'd'), bench.Dist(), a, run, P)
+    th = np.load(tmp_path / 'd' / 'thetas.npy')
+    assert th.dtype == np.float64 and th.shape == (C, K, P)
+    np.testing.assert_array_equal(th[0, :, 0], np.arange(K))
+    np.testing.assert_array_equal(th[2, :, 1], 20. + np.arange(K))
+    assert np.isnan(th[1]).all()
+    done = np.load(tmp_path / 'd' / 'transitions_done.npy')
+    assert done.dtype == np.float64 and done.tolist() == [K, 0, K + 2]
+    monkeypatch.setattr(bench, 'DUMP_MAX_BYTES', 8 * C * P * 2)  # room for two transitions
+    bench.dump_outputs(str(tmp_path / 'd'), bench.Dist(), a, run, P)
+    th2 = np.load(tmp_path / 'd' / 'thetas.npy')
+    np.testing.assert_array_equal(th2, th[:, K - 2:])
+
+
 def test_parity_inputs_match_reference_fixture():
     """The bench's parity thetas and draws are the ones tests/golden/config2_ref.npz holds the
     reference's outputs for (so that the bench can compare against the reference itself),

@@ -2,7 +2,8 @@
 one process per rank, each with its own device context and chain seeds), both pinned to the
 box's single GPU with APM_DEVICE=0 (on an 8-GPU node each rank takes GPU LOCAL_RANK). The rank-0
 JSON line must aggregate both ranks: n_gpus 2, transitions summed, no failed chain, and a
-max-over-ranks time. Also BASELINE.json configs[3]'s per-rank share (64 chains at N=4096 per
+max-over-ranks time (a `--full` run: ESS sample and parity block included); a plain one-rank
+run leaves those out and writes its `--dump-outputs` arrays. Also BASELINE.json configs[3]'s per-rank share (64 chains at N=4096 per
 GPU) for ranks 0..7 is exercised by the bench itself; here the 8 rank seeds are checked for
 disjoint streams and one chain of two different ranks' batches for state consistency."""
 import json
@@ -19,16 +20,25 @@ pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_bench_two_ranks_on_one_gpu(gpu_available):
+def test_bench_two_ranks_on_one_gpu(gpu_available, tmp_path):
     env = dict(os.environ, APM_DEVICE='0', MASTER_ADDR='127.0.0.1')
     out = subprocess.run(
         [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node=2',
          '--master-addr', '127.0.0.1', '--master-port', '29561', os.path.join(REPO, 'bench.py'),
          '--gpus', '2', '--steps', '4', '--warmup', '1', '--chains', '4', '--n-data', '1024',
-         '--n-features', '8', '--n-imp', '32', '--cpu-baseline', '0'],
+         '--n-features', '8', '--n-imp', '32', '--full', '--cpu-baseline', '0',
+         '--dump-outputs', str(tmp_path)],
         capture_output=True, text=True, env=env, timeout=500, cwd=REPO)
     assert out.returncode == 0, out.stdout[-4000:] + out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])
+    # --dump-outputs: every rank's chains, the first --steps timed transitions of each
+    th = [np.load(tmp_path / 'thetas_rank{0}.npy'.format(r)) for r in (0, 1)]
+    assert th[0].shape == th[1].shape == (4, 4, 9) and th[0].dtype == np.float64
+    assert np.isfinite(th[0]).all() and np.isfinite(th[1]).all()
+    assert not np.array_equal(th[0], th[1])  # (distinct rank seeds)
+    for r in (0, 1):
+        done = np.load(tmp_path / 'transitions_done_rank{0}.npy'.format(r))
+        assert done.shape == (4,) and (done >= 4).all()
     assert line['n_gpus'] == 2 and line['config']['global_batch'] == 8
     assert line['failed_chains'] == 0
     assert line['transitions_timed'] >= 2 * 4 * 4
@@ -39,6 +49,31 @@ def test_bench_two_ranks_on_one_gpu(gpu_available):
     assert line['parity']['vs_reference']['used'] is False  # N=1024: not the fixture's workload
     assert [r['rank'] for r in line['ranks']] == [0, 1]
     assert sum(r['transitions'] for r in line['ranks']) == line['transitions_timed']
+
+
+def test_bench_plain_run_times_and_dumps_only(gpu_available, tmp_path):
+    """A plain run (no --full) prints the headline keys, leaves what --full adds null, and
+    --dump-outputs writes the timed call's arrays; --steps sets the timed transitions."""
+    out = subprocess.run(
+        [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '3',
+         '--warmup', '1', '--chains', '4', '--n-data', '1024', '--n-features', '8', '--n-imp',
+         '32', '--dump-outputs', str(tmp_path / 'out')],
+        capture_output=True, text=True, timeout=300, cwd=REPO)
+    assert out.returncode == 0, out.stdout[-4000:] + out.stderr[-2000:]
+    line = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])
+    assert line['full'] is False and line['steps'] == 3 and line['warmup'] == 1
+    assert line['value'] > 0 and line['ms_per_step'] > 0 and line['higher_is_better'] is True
+    assert line['unit'].startswith('transitions/s') and line['dtype'] == 'mixed f64/f32'
+    # ms_per_step = timed wall time / --steps, value = timed transitions / that wall time
+    assert np.isclose(line['value'] * line['ms_per_step'] * 1e-3 * 3, line['transitions_timed'])
+    assert line['failed_chains'] == 0 and line['transitions_timed'] >= 4 * 3
+    for k in ('parity', 'cpu_baseline', 'value_prior_init', 'ess_sample', 'rhat',
+              'ess_per_sec_in_run'):
+        assert line[k] is None, k
+    th = np.load(tmp_path / 'out' / 'thetas.npy')
+    done = np.load(tmp_path / 'out' / 'transitions_done.npy')
+    assert th.shape == (4, 3, 9) and th.dtype == np.float64 and np.isfinite(th).all()
+    assert (done >= 3).all() and done.sum() == line['transitions_timed']
 
 
 def test_config3_rank_shares_consistent(gpu_available):
