@@ -57,10 +57,20 @@ def test_is_estimator_max_iters_status(nat):
     ctx.close()
 
 
-def test_chol_k_failure_raises_linalgerror(nat):
+@pytest.mark.parametrize('mixed', [None, '0'], ids=['mixed-default', 'mixed-0'])
+def test_chol_k_failure_raises_linalgerror(nat, monkeypatch, mixed):
+    """Under the default mixed-precision Newton path and under the all-fp64 one (APM_MIXED=0)."""
+    if mixed is not None:
+        monkeypatch.setenv('APM_MIXED', mixed)
     e = golden('errors')
     assert str(e['cholk_raised']) == 'LinAlgError'
     X, y, ns = e['extreme_X'], e['extreme_y'], e['extreme_ns']
+    ctx = nat.Context(X, y, nat.KERNEL_ISO, 1e-8, ns.shape[1], max_batch=1, n_slots=1, n_ubufs=1)
+    ctx.u_upload(0, ns)
+    for kind in (nat.EST_IS, nat.EST_PRIORMC):
+        _, st, _ = ctx.theta_eval(kind, e['cholk_theta'][None], [0], [0])
+        assert st[0] == nat.STATUS_CHOL_K, (kind, st)
+    ctx.close()
     es = est.LogMarginalLikelihoodApproxPosteriorISEstimator(
         X, y, krn.make_kernel_func('iso', 1e-8), lpa.laplace_approximation)
     with pytest.raises(np.linalg.LinAlgError):

@@ -275,7 +275,8 @@ def test_u_normal_moments(nat):
 
 @pytest.mark.parametrize('n,d,s,kind', [(700, 5, 32, 'ard'), (1100, 3, 8, 'iso')])
 def test_estimators_multi_panel_vs_oracle(nat, n, d, s, kind):
-    """N spanning several 256-column outer panels (the rank-256 update path) vs the oracle."""
+    """N spanning several 512-column (8 x 64) outer panels (the rank-512 update path) vs the
+    oracle."""
     from gpdemo import utils
     X, y = utils.synthetic_gp_data(n, d, 99 + n, kind)
     rng = np.random.RandomState(n)
