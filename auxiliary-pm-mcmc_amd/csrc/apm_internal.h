@@ -197,6 +197,28 @@ void launch_gram(MatB K, const double* X, int64_t ldx, int n, int d, const doubl
                  int64_t tstride, int kind, double eps, int np, Live live, int nchains,
                  hipStream_t s, bool both, MatB K2 = MatB{nullptr, 0, 0}, int k2cols = 1 << 30);
 
+// ---- predict.hip: Laplace predictive at test inputs -----------------------
+// Cross-covariance of the ms test points Xs (row-major, ld = d) against the n training points,
+// k*_rc = s exp(-1/2 sum_k ((xs_rk - x_ck)/tau_k)^2) (no epsilon: kernels.pyx adds it for i == j
+// of one point set only; s = sig[b] = exp(theta_0) computed by the host), for the 64-row tiles [0, mb) of the block, k_gram's arithmetic.
+// plain == 0 (the predictive path): chain b's A rows [row0, row0 + 64 mb), columns [0, 64 nb),
+// <- k*_rc Ws[c], exact zeros for rows >= ms and columns >= n; part[b * pstride + tj * 64 mb + r]
+// <- sum of k*_rc a_c over the columns of tile column tj (summed in order by k_predict_reduce).
+// plain != 0 (apm_gram_cross): out.base[r * out.ld + c] <- k*_rc for r < ms, c < n, one chain,
+// nothing else is touched (Ws, a, part, live may be null).
+void launch_gram_cross(MatB out, int64_t row0, const double* Xs, int ms, int mb, const double* X,
+                       int64_t ldx, int n, int d, int nb, const double* theta, int64_t tstride,
+                       const double* sig, int kind, const double* Ws, const double* a,
+                       int64_t vstride, double* part, int64_t pstride, Live live, int plain,
+                       int nchains, hipStream_t s);
+// per chain and test row r < ms: mean = sum_tj part[tj][r] (in order), var = sig[b] - |row r of V^T|^2
+// over columns [0, 64 nb) of A's rows [row0, ..), prob = Phi(mean / sqrt(1 + var)); each output
+// out[b * ostride + r]. Nothing is clamped.
+void launch_predict_reduce(MatB A, int64_t row0, int ms, int mb, int nb, const double* sig,
+                           const double* part, int64_t pstride, double* mean,
+                           double* var, double* prob, int64_t ostride, Live live, int nchains,
+                           hipStream_t s);
+
 // ---- newton.hip -----------------------------------------------------------------------------
 struct NewtonVecs {     // all per chain, stride vstride (>= np)
     double* f;          // current mode estimate

@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <functional>
+#include <limits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -200,6 +201,11 @@ struct apm_ctx {
     // the Gram wrote only the first outer panel's tile columns into chol(K)'s working copy: the
     // first trailing update then reads its old tiles from K (out of place, k_chol_update_t128 S)
     bool cholk_partial = false;
+    // the predictive path (apm_predict), allocated at its first call: one block of test inputs
+    // (np x d), the mu* partials (max_batch x nb x np), the three outputs (max_batch x np each) and
+    // behind them the chains' s = exp(theta_0) as the host computes it (max_batch)
+    double *pxs = nullptr, *ppart = nullptr, *pmean = nullptr, *pvar = nullptr, *pprob = nullptr;
+    double* psig = nullptr;
 };
 
 // ------------------------------------------------------------------------------- APM_SKEW
@@ -930,6 +936,38 @@ void augmented(apm_ctx* c, int count) {
     check_launch();
     const int nb = c->nb, R = 2 * nb + 1, Cb = 2 * nb;
     chol_range(c, c->A, 0, nb, R, Cb, APM_STATUS_CHOL_B, count, /*factor_diag=*/false, /*rows>=*/nb);
+}
+
+// Laplace predictive (predict.hip) of one block of ms <= np test inputs (packed
+// ms x d at xs) for the chains left live by an fp64 Laplace theta-call: W^1/2 . k* into the free
+// rows [np, np + 64 mb) of A and mu*'s partials, the panel solves and rank-256 updates of those
+// rows against the last Newton factor (as augmented(), without the bottom-right SYRK), the row
+// reduction; outputs in pmean / pvar / pprob (row stride np). predict_buffers() first.
+void predict_buffers(apm_ctx* c) {
+    if (c->pxs) return;
+    const int64_t np = c->np, B = c->max_batch;
+    c->pxs = dalloc<double>(c, np * std::max(c->d, 1));
+    c->ppart = dalloc<double>(c, B * c->nb * np);
+    c->pmean = dalloc<double>(c, 3 * B * np + B);
+    c->pvar = c->pmean + B * np;
+    c->pprob = c->pvar + B * np;
+    c->psig = c->pprob + B * np;
+}
+
+void predict_block(apm_ctx* c, int count, const double* xs, int ms) {
+    const Live lv = live_of(c);
+    const int nb = c->nb, mb = (ms + 63) / 64;
+    const int64_t np = c->np;
+    HIPC(hipMemcpyAsync(c->pxs, xs, sizeof(double) * ms * c->d, hipMemcpyHostToDevice, c->stream));
+    launch_gram_cross(c->A, np, c->pxs, ms, mb, c->X, c->d, c->n, c->d, nb, c->theta, c->P,
+                      c->psig, c->kind, c->v.Ws, c->v.a, c->v.vstride, c->ppart, nb * np, lv, 0,
+                      count, c->stream);
+    check_launch();
+    chol_range(c, c->A, 0, nb, /*R=*/nb + mb, /*Cb=*/nb, APM_STATUS_CHOL_B, count,
+               /*factor_diag=*/false, /*row_start=*/nb);
+    launch_predict_reduce(c->A, np, ms, mb, nb, c->psig, c->ppart, nb * np, c->pmean,
+                          c->pvar, c->pprob, np, lv, count, c->stream);
+    check_launch();
 }
 
 // Posterior-covariance factor through chol(K) (postcov.hip): 4N^3/3 flops instead of the
@@ -1917,6 +1955,104 @@ int apm_gram(int device, int kind, const double* X, int64_t n, int64_t d, int64_
             c = nullptr;
         }
         return fail(nullptr, APM_E_HIP, e.msg);
+    }
+    return APM_SUCCESS;
+}
+
+int apm_gram_cross(int device, int kind, const double* Xs, int64_t m, const double* X, int64_t n,
+                   int64_t d, int64_t ldx, const double* theta, int64_t n_theta, double* Ks,
+                   int64_t ldk) {
+    if (m <= 0 || n <= 0 || d <= 0 || !Xs || !X || !theta || !Ks || ldk < n || ldx < d ||
+        m > (1 << 24) || n > (1 << 24) || (kind != APM_KERNEL_ISO && kind != APM_KERNEL_ARD))
+        return fail(nullptr, APM_E_INVALID, "apm_gram_cross: bad arguments");
+    const int64_t P = kind == APM_KERNEL_ISO ? 2 : d + 1;
+    if (n_theta < P) return fail(nullptr, APM_E_INVALID, "apm_gram_cross: theta too short");
+    double* dev = nullptr;  // [X: n x d][Xs: m x d][theta: P][s][Ks: m x n]
+    try {
+        HIPC(hipSetDevice(device));
+        std::vector<double> h((size_t)((n + m) * d + P + 1));  // (+ s = exp(theta_0))
+        for (int64_t i = 0; i < n + m; ++i)  // both point sets take the row stride ldx
+            for (int64_t k = 0; k < d; ++k)
+                h[i * d + k] = i < n ? X[i * ldx + k] : Xs[(i - n) * ldx + k];
+        for (int64_t p = 0; p < P; ++p) h[(n + m) * d + p] = theta[p];
+        h[(n + m) * d + P] = std::exp(theta[0]);
+        HIPC(hipMalloc(reinterpret_cast<void**>(&dev), sizeof(double) * (h.size() + m * n)));
+        HIPC(hipMemcpy(dev, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
+        double* dK = dev + h.size();
+        launch_gram_cross(MatB{dK, n, 0}, 0, dev + n * d, (int)m, (int)((m + 63) / 64), dev, d,
+                          (int)n, (int)d, (int)((n + 63) / 64), dev + (n + m) * d, 0,
+                          dev + (n + m) * d + P, kind, nullptr, nullptr, 0, nullptr, 0,
+                          Live{nullptr, nullptr}, 1, 1, nullptr);
+        check_launch();
+        HIPC(hipMemcpy2D(Ks, sizeof(double) * ldk, dK, sizeof(double) * n, sizeof(double) * n, m,
+                         hipMemcpyDeviceToHost));
+        HIPC(hipFree(dev));
+    } catch (const HipError& e) {
+        if (dev) (void)hipFree(dev);
+        return fail(nullptr, APM_E_HIP, e.msg);
+    }
+    return APM_SUCCESS;
+}
+
+int apm_predict(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, const double* Xs,
+                int64_t m, int64_t ldxs, double* mean, double* var, double* prob, int64_t ldo,
+                int* status, int64_t* n_iter) {
+    if (!c) return fail(nullptr, APM_E_INVALID, "apm_predict: null context");
+    if (c->kind == APM_KERNEL_PRECOMPUTED)
+        return fail(c, APM_E_INVALID, "apm_predict: needs an ISO or ARD context (the cross-"
+                                      "covariance is built on the device)");
+    if (m <= 0) return fail(c, APM_E_INVALID, "apm_predict: m <= 0");
+    if (count <= 0 || count > c->max_batch)
+        return fail(c, APM_E_INVALID, "apm_predict: count outside [1, max_batch]");
+    if (ldo < m) return fail(c, APM_E_INVALID, "apm_predict: ldo < m");
+    if (!thetas || !Xs || !status || ldt < c->P || ldxs < c->d)
+        return fail(c, APM_E_INVALID, "apm_predict: bad arguments");
+    const SkewScope skew(c);
+    try {
+        HIPC(hipSetDevice(c->device));
+        double* th = c->hth;  // pinned: the upload is asynchronous
+        for (int64_t b = 0; b < count; ++b)
+            for (int p = 0; p < c->P; ++p) th[b * c->P + p] = thetas[b * ldt + p];
+        HIPC(hipMemcpyAsync(c->theta, th, sizeof(double) * count * c->P, hipMemcpyHostToDevice,
+                            c->stream));
+        // Gram and the fp64 Newton loop of the Laplace theta-call: L, inv(L_kk), W^1/2, a of each
+        // chain's last iteration stay in A / Dinv / the Newton vectors
+        std::vector<double> lml((size_t)count);
+        theta_eval_impl(c, APM_EST_LAPLACE, (int)count, true, lml.data(), status, n_iter);
+        int ok = 0;
+        for (int64_t b = 0; b < count; ++b) ok += status[b] == APM_STATUS_OK;
+        if (ok) {
+            // converged chains left the Newton loop with active = 0 (as augmented())
+            HIPC(hipMemsetD32Async(c->active, 1, count, c->stream));
+            c->live_n = ok;
+            predict_buffers(c);
+            std::vector<double> xs, sig((size_t)count);  // (alive until the blocks' syncs)
+            for (int64_t b = 0; b < count; ++b) sig[b] = std::exp(thetas[b * ldt]);
+            HIPC(hipMemcpyAsync(c->psig, sig.data(), sizeof(double) * count, hipMemcpyHostToDevice,
+                                c->stream));
+            for (int64_t r0 = 0; r0 < m; r0 += c->np) {  // blocks of the free rows of A
+                const int ms = (int)std::min<int64_t>(c->np, m - r0);
+                xs.resize((size_t)ms * c->d);
+                for (int i = 0; i < ms; ++i)
+                    for (int k = 0; k < c->d; ++k) xs[(size_t)i * c->d + k] = Xs[(r0 + i) * ldxs + k];
+                predict_block(c, (int)count, xs.data(), ms);
+                const std::pair<double*, const double*> outs[3] = {
+                    {mean, c->pmean}, {var, c->pvar}, {prob, c->pprob}};
+                for (const auto& o : outs)
+                    if (o.first)
+                        HIPC(hipMemcpy2DAsync(o.first + r0, sizeof(double) * ldo, o.second,
+                                              sizeof(double) * c->np, sizeof(double) * ms, count,
+                                              hipMemcpyDeviceToHost, c->stream));
+                sync(c);  // (xs is reused by the next block)
+            }
+        }
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        for (int64_t b = 0; b < count; ++b)
+            if (status[b] != APM_STATUS_OK)
+                for (double* o : {mean, var, prob})
+                    if (o) std::fill(o + b * ldo, o + b * ldo + m, nan);
+    } catch (const HipError& e) {
+        return fail(c, APM_E_HIP, e.msg);
     }
     return APM_SUCCESS;
 }

@@ -1,0 +1,191 @@
+// Laplace predictive distribution at test inputs: the two kernels around the
+// panel solves that capi.cpp's predict_block borrows from the Cholesky (chol_range on the test
+// rows only).
+//
+//   k*_c = s exp(-1/2 sum_k ((x*_k - x_ck)/tau_k)^2)   no epsilon: kernels.pyx adds it to the
+//                                                       i == j entries of ONE point set only
+//   mu*  = k*^T a,   v = L^-1 (W^1/2 . k*),   var* = s - v^T v   (prior variance k** = s)
+//   pi*  = Phi(mu* / sqrt(1 + var*))
+// with W, L, a of the last Newton iteration (latent_posterior_approximations.py:81-112).
+#include "apm_internal.h"
+
+#define GK 32         // features per LDS chunk (k_gram's)
+#define GP (128 + 2)  // LDS row pitch in doubles (k_gram's)
+// lane (g = lane >> 3 or lane & 7) -> its 8 rows (columns) of the wave's 64x64 tile (k_gram's)
+#define R8(g, p) (((p) >> 2) * 32 + 4 * (g) + ((p) & 3))
+
+// Rectangular twin of k_gram: one workgroup of 4 waves per 128x128 super-tile (si over the test
+// rows, sj over the training columns), wave w the 64x64 tile (2si + w/2, 2sj + w%2), 8x8 pairs per
+// lane, features pre-scaled by 1/tau_k while staged through LDS in chunks of GK and summed over k
+// in order - the arithmetic of k_gram. s = exp(theta_0) comes from the host (sig[b], libm's exp,
+// the same value in k* and in the prior variance k** of k_predict_reduce), so an uninformed test
+// point returns bitwise the caller's exp(theta_0); K's own s is the device's exp and may differ
+// from it in the last bit. Every (row, column) value depends on its own pair of points only, and
+// the partial sums of mu* on the column position only: a chain's outputs do not depend on its
+// batch nor a test point's on its block.
+__global__ __launch_bounds__(256, 2) void k_gram_cross(
+    MatB out, int64_t row0, const double* __restrict__ Xs, int ms, int mb,
+    const double* __restrict__ X, int64_t ldx, int n, int d, int nb,
+    const double* __restrict__ theta, int64_t tstride, const double* __restrict__ sig, int kind,
+    const double* __restrict__ Ws, const double* __restrict__ avec, int64_t vstride,
+    double* __restrict__ part, int64_t pstride, Live live, int plain) {
+    const int b = blockIdx.y;
+    if (live.active && (live.active[b] == 0 || live.status[b] != 0)) return;
+    const int nsc = (nb + 1) / 2;
+    const int si = blockIdx.x / nsc, sj = blockIdx.x % nsc;
+
+    __shared__ __attribute__((aligned(16))) double xi[GK][GP];
+    __shared__ __attribute__((aligned(16))) double xj[GK][GP];
+    __shared__ double itau[GK];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tr = lane >> 3, tc = lane & 7;
+    const int ti = 2 * si + (wv >> 1), tj = 2 * sj + (wv & 1);
+    const bool mine = ti < mb && tj < nb;  // (wave-uniform)
+    const int ro = 64 * (wv >> 1), co = 64 * (wv & 1);
+    const double* th = theta + b * tstride;
+    const double sigma = sig[b];
+
+    double acc[8][8];
+#pragma unroll
+    for (int p = 0; p < 8; ++p)
+#pragma unroll
+        for (int q = 0; q < 8; ++q) acc[p][q] = 0.0;
+
+    for (int k0 = 0; k0 < d; k0 += GK) {
+        const int kc = min(GK, d - k0);
+        __syncthreads();
+        if (tid < kc) itau[tid] = exp(-th[kind == 0 ? 1 : 1 + k0 + tid]);
+        __syncthreads();
+        for (int e = tid; e < 128 * GK; e += 256) {
+            const int r = e / GK, k = e % GK;  // consecutive lanes: consecutive features of a row
+            const int gi = si * 128 + r, gj = sj * 128 + r;
+            const double sc = (k < kc) ? itau[k] : 0.0;
+            xi[k][r] = (k < kc && gi < ms) ? Xs[(int64_t)gi * d + k0 + k] * sc : 0.0;
+            xj[k][r] = (k < kc && gj < n) ? X[(int64_t)gj * ldx + k0 + k] * sc : 0.0;
+        }
+        __syncthreads();
+        if (mine) {
+            for (int k = 0; k < kc; ++k) {
+                double a[8], c[8];
+#pragma unroll
+                for (int h = 0; h < 4; ++h) {
+                    const d2_t va = *reinterpret_cast<const d2_t*>(&xi[k][ro + R8(tr, 2 * h)]);
+                    const d2_t vc = *reinterpret_cast<const d2_t*>(&xj[k][co + R8(tc, 2 * h)]);
+                    a[2 * h] = va.x;
+                    a[2 * h + 1] = va.y;
+                    c[2 * h] = vc.x;
+                    c[2 * h + 1] = vc.y;
+                }
+#pragma unroll
+                for (int p = 0; p < 8; ++p) {
+                    double df[8];
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) df[q] = a[p] - c[q];  // pre-scaled by 1/tau_k
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) acc[p][q] = fma(df[q], df[q], acc[p][q]);
+                }
+            }
+        }
+    }
+    if (!mine) return;  // (after the last barrier)
+
+#pragma unroll
+    for (int p = 0; p < 8; ++p)
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int gi = ti * 64 + R8(tr, p), gj = tj * 64 + R8(tc, q);
+            acc[p][q] = (gi < ms && gj < n) ? sigma * exp(-0.5 * acc[p][q]) : 0.0;
+        }
+
+    if (plain) {  // apm_gram_cross: k* itself into an ms x n buffer (any ld: scalar stores)
+#pragma unroll
+        for (int p = 0; p < 8; ++p)
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int gi = ti * 64 + R8(tr, p), gj = tj * 64 + R8(tc, q);
+                if (gi < ms && gj < n) out.base[(int64_t)gi * out.ld + gj] = acc[p][q];
+            }
+        return;
+    }
+
+    // mu* partial of this tile: each lane its 8 columns in order, then the row's 8 lanes in a
+    // fixed butterfly; the tile columns are summed in order by k_predict_reduce. Then W^1/2 . k*
+    // into the work matrix (whole tiles: zeros beyond the data, the panel solves read them).
+    const double* ab = avec + b * vstride + tj * 64;
+    const double* wb = Ws + b * vstride + tj * 64;
+    double av[8], wq[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        av[q] = ab[R8(tc, q)];
+        wq[q] = wb[R8(tc, q)];
+    }
+    double* pb = part + b * pstride + (int64_t)tj * (64 * mb) + ti * 64;
+    double* Ab = out.base + b * out.cstride;
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+        double s = 0.0;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            s = fma(acc[p][q], av[q], s);
+            acc[p][q] *= wq[q];
+        }
+        s += __shfl_xor(s, 1, 64);
+        s += __shfl_xor(s, 2, 64);
+        s += __shfl_xor(s, 4, 64);
+        if (tc == 0) pb[R8(tr, p)] = s;
+        double* dst = Ab + (row0 + ti * 64 + R8(tr, p)) * out.ld + tj * 64 + 4 * tc;
+        *reinterpret_cast<d2_t*>(dst) = d2_t{acc[p][0], acc[p][1]};
+        *reinterpret_cast<d2_t*>(dst + 2) = d2_t{acc[p][2], acc[p][3]};
+        *reinterpret_cast<d2_t*>(dst + 32) = d2_t{acc[p][4], acc[p][5]};
+        *reinterpret_cast<d2_t*>(dst + 34) = d2_t{acc[p][6], acc[p][7]};
+    }
+}
+
+void launch_gram_cross(MatB out, int64_t row0, const double* Xs, int ms, int mb, const double* X,
+                       int64_t ldx, int n, int d, int nb, const double* theta, int64_t tstride,
+                       const double* sig, int kind, const double* Ws, const double* a,
+                       int64_t vstride, double* part, int64_t pstride, Live live, int plain,
+                       int nchains, hipStream_t s) {
+    const int nsr = (mb + 1) / 2, nsc = (nb + 1) / 2;
+    APM_LAUNCH(k_gram_cross, dim3(nsr * nsc, nchains), dim3(256), 0, s, out, row0, Xs, ms, mb, X,
+               ldx, n, d, nb, theta, tstride, sig, kind, Ws, a, vstride, part, pstride, live, plain);
+}
+
+// One wave per (chain, test row): the squared norm of the row of V^T = (W^1/2 . k*)^T L^-T over
+// the 64 nb columns (16-byte loads, consecutive lanes consecutive pieces; each lane its pieces in
+// order, then the wave's butterfly), mu* from the tile-column partials in order, and the probit
+// average through erfc, whose lower tail keeps its relative accuracy (Phi(z) = erfc(-z/sqrt2)/2).
+__global__ __launch_bounds__(256) void k_predict_reduce(
+    MatB A, int64_t row0, int ms, int mb, int nb, const double* __restrict__ sig,
+    const double* __restrict__ part, int64_t pstride, double* __restrict__ mean,
+    double* __restrict__ var, double* __restrict__ prob, int64_t ostride, Live live) {
+    const int b = blockIdx.y;
+    if (live.active[b] == 0 || live.status[b] != 0) return;
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= ms) return;
+    const double* row = A.base + b * A.cstride + (row0 + r) * A.ld;
+    double s = 0.0;
+    for (int c = 2 * lane; c < 64 * nb; c += 128) {
+        const d2_t v = *reinterpret_cast<const d2_t*>(row + c);
+        s = fma(v.x, v.x, s);
+        s = fma(v.y, v.y, s);
+    }
+    s = wave_sum_d(s);
+    if (lane != 0) return;
+    const double* pb = part + b * pstride + r;
+    double mu = 0.0;
+    for (int tj = 0; tj < nb; ++tj) mu += pb[(int64_t)tj * (64 * mb)];
+    const double v = sig[b] - s;
+    const double z = mu / sqrt(1.0 + v);
+    mean[b * ostride + r] = mu;
+    var[b * ostride + r] = v;
+    prob[b * ostride + r] = 0.5 * erfc(-z * 0.70710678118654752440);
+}
+
+void launch_predict_reduce(MatB A, int64_t row0, int ms, int mb, int nb, const double* sig,
+                           const double* part, int64_t pstride, double* mean,
+                           double* var, double* prob, int64_t ostride, Live live, int nchains,
+                           hipStream_t s) {
+    APM_LAUNCH(k_predict_reduce, dim3((ms + 3) / 4, nchains), dim3(256), 0, s, A, row0, ms, mb, nb,
+               sig, part, pstride, mean, var, prob, ostride, live);
+}

@@ -3,4 +3,5 @@
 
 Module layout mirrors the reference's ``gpdemo`` package: ``kernels`` (Gram builders),
 ``latent_posterior_approximations`` (Laplace), ``estimators`` (log-marginal-likelihood
-estimators), ``utils`` (priors, adaptation schedule, I/O)."""
+estimators), ``utils`` (priors, adaptation schedule, I/O); ``predict`` (the Laplace predictive
+distribution at held-out inputs) has no reference counterpart."""

@@ -62,6 +62,8 @@ _SIGS = {
     'apm_cache_release': (_i, [_p, _i64]),
     'apm_cache_refcount': (_i64, [_p, _i64]),
     'apm_gram': (_i, [_i, _i, _p, _i64, _i64, _i64, _p, _i64, _d, _p, _i64]),
+    'apm_gram_cross': (_i, [_i, _i, _p, _i64, _p, _i64, _i64, _i64, _p, _i64, _p, _i64]),
+    'apm_predict': (_i, [_p, _i64, _p, _i64, _p, _i64, _i64, _p, _p, _p, _i64, _p, _p]),
     'apm_laplace': (_i, [_i, _p, _i64, _i64, _p, _i, _i, _d, _i64, _p, _p, _i64, _p, _p, _p]),
     'apm_prof_enable': (_i, [_p, _i]),
     'apm_prof_marker': (_i, [_p, _i]),
@@ -139,6 +141,24 @@ def gram(kind, K, X, theta, epsilon, device=None):
     if out is not K:
         K[...] = out
     return None
+
+
+def gram_cross(kind, X_test, X, theta, device=None):
+    """(m, n) cross-covariance k(X_test_i, X_j) of the SE kernel on the GPU: no epsilon, also
+    where a test point coincides with a training point."""
+    lib = load_library()
+    X, Xs = _f64(X), _f64(X_test)
+    theta = _f64(np.atleast_1d(theta))
+    n, d = X.shape
+    if Xs.ndim != 2 or Xs.shape[1] != d:
+        raise ValueError('X_test has shape {0}, expected (m, {1})'.format(Xs.shape, d))
+    if theta.shape[0] < (2 if kind == KERNEL_ISO else d + 1):
+        raise IndexError('Out of bounds on buffer access (axis 0)')
+    Ks = np.empty((Xs.shape[0], n))
+    _check(lib.apm_gram_cross(default_device() if device is None else device, kind, _ptr(Xs),
+                              Xs.shape[0], _ptr(X), n, d, d, _ptr(theta), theta.shape[0],
+                              _ptr(Ks), n))
+    return Ks
 
 
 def laplace(K, y, calc_cov, calc_lml, diff_f_tol, max_iters, device=None):
@@ -322,6 +342,28 @@ class Context(object):
         _check(self.lib.apm_theta_eval_K(self._h, est, _ptr(K), K.shape[1], int(ubuf), int(slot),
                                          _ptr(out), _ptr(st), _ptr(nops)), self._h)
         return out, st, nops
+
+    def predict(self, thetas, X_test):
+        """Laplace predictive at X_test (m, d) for every row of thetas, `max_batch` at a time:
+        ``(mean, var, prob, status, n_iter)``, the first three (T, m) with NaN rows where
+        status != 0 (include/apm.h apm_predict)."""
+        th = np.atleast_2d(_f64(thetas))
+        if th.shape[1] < self.theta_len:
+            raise IndexError('Out of bounds on buffer access (axis 0)')
+        Xs = _f64(X_test)
+        if Xs.ndim != 2 or Xs.shape[1] != self.d:
+            raise ValueError('X_test has shape {0}, expected (m, {1})'.format(Xs.shape, self.d))
+        T, m = th.shape[0], Xs.shape[0]
+        mean, var, prob = (np.full((T, m), np.nan) for _ in range(3))
+        st = np.zeros(T, dtype=np.int32)
+        nit = np.zeros(T, dtype=np.int64)
+        for t0 in range(0, T, self.max_batch):
+            cnt = min(self.max_batch, T - t0)
+            _check(self.lib.apm_predict(
+                self._h, cnt, th[t0:].ctypes.data, th.shape[1], _ptr(Xs), m, self.d,
+                mean[t0:].ctypes.data, var[t0:].ctypes.data, prob[t0:].ctypes.data, m,
+                st[t0:].ctypes.data, nit[t0:].ctypes.data), self._h)
+        return mean, var, prob, st, nit
 
     def u_eval(self, slots, ubufs):
         sl = np.ascontiguousarray(slots, dtype=np.int64)

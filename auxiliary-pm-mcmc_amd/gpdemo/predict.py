@@ -1,0 +1,114 @@
+# -*- coding: utf-8 -*-
+"""Laplace predictive distribution of the probit GP classifier at held-out inputs, on the GPU.
+
+For a hyperparameter sample ``theta`` the Laplace fit of ``latent_posterior_approximations``
+(Newton quantities ``W``, ``L = chol(I + W^1/2 K W^1/2)``, ``a`` of the last iteration) gives at
+a test input ``x*`` the latent mean ``mu* = k*^T a``, the latent variance ``var* = k** -
+|L^-1 (W^1/2 . k*)|^2`` and the class probability ``pi* = Phi(mu* / sqrt(1 + var*))`` (Rasmussen
+& Williams, Alg. 3.2 with the probit's closed-form average). ``k*`` and ``k** = exp(theta_0)``
+carry no jitter: the reference's kernels add epsilon to the diagonal of one point set's Gram
+matrix only. The reference has no such function; everything runs in libapm.so (``apm_predict``,
+DESIGN.md §12) and nothing but theta and the test inputs crosses the host boundary.
+
+:class:`LaplacePredictor` evaluates a set of theta samples (e.g. a saved run's, see
+INTEGRATION.md); the array math on its outputs is in the module-level functions, which need no
+device.
+"""
+import numpy as np
+from scipy.special import log_ndtr
+
+from . import _native
+from .estimators import _kernel_spec, _raise_for_status
+
+__all__ = ['LaplacePredictor', 'posterior_average', 'log_predictive_density']
+
+
+def _keep(a, burn, thin):
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim != 2:
+        raise ValueError('expected a (T, M) array, got shape {0}'.format(a.shape))
+    a = a[int(burn)::int(thin)]
+    if a.shape[0] == 0:
+        raise ValueError('no samples left after burn / thin')
+    return a
+
+
+def posterior_average(prob, burn=0, thin=1):
+    """Hyperparameter-marginalised class probability: the mean of ``prob`` (T, M) over the kept
+    samples ``burn::thin``."""
+    return _keep(prob, burn, thin).mean(0)
+
+
+def log_predictive_density(mean, var, y_test, burn=0, thin=1):
+    """Test log predictive density per point: the mean over the M test points of
+    ``log(mean_t Phi(y* z_t))`` with ``z = mean / sqrt(1 + var)`` (T, M) and labels ``y*`` in
+    {-1, +1}. ``log Phi`` through ``log_ndtr`` and a log-mean-exp over the samples, so that
+    confident predictions neither underflow to ``-inf`` nor round to 0."""
+    z = _keep(mean, burn, thin) / np.sqrt(1.0 + _keep(var, burn, thin))
+    y = np.asarray(y_test, dtype=np.float64)
+    if y.shape != (z.shape[1],):
+        raise ValueError('y_test has shape {0}, expected ({1},)'.format(y.shape, z.shape[1]))
+    lp = log_ndtr(y[None, :] * z)
+    top = lp.max(0)
+    return float(np.mean(top + np.log(np.mean(np.exp(lp - top[None, :]), axis=0))))
+
+
+class LaplacePredictor(object):
+    """Predictive distribution at ``X_test`` (M, D) of the probit GP classifier trained on
+    ``(X, y)``, for batches of hyperparameter samples.
+
+    ``kernel_func`` must be one of the two device kernels (``gpdemo.kernels.make_kernel_func``):
+    the cross-covariance is built on the device, so a foreign callable raises
+    ``NotImplementedError``. ``diff_f_tol`` / ``max_iters`` are the Newton settings of
+    ``laplace_approximation``; ``max_batch`` thetas are fitted per device call.
+    """
+
+    def __init__(self, X, y, kernel_func, X_test, diff_f_tol=1e-4, max_iters=1000, max_batch=8,
+                 device=None):
+        kind, eps = _kernel_spec(kernel_func)
+        if kind == _native.KERNEL_PRECOMPUTED:
+            raise NotImplementedError(
+                'the device predictor builds the cross-covariance itself and needs one of '
+                'gpdemo.kernels.make_kernel_func("iso" | "ard"); got {0!r}'.format(kernel_func))
+        self.X = np.asarray(X, dtype=np.float64)
+        self.y = np.asarray(y, dtype=np.float64)
+        self.X_test = np.ascontiguousarray(X_test, dtype=np.float64)
+        if self.X_test.ndim != 2 or self.X_test.shape[1] != self.X.shape[1]:
+            raise ValueError('X_test has shape {0}, expected (M, {1})'
+                             .format(self.X_test.shape, self.X.shape[1]))
+        self.kernel_func = kernel_func
+        self.max_iters = int(max_iters)
+        # prediction uses neither cache slots nor U buffers: one of each, one draw
+        self._ctx = _native.Context(self.X, self.y, kind, eps, 1, max_batch=int(max_batch),
+                                    n_slots=1, n_ubufs=1, device=device)
+        self._ctx.set_newton(diff_f_tol, max_iters)
+        self.n_iter = None
+
+    def __call__(self, thetas, on_error='raise'):
+        """``(mean, var, prob)``, each (T, M), for thetas of shape (T, P) or (P,). A theta whose
+        Laplace fit fails raises the estimators' exception (``LinAlgError``,
+        ``MaximumIterationsExceededError``); with ``on_error='nan'`` its rows are NaN instead.
+        ``self.n_iter`` keeps the Newton iteration counts and ``self.status`` the status codes."""
+        if on_error not in ('raise', 'nan'):
+            raise ValueError("on_error must be 'raise' or 'nan'")
+        th = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
+        mean, var, prob, st, nit = self._ctx.predict(th, self.X_test)
+        self.n_iter, self.status = nit, st
+        if on_error == 'raise':
+            for s in st:
+                _raise_for_status(int(s), self._ctx, self.max_iters)
+        return mean, var, prob
+
+    def posterior_average(self, thetas, burn=0, thin=1, on_error='raise'):
+        """Class probabilities (M,) averaged over the kept theta samples."""
+        th = np.atleast_2d(np.asarray(thetas, dtype=np.float64))[int(burn)::int(thin)]
+        return posterior_average(self(th, on_error)[2])
+
+    def log_predictive_density(self, thetas, y_test, burn=0, thin=1, on_error='raise'):
+        """Mean test log predictive density of labels ``y_test`` (M,) in {-1, +1}."""
+        th = np.atleast_2d(np.asarray(thetas, dtype=np.float64))[int(burn)::int(thin)]
+        mean, var, _ = self(th, on_error)
+        return log_predictive_density(mean, var, y_test)
+
+    def close(self):
+        self._ctx.close()

@@ -7,6 +7,9 @@
  *
  *   apm_gram           <- gpdemo/kernels.pyx:12-49  isotropic_squared_exponential_kernel(K, X, theta, epsilon)
  *                         gpdemo/kernels.pyx:52-90  diagonal_squared_exponential_kernel(K, X, theta, epsilon)
+ *   apm_gram_cross     <- the same two kernels between two point sets (their i != j entries)
+ *   apm_predict        <- no reference counterpart: the Laplace predictive distribution at test
+ *                         inputs from the Newton quantities of laplace_approximation (:81-112)
  *   apm_laplace        <- gpdemo/latent_posterior_approximations.py:22-124  laplace_approximation(K, y, ...)
  *   apm_theta_eval     <- gpdemo/estimators.py:201-217 (+ :221-241)  ApproxPosteriorIS.__call__(ns, theta)
  *                         gpdemo/estimators.py:317-325               PriorMC.__call__(ns, theta)
@@ -98,6 +101,17 @@ int apm_theta_eval(apm_ctx *ctx, int estimator, int64_t count, const double *the
 /* the same for one chain with K (n x n, ldk) computed by the caller (any kernel_func) */
 int apm_theta_eval_K(apm_ctx *ctx, int estimator, const double *K, int64_t ldk, int64_t ubuf,
                      int64_t slot, double *out_logf, int *status, int64_t *n_cubic_ops);
+/* Laplace predictive at m test inputs Xs (m x d, ldxs) for `count` thetas (count <= max_batch):
+ * Gram -> fp64 Newton (apm_set_newton settings) -> mean/var/prob, each count x m with row stride
+ * ldo (any of the three may be NULL). status[i]: APM_STATUS_* of chain i (outputs of a failed
+ * chain are NaN); n_iter[i] (may be NULL): Newton iterations. Needs an ISO or ARD context.
+ * mean = k*^T a, var = s - |L^-1 (W^1/2 . k*)|^2 with s = exp(theta_0) (no epsilon on k* or k**:
+ * kernels.pyx adds it to the diagonal of one point set's Gram only), prob = Phi(mean /
+ * sqrt(1 + var)); W, L, a of the last Newton iteration (lpa.py:81-112). Nothing is clamped.
+ * Uses the context's work matrix like every theta-call; cache slots are not touched. */
+int apm_predict(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ldt,
+                const double *Xs, int64_t m, int64_t ldxs, double *mean, double *var,
+                double *prob, int64_t ldo, int *status, int64_t *n_iter);
 /* cached u-call: reuse slots[i]'s per-theta state with draws ubufs[i] */
 int apm_u_eval(apm_ctx *ctx, int64_t count, const int64_t *slots, const int64_t *ubufs,
                double *out_logf, int *status);
@@ -118,6 +132,11 @@ int apm_slot_read(apm_ctx *ctx, int64_t slot, double *L, int64_t ldl, double *f_
 /* ---- stand-alone building blocks (host in / host out) ---------------------------------------- */
 int apm_gram(int device, int kernel_kind, const double *X, int64_t n, int64_t d, int64_t ldx,
              const double *theta, int64_t n_theta, double epsilon, double *K, int64_t ldk);
+/* stand-alone building block, as apm_gram: Ks (m x n, ldk) = k(Xs_i, X_j), no epsilon (both
+ * point sets with row stride ldx) */
+int apm_gram_cross(int device, int kernel_kind, const double *Xs, int64_t m, const double *X,
+                   int64_t n, int64_t d, int64_t ldx, const double *theta, int64_t n_theta,
+                   double *Ks, int64_t ldk);
 /* laplace_approximation(K, y, calc_cov, calc_lml, diff_f_tol, max_iters): f_out (n), C_out
  * (n x n, ldc; if calc_cov), lml_out (if calc_lml), n_iter_out = Newton iterations */
 int apm_laplace(int device, const double *K, int64_t n, int64_t ldk, const double *y,
