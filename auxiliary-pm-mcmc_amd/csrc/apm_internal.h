@@ -219,6 +219,32 @@ void launch_predict_reduce(MatB A, int64_t row0, int ms, int mb, int nb, const d
                            double* var, double* prob, int64_t ostride, Live live, int nchains,
                            hipStream_t s);
 
+// ---- gradient.hip: gradient of the Laplace LML w.r.t. theta ---------------
+// per chain and row r < 64 nb: dS = K_rr - |row np + r of A over columns [0, 64 nb)|^2,
+// g = y phi(f)/Phi(y f), s2 = 1/2 dS d3 (third derivative of log p at f); zeros for r >= n.
+// Each output out[b * gstride + r]; f per chain with stride vstride.
+void launch_grad_rows(MatB A, MatB K, int n, int nb, const double* f, const double* y,
+                      int64_t vstride, double* dS, double* g, double* s2, int64_t gstride,
+                      Live live, int nchains, hipStream_t s);
+// A's rows [np, 2np) x columns [0, np) <- diag(Ws) (whole tiles), and zeros in the lower tiles of
+// the bottom-right block
+void launch_grad_fill(MatB A, const double* Ws, int64_t vstride, int nb, Live live, int nchains,
+                      hipStream_t s);
+// q = s2 + u for rows < n, zero beyond
+void launch_grad_q(const double* s2, const double* u, double* q, int64_t gstride, int n, int np,
+                   Live live, int nchains, hipStream_t s);
+// part[b * pstride + t * P + j] <- super-tile t's share of sum_ik M_ik (dK/dtheta_j)_ik with
+// M = 1/2 a a^T + 1/2 Rn + 1/2 (q g^T + g q^T) (Rn = -R, lower tiles) and S from K's lower tiles
+// off the diagonal, exp(theta_0) on it; t over the ns (ns + 1) / 2 lower super-tiles, ns =
+// ceil(nb / 2). launch_grad_sum adds them in tile order into grad[b * P + j].
+void launch_grad_reduce(MatB K, MatB Rn, const double* X, int64_t ldx, int n, int d, int nb,
+                        const double* theta, int64_t tstride, int kind, const double* a,
+                        int64_t vstride, const double* q, const double* g, int64_t gstride,
+                        double* part, int64_t pstride, int P, Live live, int nchains,
+                        hipStream_t s);
+void launch_grad_sum(const double* part, int64_t pstride, int nst, int P, double* grad, Live live,
+                     int nchains, hipStream_t s);
+
 // ---- newton.hip -----------------------------------------------------------------------------
 struct NewtonVecs {     // all per chain, stride vstride (>= np)
     double* f;          // current mode estimate

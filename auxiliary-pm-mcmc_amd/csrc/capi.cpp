@@ -206,6 +206,10 @@ struct apm_ctx {
     // behind them the chains' s = exp(theta_0) as the host computes it (max_batch)
     double *pxs = nullptr, *ppart = nullptr, *pmean = nullptr, *pvar = nullptr, *pprob = nullptr;
     double* psig = nullptr;
+    // the gradient path (apm_laplace_grad), allocated at its first call: six vectors per chain
+    // (dS, g, s2, t = K s2, u = -R t, q; max_batch x np each), the super-tile partials
+    // (max_batch x ns (ns + 1) / 2 x P) and the gradients (max_batch x P)
+    double *gvec = nullptr, *gpart = nullptr, *gout = nullptr;
 };
 
 // ------------------------------------------------------------------------------- APM_SKEW
@@ -967,6 +971,60 @@ void predict_block(apm_ctx* c, int count, const double* xs, int ms) {
                /*factor_diag=*/false, /*row_start=*/nb);
     launch_predict_reduce(c->A, np, ms, mb, nb, c->psig, c->ppart, nb * np, c->pmean,
                           c->pvar, c->pprob, np, lv, count, c->stream);
+    check_launch();
+}
+
+// Gradient of the Laplace LML w.r.t. theta (gradient.hip) for the chains left live
+// by an fp64 Laplace theta-call, in two passes over the bottom rows [np, 2np) of A against the
+// last Newton factor (chol_range's solve-only form, as augmented() and predict_block use it):
+//   1. K W^1/2 in the bottom-left (k_form_aug), panel solves -> V^T; its row norms give dS, then
+//      g, s2 and t = K s2;
+//   2. diag(W^1/2) in the bottom-left and zeros in the bottom-right's lower tiles, panel solves
+//      and trailing updates -> Z^T and -Z^T Z = -R; q = s2 + (-R) t;
+// then the fused contraction of M against dK/dtheta_j (k_grad_reduce) and the sum of its
+// super-tile partials into gout (count x P). grad_buffers() first.
+void grad_buffers(apm_ctx* c) {
+    if (c->gvec) return;
+    const int64_t np = c->np, B = c->max_batch, ns = (c->nb + 1) / 2;
+    c->gvec = dalloc<double>(c, 6 * B * np);
+    c->gpart = dalloc<double>(c, B * (ns * (ns + 1) / 2) * c->P);
+    c->gout = dalloc<double>(c, B * c->P);
+}
+
+void grad_block(apm_ctx* c, int count) {
+    const Live lv = live_of(c);
+    const int nb = c->nb, ns = (nb + 1) / 2, nst = ns * (ns + 1) / 2;
+    const int64_t np = c->np, B = c->max_batch;
+    double *dS = c->gvec, *g = dS + B * np, *s2 = g + B * np, *t = s2 + B * np, *u = t + B * np,
+           *q = u + B * np;
+    launch_form_aug(c->K, c->A, c->v, c->np, lv, count, c->stream, /*lower_only=*/!c->k_full);
+    check_launch();
+    chol_range(c, c->A, 0, nb, /*R=*/2 * nb, /*Cb=*/nb, APM_STATUS_CHOL_B, count,
+               /*factor_diag=*/false, /*row_start=*/nb);
+    launch_grad_rows(c->A, c->K, c->n, nb, c->v.f, c->y, c->v.vstride, dS, g, s2, np, lv, count,
+                     c->stream);
+    check_launch();
+    launch_symv(c->K, s2, np, t, np, c->sympart, c->sstride, c->np, MatF{}, nullptr, 0, lv, count,
+                c->stream, c->symv_tpw);
+    check_launch();
+    launch_grad_fill(c->A, c->v.Ws, c->v.vstride, nb, lv, count, c->stream);
+    check_launch();
+    chol_range(c, c->A, 0, nb, /*R=*/2 * nb, /*Cb=*/2 * nb, APM_STATUS_CHOL_B, count,
+               /*factor_diag=*/false, /*row_start=*/nb);
+    const MatB Rn{c->A.base + np * c->A.ld + np, c->A.ld, c->A.cstride};  // -R, lower tiles
+    launch_symv(Rn, t, np, u, np, c->sympart, c->sstride, c->np, MatF{}, nullptr, 0, lv, count,
+                c->stream, c->symv_tpw);
+    check_launch();
+    launch_grad_q(s2, u, q, np, c->n, c->np, lv, count, c->stream);
+    check_launch();
+    {   // bytes: the lower triangles of R and K (the inputs and vectors are small beside them)
+        ProfScope ps(c, APM_PROF_GRAD_REDUCE, 8.0 * (double)c->n * (c->n + 1) * c->live_n);
+        launch_grad_reduce(c->K, Rn, c->X, c->d, c->n, c->d, nb, c->theta, c->P, c->kind, c->v.a,
+                           c->v.vstride, q, g, np, c->gpart, (int64_t)nst * c->P, c->P, lv, count,
+                           c->stream);
+        check_launch();
+    }
+    launch_grad_sum(c->gpart, (int64_t)nst * c->P, nst, c->P, c->gout, lv, count, c->stream);
     check_launch();
 }
 
@@ -2051,6 +2109,55 @@ int apm_predict(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, co
             if (status[b] != APM_STATUS_OK)
                 for (double* o : {mean, var, prob})
                     if (o) std::fill(o + b * ldo, o + b * ldo + m, nan);
+    } catch (const HipError& e) {
+        return fail(c, APM_E_HIP, e.msg);
+    }
+    return APM_SUCCESS;
+}
+
+int apm_laplace_grad(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, double* lml,
+                     double* grad, int64_t ldg, int* status, int64_t* n_iter) {
+    if (!c) return fail(nullptr, APM_E_INVALID, "apm_laplace_grad: null context");
+    if (c->kind == APM_KERNEL_PRECOMPUTED)
+        return fail(c, APM_E_INVALID, "apm_laplace_grad: needs an ISO or ARD context (dK/dtheta "
+                                      "is built on the device)");
+    if (count <= 0 || count > c->max_batch)
+        return fail(c, APM_E_INVALID, "apm_laplace_grad: count outside [1, max_batch]");
+    if (ldt < c->P) return fail(c, APM_E_INVALID, "apm_laplace_grad: ldt < theta length");
+    if (ldg < c->P) return fail(c, APM_E_INVALID, "apm_laplace_grad: ldg < theta length");
+    if (!thetas || !grad || !status)
+        return fail(c, APM_E_INVALID, "apm_laplace_grad: bad arguments");
+    const SkewScope skew(c);
+    try {
+        HIPC(hipSetDevice(c->device));
+        double* th = c->hth;  // pinned: the upload is asynchronous
+        for (int64_t b = 0; b < count; ++b)
+            for (int p = 0; p < c->P; ++p) th[b * c->P + p] = thetas[b * ldt + p];
+        HIPC(hipMemcpyAsync(c->theta, th, sizeof(double) * count * c->P, hipMemcpyHostToDevice,
+                            c->stream));
+        // the Laplace theta-call itself (Gram, fp64 Newton, LML): L, inv(L_kk), W^1/2, a and the
+        // mode of each chain's last iteration stay in A / Dinv / the Newton vectors
+        std::vector<double> val((size_t)count);
+        theta_eval_impl(c, APM_EST_LAPLACE, (int)count, true, val.data(), status, n_iter);
+        int ok = 0;
+        for (int64_t b = 0; b < count; ++b) ok += status[b] == APM_STATUS_OK;
+        std::vector<double> gh((size_t)count * c->P);
+        if (ok) {
+            // converged chains left the Newton loop with active = 0 (as augmented())
+            HIPC(hipMemsetD32Async(c->active, 1, count, c->stream));
+            c->live_n = ok;
+            grad_buffers(c);
+            grad_block(c, (int)count);
+            HIPC(hipMemcpyAsync(gh.data(), c->gout, sizeof(double) * count * c->P,
+                                hipMemcpyDeviceToHost, c->stream));
+            sync(c);
+        }
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        for (int64_t b = 0; b < count; ++b) {
+            const bool good = status[b] == APM_STATUS_OK;
+            if (lml) lml[b] = good ? val[b] : nan;
+            for (int p = 0; p < c->P; ++p) grad[b * ldg + p] = good ? gh[b * c->P + p] : nan;
+        }
     } catch (const HipError& e) {
         return fail(c, APM_E_HIP, e.msg);
     }

@@ -1,0 +1,315 @@
+// Gradient of the Laplace log marginal likelihood with respect to theta: the
+// kernels around the two Schur-complement passes that capi.cpp's grad_block borrows from the
+// Cholesky (chol_range on the bottom rows of the work matrix against the last Newton factor).
+//
+//   v = phi(f)/Phi(y f),  g = y v,  d3 = -[(2v + y f)(-f v - y v^2) + y v]      (f = K a, the mode)
+//   dS_i = K_ii - |L^-1 (W^1/2 . K[:, i])|^2,  s2 = 1/2 dS . d3
+//   R = Z^T Z with Z = L^-1 diag(W^1/2),  q = s2 - R (K s2)
+//   M = 1/2 a a^T - 1/2 R + 1/2 (q g^T + g q^T)
+//   dLML/dtheta_j = sum_ik M_ik (dK/dtheta_j)_ik
+//   dK/dtheta_0 = S (K without its jitter: s on the diagonal, not s + epsilon),
+//   dK/dtheta_{k+1} = S_ik ((x_ik - x_jk)/tau_k)^2 (ARD), the sum over k of these (iso)
+// with W, L, a of the last Newton iteration (latent_posterior_approximations.py:81-106).
+#include "apm_internal.h"
+
+#define GK 32         // features per LDS chunk (k_gram's)
+#define GP (128 + 2)  // LDS row pitch in doubles (k_gram's)
+// lane (g = lane >> 3 or lane & 7) -> its 8 rows (columns) of the wave's 64x64 tile (k_gram's)
+#define R8(g, p) (((p) >> 2) * 32 + 4 * (g) + ((p) & 3))
+
+__device__ __forceinline__ bool live_g(const Live& lv, int b) {
+    return lv.active[b] != 0 && lv.status[b] == 0;
+}
+
+// One wave per (chain, training row r): dS_r from the squared norm of row np + r of the work
+// matrix over its first 64 nb columns (the row of (K W^1/2) L^-T; 16-byte loads, consecutive
+// lanes consecutive pieces, each lane its pieces in order, then the wave's butterfly) and K's own
+// diagonal entry, then g_r and s2_r at the mode. Rows >= n get exact zeros.
+__global__ __launch_bounds__(256) void k_grad_rows(MatB A, MatB K, int n, int nb,
+                                                   const double* __restrict__ f,
+                                                   const double* __restrict__ y, int64_t vstride,
+                                                   double* __restrict__ dS, double* __restrict__ g,
+                                                   double* __restrict__ s2, int64_t gstride,
+                                                   Live live) {
+    const int b = blockIdx.y;
+    if (!live_g(live, b)) return;
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int np = 64 * nb;
+    if (r >= np) return;
+    const int64_t o = b * gstride + r;
+    if (r >= n) {  // (wave-uniform)
+        if (lane == 0) dS[o] = g[o] = s2[o] = 0.0;
+        return;
+    }
+    const double* row = A.base + b * A.cstride + (int64_t)(np + r) * A.ld;
+    double s = 0.0;
+    for (int c = 2 * lane; c < np; c += 128) {
+        const d2_t v = *reinterpret_cast<const d2_t*>(row + c);
+        s = fma(v.x, v.x, s);
+        s = fma(v.y, v.y, s);
+    }
+    s = wave_sum_d(s);
+    if (lane != 0) return;
+    const double ds = K.base[b * K.cstride + (int64_t)r * K.ld + r] - s;
+    const double fi = f[b * vstride + r], yi = y[r];
+    const double v = exp(-0.5 * fi * fi - log_ndtr_d(yi * fi) - 0.91893853320467274178);
+    const double d3 = -((2.0 * v + yi * fi) * (-fi * v - yi * v * v) + yi * v);
+    dS[o] = ds;
+    g[o] = yi * v;
+    s2[o] = 0.5 * ds * d3;
+}
+
+void launch_grad_rows(MatB A, MatB K, int n, int nb, const double* f, const double* y,
+                      int64_t vstride, double* dS, double* g, double* s2, int64_t gstride,
+                      Live live, int nchains, hipStream_t s) {
+    APM_LAUNCH(k_grad_rows, dim3((64 * nb + 3) / 4, nchains), dim3(256), 0, s, A, K, n, nb, f, y,
+               vstride, dS, g, s2, gstride, live);
+}
+
+// Right-hand side of the second pass: rows [np, 2np) x columns [0, np) of the work matrix
+// <- diag(W^1/2) (whole tiles, zero off the diagonal; W^1/2 is zero beyond the data), and zeros
+// in the lower tiles of the bottom-right block, which the trailing updates then turn into -Z^T Z.
+__global__ __launch_bounds__(256) void k_grad_fill(MatB A, const double* __restrict__ Ws,
+                                                   int64_t vstride, int nb, Live live) {
+    const int b = blockIdx.y;
+    if (!live_g(live, b)) return;
+    const int t = blockIdx.x, nbl = nb * nb;
+    int ti, tj;
+    int64_t c0 = 0;
+    if (t < nbl) {
+        ti = t / nb;
+        tj = t % nb;
+    } else {  // lower-triangular tile index -> (ti, tj) of the bottom-right block
+        const int u = t - nbl;
+        ti = (int)floor((sqrt(8.0 * u + 1.0) - 1.0) * 0.5);
+        while (ti * (ti + 1) / 2 > u) --ti;
+        while ((ti + 1) * (ti + 2) / 2 <= u) ++ti;
+        tj = u - ti * (ti + 1) / 2;
+        c0 = (int64_t)nb * 64;
+    }
+    const bool dg = t < nbl && ti == tj;
+    const double* wb = Ws + b * vstride + ti * 64;
+    double* At = A.base + b * A.cstride + ((int64_t)nb * 64 + ti * 64) * A.ld + c0 + tj * 64;
+#pragma unroll
+    for (int h = 0; h < 8; ++h) {
+        const int e = threadIdx.x + 256 * h;  // piece: row e / 32, columns 2 (e % 32) .. +1
+        const int r = e >> 5, c = 2 * (e & 31);
+        d2_t v{0.0, 0.0};
+        if (dg && (r >> 1) == (c >> 1)) {
+            if (r == c) v.x = wb[r];
+            else v.y = wb[r];
+        }
+        *reinterpret_cast<d2_t*>(At + (int64_t)r * A.ld + c) = v;
+    }
+}
+
+void launch_grad_fill(MatB A, const double* Ws, int64_t vstride, int nb, Live live, int nchains,
+                      hipStream_t s) {
+    APM_LAUNCH(k_grad_fill, dim3(nb * nb + nb * (nb + 1) / 2, nchains), dim3(256), 0, s, A, Ws,
+               vstride, nb, live);
+}
+
+// q = s2 - R t with u = (-R) t from the symmetric product over the bottom-right block's lower
+// tiles (launch_symv); exact zeros beyond the data
+__global__ __launch_bounds__(256) void k_grad_q(const double* __restrict__ s2,
+                                                const double* __restrict__ u,
+                                                double* __restrict__ q, int64_t gstride, int n,
+                                                int np, Live live) {
+    const int b = blockIdx.y;
+    if (!live_g(live, b)) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= np) return;
+    const int64_t o = b * gstride + i;
+    q[o] = i < n ? s2[o] + u[o] : 0.0;
+}
+
+void launch_grad_q(const double* s2, const double* u, double* q, int64_t gstride, int n, int np,
+                   Live live, int nchains, hipStream_t s) {
+    APM_LAUNCH(k_grad_q, dim3((np + 255) / 256, nchains), dim3(256), 0, s, s2, u, q, gstride, n,
+               np, live);
+}
+
+// The contraction sum_ik M_ik (dK/dtheta_j)_ik for every j in one pass over the inputs: k_gram's
+// tiling - one workgroup of 4 waves per lower 128x128 super-tile (si, sj) and chain, wave w the
+// 64x64 tile (2si + w/2, 2sj + w%2) (the upper tile of a diagonal super-tile and tiles beyond the
+// padded size are skipped), 8x8 pairs per lane, features pre-scaled by 1/tau_k while staged
+// through LDS in chunks of GK. Per pair the lane first forms w = c M_ik S_ik once: M from Rn (the
+// bottom-right block of the work matrix, -R in its lower tiles), a, q and g; S from K off the
+// diagonal and s = exp(theta_0) on it (no epsilon); c the count of the symmetric sum - 2 for
+// i > k, 1 on the diagonal, 0 for the upper half of a diagonal tile and for any row or column
+// beyond the data (K is identity-padded there: masked, not multiplied). Then theta_0's sum is
+// sum w, and feature k's is sum w df_k^2: each lane its 8 rows (8 pairs each, in order) and the 8
+// row sums in order, the wave's butterfly, the 4 waves in order. ARD writes one partial per
+// feature; iso adds the features in order into one. Partials go to part[b][t][0..P) for
+// super-tile t; k_grad_sum adds them in tile order. No atomics, no hand-over between workgroups:
+// every output depends on its own chain and on fixed positions only.
+__global__ __launch_bounds__(256) void k_grad_reduce(
+    MatB K, MatB Rn, const double* __restrict__ X, int64_t ldx, int n, int d, int nb,
+    const double* __restrict__ theta, int64_t tstride, int kind, const double* __restrict__ avec,
+    int64_t vstride, const double* __restrict__ qvec, const double* __restrict__ gvec,
+    int64_t gstride, double* __restrict__ part, int64_t pstride, int P, Live live) {
+    const int b = blockIdx.y;
+    if (!live_g(live, b)) return;
+    // lower-triangular super-tile index -> (si, sj), si >= sj
+    const int t = blockIdx.x;
+    int si = (int)floor((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
+    while (si * (si + 1) / 2 > t) --si;
+    while ((si + 1) * (si + 2) / 2 <= t) ++si;
+    const int sj = t - si * (si + 1) / 2;
+
+    __shared__ __attribute__((aligned(16))) double xi[GK][GP];
+    __shared__ __attribute__((aligned(16))) double xj[GK][GP];
+    __shared__ double itau[GK];
+    __shared__ double red[4][GK];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tr = lane >> 3, tc = lane & 7;
+    const int ti = 2 * si + (wv >> 1), tj = 2 * sj + (wv & 1);
+    const bool mine = ti < nb && tj <= ti;  // (wave-uniform)
+    const int ro = 64 * (wv >> 1), co = 64 * (wv & 1);
+    const double* th = theta + b * tstride;
+    double* pb = part + b * pstride + (int64_t)t * P;
+
+    double w[8][8];
+    double s0 = 0.0;
+    if (mine) {
+        const double sigma = exp(th[0]);
+        const double* ab = avec + b * vstride;
+        const double* qb = qvec + b * gstride;
+        const double* gb = gvec + b * gstride;
+        double ak[8], qk[8], gk[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int gj = tj * 64 + R8(tc, q);
+            ak[q] = ab[gj];
+            qk[q] = qb[gj];
+            gk[q] = gb[gj];
+        }
+        const double* Kt = K.base + b * K.cstride + tj * 64 + 4 * tc;
+        const double* Rt = Rn.base + b * Rn.cstride + tj * 64 + 4 * tc;
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+            const int gi = ti * 64 + R8(tr, p);
+            const double* kr = Kt + (int64_t)gi * K.ld;
+            const double* rr = Rt + (int64_t)gi * Rn.ld;
+            const d2_t k0 = *reinterpret_cast<const d2_t*>(kr);
+            const d2_t k1 = *reinterpret_cast<const d2_t*>(kr + 2);
+            const d2_t k2 = *reinterpret_cast<const d2_t*>(kr + 32);
+            const d2_t k3 = *reinterpret_cast<const d2_t*>(kr + 34);
+            const d2_t r0 = *reinterpret_cast<const d2_t*>(rr);
+            const d2_t r1 = *reinterpret_cast<const d2_t*>(rr + 2);
+            const d2_t r2 = *reinterpret_cast<const d2_t*>(rr + 32);
+            const d2_t r3 = *reinterpret_cast<const d2_t*>(rr + 34);
+            const double kv[8] = {k0.x, k0.y, k1.x, k1.y, k2.x, k2.y, k3.x, k3.y};
+            const double rv[8] = {r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, r3.x, r3.y};
+            const double ai = ab[gi], qi = qb[gi], gg = gb[gi];
+            double sp = 0.0;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int gj = tj * 64 + R8(tc, q);
+                const double m = 0.5 * (fma(ai, ak[q], rv[q]) + fma(qi, gk[q], gg * qk[q]));
+                const double sv = (gi == gj) ? sigma : kv[q];
+                const double cnt = (gi > gj) ? 2.0 : 1.0;
+                const bool in = gi < n && gj <= gi;  // (gj <= gi < n)
+                w[p][q] = in ? cnt * (m * sv) : 0.0;
+                sp += w[p][q];
+            }
+            s0 += sp;
+        }
+    } else {
+#pragma unroll
+        for (int p = 0; p < 8; ++p)
+#pragma unroll
+            for (int q = 0; q < 8; ++q) w[p][q] = 0.0;
+    }
+    s0 = wave_sum_d(s0);
+
+    double iso = 0.0;  // (thread 0: the features' sums in order)
+    for (int k0 = 0; k0 < d; k0 += GK) {
+        const int kc = min(GK, d - k0);
+        __syncthreads();
+        if (tid < kc) itau[tid] = exp(-th[kind == 0 ? 1 : 1 + k0 + tid]);
+        __syncthreads();
+        for (int e = tid; e < 128 * GK; e += 256) {
+            const int r = e / GK, k = e % GK;  // consecutive lanes: consecutive features of a row
+            const int gi = si * 128 + r, gj = sj * 128 + r;
+            const double sc = (k < kc) ? itau[k] : 0.0;
+            xi[k][r] = (k < kc && gi < n) ? X[(int64_t)gi * ldx + k0 + k] * sc : 0.0;
+            xj[k][r] = (k < kc && gj < n) ? X[(int64_t)gj * ldx + k0 + k] * sc : 0.0;
+        }
+        __syncthreads();
+        for (int k = 0; k < kc; ++k) {
+            double sk = 0.0;
+            if (mine) {
+                double a[8], c[8];
+#pragma unroll
+                for (int h = 0; h < 4; ++h) {
+                    const d2_t va = *reinterpret_cast<const d2_t*>(&xi[k][ro + R8(tr, 2 * h)]);
+                    const d2_t vc = *reinterpret_cast<const d2_t*>(&xj[k][co + R8(tc, 2 * h)]);
+                    a[2 * h] = va.x;
+                    a[2 * h + 1] = va.y;
+                    c[2 * h] = vc.x;
+                    c[2 * h + 1] = vc.y;
+                }
+                double sp[8];  // one chain of 8 fmas per row: 8 independent chains in flight
+#pragma unroll
+                for (int p = 0; p < 8; ++p) {
+                    double df[8];
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) df[q] = a[p] - c[q];  // pre-scaled by 1/tau_k
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) df[q] *= df[q];
+                    sp[p] = 0.0;
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) sp[p] = fma(w[p][q], df[q], sp[p]);
+                }
+#pragma unroll
+                for (int p = 0; p < 8; ++p) sk += sp[p];
+                sk = wave_sum_d(sk);
+            }
+            if (lane == 0) red[wv][k] = sk;
+        }
+        __syncthreads();
+        if (kind != 0) {
+            if (tid < kc) pb[1 + k0 + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+        } else if (tid == 0) {
+            for (int k = 0; k < kc; ++k) iso += ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+        }
+    }
+    __syncthreads();
+    if (lane == 0) red[wv][0] = s0;
+    __syncthreads();
+    if (tid == 0) {
+        pb[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
+        if (kind == 0) pb[1] = iso;
+    }
+}
+
+void launch_grad_reduce(MatB K, MatB Rn, const double* X, int64_t ldx, int n, int d, int nb,
+                        const double* theta, int64_t tstride, int kind, const double* a,
+                        int64_t vstride, const double* q, const double* g, int64_t gstride,
+                        double* part, int64_t pstride, int P, Live live, int nchains,
+                        hipStream_t s) {
+    const int ns = (nb + 1) / 2;
+    APM_LAUNCH(k_grad_reduce, dim3(ns * (ns + 1) / 2, nchains), dim3(256), 0, s, K, Rn, X, ldx, n,
+               d, nb, theta, tstride, kind, a, vstride, q, g, gstride, part, pstride, P, live);
+}
+
+// grad[b][p] = the nst super-tile partials of (chain b, parameter p) added in tile order
+__global__ __launch_bounds__(256) void k_grad_sum(const double* __restrict__ part,
+                                                  int64_t pstride, int nst, int P,
+                                                  double* __restrict__ grad, Live live) {
+    const int b = blockIdx.y;
+    if (!live_g(live, b)) return;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= P) return;
+    const double* pb = part + b * pstride + p;
+    double s = 0.0;
+    for (int t = 0; t < nst; ++t) s += pb[(int64_t)t * P];
+    grad[(int64_t)b * P + p] = s;
+}
+
+void launch_grad_sum(const double* part, int64_t pstride, int nst, int P, double* grad, Live live,
+                     int nchains, hipStream_t s) {
+    APM_LAUNCH(k_grad_sum, dim3((P + 255) / 256, nchains), dim3(256), 0, s, part, pstride, nst, P,
+               grad, live);
+}

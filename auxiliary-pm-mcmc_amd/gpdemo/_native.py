@@ -22,7 +22,7 @@ STATUS_GUARD = 5
 PROF_GRAM, PROF_CHOL_UPDATE, PROF_UGEMM, PROF_CHOL_UPDATE32, PROF_STATS = 0, 1, 2, 3, 4
 PROF_CHOL_UPDATE32_OUTER, PROF_CHOL_UPDATE_OUTER, PROF_DF_TIMEOUTS = 5, 6, 7
 PROF_POST32_OUTER, PROF_POST64_RERUNS, PROF_TRSV_TIMEOUTS = 8, 9, 10
-PROF_ICM_CHECKS, PROF_GUARD, PROF_NKINDS = 11, 12, 13
+PROF_ICM_CHECKS, PROF_GUARD, PROF_GRAD_REDUCE, PROF_NKINDS = 11, 12, 13, 14
 
 
 class NativeUnavailableError(RuntimeError):
@@ -64,6 +64,7 @@ _SIGS = {
     'apm_gram': (_i, [_i, _i, _p, _i64, _i64, _i64, _p, _i64, _d, _p, _i64]),
     'apm_gram_cross': (_i, [_i, _i, _p, _i64, _p, _i64, _i64, _i64, _p, _i64, _p, _i64]),
     'apm_predict': (_i, [_p, _i64, _p, _i64, _p, _i64, _i64, _p, _p, _p, _i64, _p, _p]),
+    'apm_laplace_grad': (_i, [_p, _i64, _p, _i64, _p, _p, _i64, _p, _p]),
     'apm_laplace': (_i, [_i, _p, _i64, _i64, _p, _i, _i, _d, _i64, _p, _p, _i64, _p, _p, _p]),
     'apm_prof_enable': (_i, [_p, _i]),
     'apm_prof_marker': (_i, [_p, _i]),
@@ -364,6 +365,25 @@ class Context(object):
                 mean[t0:].ctypes.data, var[t0:].ctypes.data, prob[t0:].ctypes.data, m,
                 st[t0:].ctypes.data, nit[t0:].ctypes.data), self._h)
         return mean, var, prob, st, nit
+
+    def laplace_grad(self, thetas):
+        """Laplace log marginal likelihood and its gradient with respect to theta for every row
+        of thetas, `max_batch` at a time: ``(lml (T,), grad (T, P), status, n_iter)`` with NaN
+        where status != 0 (include/apm.h apm_laplace_grad)."""
+        th = np.atleast_2d(_f64(thetas))
+        if th.shape[1] < self.theta_len:
+            raise IndexError('Out of bounds on buffer access (axis 0)')
+        T, P = th.shape[0], self.theta_len
+        lml = np.full(T, np.nan)
+        grad = np.full((T, P), np.nan)
+        st = np.zeros(T, dtype=np.int32)
+        nit = np.zeros(T, dtype=np.int64)
+        for t0 in range(0, T, self.max_batch):
+            cnt = min(self.max_batch, T - t0)
+            _check(self.lib.apm_laplace_grad(
+                self._h, cnt, th[t0:].ctypes.data, th.shape[1], lml[t0:].ctypes.data,
+                grad[t0:].ctypes.data, P, st[t0:].ctypes.data, nit[t0:].ctypes.data), self._h)
+        return lml, grad, st, nit
 
     def u_eval(self, slots, ubufs):
         sl = np.ascontiguousarray(slots, dtype=np.int64)

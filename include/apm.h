@@ -10,6 +10,8 @@
  *   apm_gram_cross     <- the same two kernels between two point sets (their i != j entries)
  *   apm_predict        <- no reference counterpart: the Laplace predictive distribution at test
  *                         inputs from the Newton quantities of laplace_approximation (:81-112)
+ *   apm_laplace_grad   <- no reference counterpart: the gradient of the Laplace log marginal
+ *                         likelihood (:103-106) with respect to theta
  *   apm_laplace        <- gpdemo/latent_posterior_approximations.py:22-124  laplace_approximation(K, y, ...)
  *   apm_theta_eval     <- gpdemo/estimators.py:201-217 (+ :221-241)  ApproxPosteriorIS.__call__(ns, theta)
  *                         gpdemo/estimators.py:317-325               PriorMC.__call__(ns, theta)
@@ -112,6 +114,26 @@ int apm_theta_eval_K(apm_ctx *ctx, int estimator, const double *K, int64_t ldk, 
 int apm_predict(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ldt,
                 const double *Xs, int64_t m, int64_t ldxs, double *mean, double *var,
                 double *prob, int64_t ldo, int *status, int64_t *n_iter);
+/* Gradient of the Laplace log marginal likelihood with respect to theta for `count` thetas
+ * (count <= max_batch): Gram -> fp64 Newton (apm_set_newton settings) -> lml[i] (may be NULL) and
+ * grad row i (count x P, row stride ldg >= P = apm_theta_len). status[i]: APM_STATUS_* of chain i
+ * (lml and the grad row of a failed chain are NaN); n_iter[i] (may be NULL): Newton iterations.
+ * Needs an ISO or ARD context. No reference counterpart. With W, W^1/2, L = chol(I + W^1/2 K
+ * W^1/2), a of the last Newton iteration and the mode f = K a (lpa.py:81-106):
+ *   v = phi(f)/Phi(y f), g = y v, d3 = -[(2v + y f)(-f v - y v^2) + y v],
+ *   R = Z^T Z with Z = L^-1 diag(W^1/2), dS_i = K_ii - |L^-1 (W^1/2 . K[:, i])|^2,
+ *   s2 = 1/2 dS . d3, q = s2 - R (K s2), M = 1/2 a a^T - 1/2 R + 1/2 (q g^T + g q^T),
+ *   grad_j = sum_ik M_ik (dK/dtheta_j)_ik,
+ * dK/dtheta_0 = S, the covariance function WITHOUT epsilon (its diagonal is exp(theta_0): the
+ * jitter kernels.pyx adds does not depend on theta), dK/dtheta_{k+1} = S_ik ((x_ik - x_jk) /
+ * tau_k)^2 (ARD) or the sum over k of these (ISO); K = S + epsilon I everywhere else. This is the
+ * derivative at the exact mode: at a loose diff_f_tol it is approximate.
+ * lml[i] is bitwise the value apm_theta_eval(APM_EST_LAPLACE) returns for the same theta and
+ * Newton settings: that call always takes this fp64 Newton path, so no setting is needed.
+ * A chain's outputs do not depend on its position in the batch nor on the other chains. Uses the
+ * context's work matrix like every theta-call; cache slots and U buffers are not touched. */
+int apm_laplace_grad(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ldt, double *lml,
+                     double *grad, int64_t ldg, int *status, int64_t *n_iter);
 /* cached u-call: reuse slots[i]'s per-theta state with draws ubufs[i] */
 int apm_u_eval(apm_ctx *ctx, int64_t count, const int64_t *slots, const int64_t *ubufs,
                double *out_logf, int *status);
@@ -166,7 +188,9 @@ int apm_laplace(int device, const double *K, int64_t n, int64_t ldk, const doubl
 #define APM_PROF_ICM_CHECKS 11 /* not a kernel: launches = chains whose chol(C) was also formed the
                                  reference's way (the InvalidCovarianceMatrixError check) */
 #define APM_PROF_GUARD 12 /* not a kernel: launches = chains failed by the guard (APM_STATUS_GUARD) */
-#define APM_PROF_NKINDS 13
+#define APM_PROF_GRAD_REDUCE 13 /* k_grad_reduce of apm_laplace_grad; work = bytes (the lower
+                                   triangles of R and K it reads) */
+#define APM_PROF_NKINDS 14
 /* on = 0 off; 1 the roofline kinds (GRAM, UGEMM and the two *_OUTER kinds: one event pair per
  * launch of those kernels only, so that the timing adds little to a timed region); 2 every kind
  * (CHOL_UPDATE / CHOL_UPDATE32 add an event pair around every in-panel update launch) */
