@@ -69,6 +69,11 @@ def chain_streams(seed, n_chains, first_chain=0):
     return prngs, dev_seeds
 
 
+_KERNEL_KINDS = {'ard': _native.KERNEL_ARD,
+                 'matern32_iso': _native.KERNEL_M32_ISO, 'matern32_ard': _native.KERNEL_M32_ARD,
+                 'matern52_iso': _native.KERNEL_M52_ISO, 'matern52_ard': _native.KERNEL_M52_ARD}
+
+
 class _BatchedChains(object):
     """Device context, per-chain streams and state shared by the batched samplers.
 
@@ -83,7 +88,8 @@ class _BatchedChains(object):
         self.prior = dict(prior)
         self.max_slice_iters = int(max_slice_iters)
         self.est = _EST[estimator]
-        kind = _native.KERNEL_ARD if kernel == 'ard' else _native.KERNEL_ISO
+        # 'ard' and the four Matern names select their kind; anything else is ISO, as before
+        kind = _KERNEL_KINDS.get(kernel, _native.KERNEL_ISO)
         C = self.n_chains
         self.ctx = _native.Context(X, y, kind, epsilon, n_imp, max_batch=C, n_slots=2 * C,
                                    n_ubufs=3 * C, device=device)
@@ -359,7 +365,8 @@ class _BatchedChains(object):
 class BatchedAPMEllSSPlusRandDirSliceSampler(_BatchedChains):
     """Batch of APM E-SS(u) + RD-SS(theta) chains on one device.
 
-    Parameters mirror the notebook protocol: ``kernel`` 'ard' | 'iso', ``epsilon`` jitter,
+    Parameters mirror the notebook protocol: ``kernel`` 'ard' | 'iso' (SE) or
+    'matern32_iso' | 'matern32_ard' | 'matern52_iso' | 'matern52_ard', ``epsilon`` jitter,
     ``n_imp`` importance samples, slice width ``w`` and ``max_steps_out`` (E-SS+RD-SS.ipynb:64-67),
     ``prior`` the log-Gamma hyper-parameters (a_sigma, b_sigma, a_tau, b_tau).
     """

@@ -188,9 +188,71 @@ void launch_refine_mask(Live live, int* refining, int nchains, hipStream_t s);
 void launch_refine(int mode, const double* Ws, const double* Kb, double* x, const double* Kt,
                    double* out, int64_t vstride, int np, Live live, int nchains, hipStream_t s);
 
+// ---- covariance kinds -----------------------------------------------------------------------
+// The one place that reads an APM_KERNEL_* value of include/apm.h: a kind the device builds is a
+// (family, iso / ARD) pair; everything else (APM_KERNEL_PRECOMPUTED, unknown values) is not.
+//   SE          S = s exp(-r^2 / 2)                                G = S
+//   Matern 3/2  S = s (1 + sqrt3 r) exp(-sqrt3 r)                  G = 3 s exp(-sqrt3 r)
+//   Matern 5/2  S = s (1 + sqrt5 r + 5/3 r^2) exp(-sqrt5 r)        G = 5/3 s (1 + sqrt5 r) exp(-sqrt5 r)
+// with r^2 = sum_k ((x_ik - x_jk)/tau_k)^2, s = exp(theta_0), tau_k = exp(theta_{k+1}) (ARD) or
+// exp(theta_1) for every k (iso); dK/dtheta_{k+1} = G ((x_ik - x_jk)/tau_k)^2 (gradient.hip).
+enum { APM_FAM_SE = 0, APM_FAM_M32 = 1, APM_FAM_M52 = 2 };
+struct KernelKind {
+    int family;  // APM_FAM_*, -1: not built on the device
+    int iso;     // one length scale (theta has 2 entries) instead of d (d + 1 entries)
+    bool on_device() const { return family >= 0; }
+    int64_t theta_len(int64_t d) const { return family < 0 ? 0 : (iso ? 2 : d + 1); }
+};
+inline KernelKind kernel_kind_of(int kind) {
+    switch (kind) {
+        case 0: return KernelKind{APM_FAM_SE, 1};   // APM_KERNEL_ISO
+        case 1: return KernelKind{APM_FAM_SE, 0};   // APM_KERNEL_ARD
+        case 3: return KernelKind{APM_FAM_M32, 1};  // APM_KERNEL_M32_ISO
+        case 4: return KernelKind{APM_FAM_M32, 0};  // APM_KERNEL_M32_ARD
+        case 5: return KernelKind{APM_FAM_M52, 1};  // APM_KERNEL_M52_ISO
+        case 6: return KernelKind{APM_FAM_M52, 0};  // APM_KERNEL_M52_ARD
+        default: return KernelKind{-1, 0};          // APM_KERNEL_PRECOMPUTED and unknown values
+    }
+}
+// the launchers' dispatch on the family (a template parameter of k_gram, k_gram_cross and
+// k_grad_reduce: their epilogues differ, everything else is shared)
+#define APM_FAMILY_DISPATCH(family, ...)                                           \
+    switch (family) {                                                              \
+        case APM_FAM_M32: { constexpr int FAM = APM_FAM_M32; __VA_ARGS__; } break; \
+        case APM_FAM_M52: { constexpr int FAM = APM_FAM_M52; __VA_ARGS__; } break; \
+        default: { constexpr int FAM = APM_FAM_SE; __VA_ARGS__; } break;           \
+    }
+#ifdef __HIPCC__
+// the covariance function of the pair's scaled squared distance r2, family FAM
+template <int FAM>
+__device__ __forceinline__ double cov_S(double sigma, double r2) {
+    if constexpr (FAM == APM_FAM_SE) {
+        return sigma * exp(-0.5 * r2);
+    } else if constexpr (FAM == APM_FAM_M32) {
+        const double t = 1.7320508075688772 * sqrt(r2);
+        return sigma * ((1.0 + t) * exp(-t));
+    } else {
+        const double t = 2.23606797749979 * sqrt(r2);
+        return sigma * ((1.0 + t + (5.0 / 3.0) * r2) * exp(-t));
+    }
+}
+// the Matern families' length-scale weight G (the SE family's is S itself)
+template <int FAM>
+__device__ __forceinline__ double cov_G(double sigma, double r2) {
+    static_assert(FAM == APM_FAM_M32 || FAM == APM_FAM_M52, "SE: G = S");
+    if constexpr (FAM == APM_FAM_M32) {
+        const double t = 1.7320508075688772 * sqrt(r2);
+        return (3.0 * sigma) * exp(-t);
+    } else {
+        const double t = 2.23606797749979 * sqrt(r2);
+        return ((5.0 / 3.0) * sigma) * ((1.0 + t) * exp(-t));
+    }
+}
+#endif
+
 // ---- gram.hip -------------------------------------------------------------------------------
 // K[b] (np x np, identity-padded beyond n) from X (n x d, row-major, ldx) and theta[b]
-// kind 0 = isotropic SE (kernels.pyx:12-49), 1 = ARD SE (kernels.pyx:52-90)
+// kind: an APM_KERNEL_* value with kernel_kind_of(kind).on_device() (SE: kernels.pyx:12-49, :52-90)
 // both: write both triangles (else K's lower tiles only); K2.base: the lower tiles of tile
 // columns < k2cols also to K2 (direct-form distances on the fp64 VALU, k_gram)
 void launch_gram(MatB K, const double* X, int64_t ldx, int n, int d, const double* theta,

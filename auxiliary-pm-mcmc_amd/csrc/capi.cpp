@@ -22,7 +22,7 @@
 #include "../../include/apm.h"
 #include "apm_internal.h"
 
-#define APM_VERSION 1
+#define APM_VERSION 2
 
 static thread_local std::string g_err;
 
@@ -1540,7 +1540,7 @@ void init_ctx(apm_ctx* c, int device, int kind, const double* X, int64_t n, int6
         c->ev.far.assign(np32, nullptr);
         for (hipEvent_t* e : c->ev.all()) HIPC(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
-    c->P = kind == APM_KERNEL_ISO ? 2 : (kind == APM_KERNEL_ARD ? (int)d + 1 : 0);
+    c->P = (int)kernel_kind_of(kind).theta_len(d);  // (0: APM_KERNEL_PRECOMPUTED)
     c->S = (int)S;
     c->sp = (int)((S + 63) / 64 * 64);
     c->max_batch = (int)max_batch;
@@ -1695,7 +1695,8 @@ apm_ctx* apm_create(int device, int kernel_kind, const double* X, int64_t n, int
                     int64_t ldx, const double* y, double epsilon, int64_t n_imp,
                     int64_t max_batch, int64_t n_slots, int64_t n_ubufs) {
     if (n <= 0 || d < 0 || n_imp <= 0 || max_batch <= 0 || n_slots <= 0 || n_ubufs <= 0 ||
-        kernel_kind < 0 || kernel_kind > 2 || (kernel_kind != APM_KERNEL_PRECOMPUTED && !X) ||
+        (kernel_kind != APM_KERNEL_PRECOMPUTED && !kernel_kind_of(kernel_kind).on_device()) ||
+        (kernel_kind != APM_KERNEL_PRECOMPUTED && !X) ||
         n_imp > 1 << 20) {
         g_err = "apm_create: invalid arguments";
         return nullptr;
@@ -1979,9 +1980,9 @@ int apm_slot_read(apm_ctx* c, int64_t slot, double* L, int64_t ldl, double* f_po
 int apm_gram(int device, int kind, const double* X, int64_t n, int64_t d, int64_t ldx,
              const double* theta, int64_t n_theta, double eps, double* K, int64_t ldk) {
     if (n <= 0 || d <= 0 || !X || !theta || !K || ldk < n || ldx < d ||
-        (kind != APM_KERNEL_ISO && kind != APM_KERNEL_ARD))
+        !kernel_kind_of(kind).on_device())
         return fail(nullptr, APM_E_INVALID, "apm_gram: bad arguments");
-    const int64_t P = kind == APM_KERNEL_ISO ? 2 : d + 1;
+    const int64_t P = kernel_kind_of(kind).theta_len(d);
     if (n_theta < P) return fail(nullptr, APM_E_INVALID, "apm_gram: theta too short");
     std::lock_guard<std::mutex> lk(g_mu);
     auto key = std::make_tuple(device, n, d, kind + 16);
@@ -2021,9 +2022,9 @@ int apm_gram_cross(int device, int kind, const double* Xs, int64_t m, const doub
                    int64_t d, int64_t ldx, const double* theta, int64_t n_theta, double* Ks,
                    int64_t ldk) {
     if (m <= 0 || n <= 0 || d <= 0 || !Xs || !X || !theta || !Ks || ldk < n || ldx < d ||
-        m > (1 << 24) || n > (1 << 24) || (kind != APM_KERNEL_ISO && kind != APM_KERNEL_ARD))
+        m > (1 << 24) || n > (1 << 24) || !kernel_kind_of(kind).on_device())
         return fail(nullptr, APM_E_INVALID, "apm_gram_cross: bad arguments");
-    const int64_t P = kind == APM_KERNEL_ISO ? 2 : d + 1;
+    const int64_t P = kernel_kind_of(kind).theta_len(d);
     if (n_theta < P) return fail(nullptr, APM_E_INVALID, "apm_gram_cross: theta too short");
     double* dev = nullptr;  // [X: n x d][Xs: m x d][theta: P][s][Ks: m x n]
     try {

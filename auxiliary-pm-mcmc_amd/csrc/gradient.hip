@@ -8,7 +8,8 @@
 //   M = 1/2 a a^T - 1/2 R + 1/2 (q g^T + g q^T)
 //   dLML/dtheta_j = sum_ik M_ik (dK/dtheta_j)_ik
 //   dK/dtheta_0 = S (K without its jitter: s on the diagonal, not s + epsilon),
-//   dK/dtheta_{k+1} = S_ik ((x_ik - x_jk)/tau_k)^2 (ARD), the sum over k of these (iso)
+//   dK/dtheta_{k+1} = G_ik ((x_ik - x_jk)/tau_k)^2 (ARD), the sum over k of these (iso); G = S for
+//   the SE family, cov_G (apm_internal.h) for Matern 3/2 and 5/2
 // with W, L, a of the last Newton iteration (latent_posterior_approximations.py:81-106).
 #include "apm_internal.h"
 
@@ -16,6 +17,13 @@
 #define GP (128 + 2)  // LDS row pitch in doubles (k_gram's)
 // lane (g = lane >> 3 or lane & 7) -> its 8 rows (columns) of the wave's 64x64 tile (k_gram's)
 #define R8(g, p) (((p) >> 2) * 32 + 4 * (g) + ((p) & 3))
+
+// nothing moves across: neither the compiler's passes (memory clobber) nor the machine scheduler
+#define APM_WALL()                           \
+    do {                                     \
+        asm volatile("" ::: "memory");       \
+        __builtin_amdgcn_sched_barrier(0);   \
+    } while (0)
 
 __device__ __forceinline__ bool live_g(const Live& lv, int b) {
     return lv.active[b] != 0 && lv.status[b] == 0;
@@ -129,6 +137,23 @@ void launch_grad_q(const double* s2, const double* u, double* q, int64_t gstride
                np, live);
 }
 
+// k_grad_reduce's staging step (both of a Matern family's passes take it): features [k0, k0 + kc)
+// of the super-tile's rows and columns -> LDS, pre-scaled by 1/tau_k
+#define GRAD_STAGE(k0, kc)                                                                       \
+    do {                                                                                         \
+        __syncthreads();                                                                         \
+        if (tid < kc) itau[tid] = exp(-th[ard == 0 ? 1 : 1 + k0 + tid]);                         \
+        __syncthreads();                                                                         \
+        for (int e = tid; e < 128 * GK; e += 256) {                                              \
+            const int r = e / GK, k = e % GK; /* consecutive lanes: consecutive features */      \
+            const int gi = si * 128 + r, gj = sj * 128 + r;                                      \
+            const double sc = (k < kc) ? itau[k] : 0.0;                                          \
+            xi[k][r] = (k < kc && gi < n) ? X[(int64_t)gi * ldx + k0 + k] * sc : 0.0;            \
+            xj[k][r] = (k < kc && gj < n) ? X[(int64_t)gj * ldx + k0 + k] * sc : 0.0;            \
+        }                                                                                        \
+        __syncthreads();                                                                         \
+    } while (0)
+
 // The contraction sum_ik M_ik (dK/dtheta_j)_ik for every j in one pass over the inputs: k_gram's
 // tiling - one workgroup of 4 waves per lower 128x128 super-tile (si, sj) and chain, wave w the
 // 64x64 tile (2si + w/2, 2sj + w%2) (the upper tile of a diagonal super-tile and tiles beyond the
@@ -143,9 +168,18 @@ void launch_grad_q(const double* s2, const double* u, double* q, int64_t gstride
 // feature; iso adds the features in order into one. Partials go to part[b][t][0..P) for
 // super-tile t; k_grad_sum adds them in tile order. No atomics, no hand-over between workgroups:
 // every output depends on its own chain and on fixed positions only.
-__global__ __launch_bounds__(256) void k_grad_reduce(
+//
+// FAM (APM_FAM_*): for the SE family the one weight w serves theta_0 and the length scales
+// (G = S). For a Matern family the length scales need c M G, and G needs the pair's complete r^2
+// before the per-feature sums start; a second 8x8 block of registers is not available (254
+// VGPRs), so the kernel makes two passes over the staged feature chunks: the first accumulates
+// r^2 into w (k_gram's loop, k in order), the K / R / vector stage adds c M S into theta_0's sum
+// and overwrites w with c M G (cov_G of the lane's own r^2), the second is the SE pass. Every
+// sum keeps the order above. ard: theta[1 + k] scales feature k, else theta[1] every feature.
+template <int FAM>
+__global__ __launch_bounds__(256, FAM == APM_FAM_SE ? 1 : 2) void k_grad_reduce(
     MatB K, MatB Rn, const double* __restrict__ X, int64_t ldx, int n, int d, int nb,
-    const double* __restrict__ theta, int64_t tstride, int kind, const double* __restrict__ avec,
+    const double* __restrict__ theta, int64_t tstride, int ard, const double* __restrict__ avec,
     int64_t vstride, const double* __restrict__ qvec, const double* __restrict__ gvec,
     int64_t gstride, double* __restrict__ part, int64_t pstride, int P, Live live) {
     const int b = blockIdx.y;
@@ -171,51 +205,151 @@ __global__ __launch_bounds__(256) void k_grad_reduce(
 
     double w[8][8];
     double s0 = 0.0;
+    if constexpr (FAM != APM_FAM_SE) {  // first pass: w <- the pairs' r^2 (k_gram's loop)
+#pragma unroll
+        for (int p = 0; p < 8; ++p)
+#pragma unroll
+            for (int q = 0; q < 8; ++q) w[p][q] = 0.0;
+        for (int k0 = 0; k0 < d; k0 += GK) {
+            const int kc = min(GK, d - k0);
+            GRAD_STAGE(k0, kc);
+            if (mine) {
+                for (int k = 0; k < kc; ++k) {
+                    double a[8], c[8];
+#pragma unroll
+                    for (int h = 0; h < 4; ++h) {
+                        const d2_t va = *reinterpret_cast<const d2_t*>(&xi[k][ro + R8(tr, 2 * h)]);
+                        const d2_t vc = *reinterpret_cast<const d2_t*>(&xj[k][co + R8(tc, 2 * h)]);
+                        a[2 * h] = va.x;
+                        a[2 * h + 1] = va.y;
+                        c[2 * h] = vc.x;
+                        c[2 * h + 1] = vc.y;
+                    }
+#pragma unroll
+                    for (int p = 0; p < 8; ++p) {
+                        double df[8];
+#pragma unroll
+                        for (int q = 0; q < 8; ++q) df[q] = a[p] - c[q];  // pre-scaled by 1/tau_k
+#pragma unroll
+                        for (int q = 0; q < 8; ++q) w[p][q] = fma(df[q], df[q], w[p][q]);
+                    }
+                }
+            }
+        }
+    }
     if (mine) {
         const double sigma = exp(th[0]);
         const double* ab = avec + b * vstride;
         const double* qb = qvec + b * gstride;
         const double* gb = gvec + b * gstride;
-        double ak[8], qk[8], gk[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int gj = tj * 64 + R8(tc, q);
-            ak[q] = ab[gj];
-            qk[q] = qb[gj];
-            gk[q] = gb[gj];
-        }
-        const double* Kt = K.base + b * K.cstride + tj * 64 + 4 * tc;
-        const double* Rt = Rn.base + b * Rn.cstride + tj * 64 + 4 * tc;
-#pragma unroll
-        for (int p = 0; p < 8; ++p) {
-            const int gi = ti * 64 + R8(tr, p);
-            const double* kr = Kt + (int64_t)gi * K.ld;
-            const double* rr = Rt + (int64_t)gi * Rn.ld;
-            const d2_t k0 = *reinterpret_cast<const d2_t*>(kr);
-            const d2_t k1 = *reinterpret_cast<const d2_t*>(kr + 2);
-            const d2_t k2 = *reinterpret_cast<const d2_t*>(kr + 32);
-            const d2_t k3 = *reinterpret_cast<const d2_t*>(kr + 34);
-            const d2_t r0 = *reinterpret_cast<const d2_t*>(rr);
-            const d2_t r1 = *reinterpret_cast<const d2_t*>(rr + 2);
-            const d2_t r2 = *reinterpret_cast<const d2_t*>(rr + 32);
-            const d2_t r3 = *reinterpret_cast<const d2_t*>(rr + 34);
-            const double kv[8] = {k0.x, k0.y, k1.x, k1.y, k2.x, k2.y, k3.x, k3.y};
-            const double rv[8] = {r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, r3.x, r3.y};
-            const double ai = ab[gi], qi = qb[gi], gg = gb[gi];
-            double sp = 0.0;
+        if constexpr (FAM == APM_FAM_SE) {
+            double ak[8], qk[8], gk[8];
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 const int gj = tj * 64 + R8(tc, q);
-                const double m = 0.5 * (fma(ai, ak[q], rv[q]) + fma(qi, gk[q], gg * qk[q]));
-                const double sv = (gi == gj) ? sigma : kv[q];
-                const double cnt = (gi > gj) ? 2.0 : 1.0;
-                const bool in = gi < n && gj <= gi;  // (gj <= gi < n)
-                w[p][q] = in ? cnt * (m * sv) : 0.0;
-                sp += w[p][q];
+                ak[q] = ab[gj];
+                qk[q] = qb[gj];
+                gk[q] = gb[gj];
             }
-            s0 += sp;
+            const double* Kt = K.base + b * K.cstride + tj * 64 + 4 * tc;
+            const double* Rt = Rn.base + b * Rn.cstride + tj * 64 + 4 * tc;
+#pragma unroll
+            for (int p = 0; p < 8; ++p) {
+                const int gi = ti * 64 + R8(tr, p);
+                const double* kr = Kt + (int64_t)gi * K.ld;
+                const double* rr = Rt + (int64_t)gi * Rn.ld;
+                const d2_t k0 = *reinterpret_cast<const d2_t*>(kr);
+                const d2_t k1 = *reinterpret_cast<const d2_t*>(kr + 2);
+                const d2_t k2 = *reinterpret_cast<const d2_t*>(kr + 32);
+                const d2_t k3 = *reinterpret_cast<const d2_t*>(kr + 34);
+                const d2_t r0 = *reinterpret_cast<const d2_t*>(rr);
+                const d2_t r1 = *reinterpret_cast<const d2_t*>(rr + 2);
+                const d2_t r2 = *reinterpret_cast<const d2_t*>(rr + 32);
+                const d2_t r3 = *reinterpret_cast<const d2_t*>(rr + 34);
+                const double kv[8] = {k0.x, k0.y, k1.x, k1.y, k2.x, k2.y, k3.x, k3.y};
+                const double rv[8] = {r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, r3.x, r3.y};
+                const double ai = ab[gi], qi = qb[gi], gg = gb[gi];
+                double sp = 0.0;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const int gj = tj * 64 + R8(tc, q);
+                    const double m = 0.5 * (fma(ai, ak[q], rv[q]) + fma(qi, gk[q], gg * qk[q]));
+                    const double sv = (gi == gj) ? sigma : kv[q];
+                    const double cnt = (gi > gj) ? 2.0 : 1.0;
+                    const bool in = gi < n && gj <= gi;  // (gj <= gi < n)
+                    w[p][q] = in ? cnt * (m * sv) : 0.0;
+                    sp += w[p][q];
+                }
+                s0 += sp;
+            }
+        } else {
+            // w <- G of the pair's r^2 while nothing else is live (a few sqrt / exp chains in
+            // flight, not 64: their temporaries must fit beside w)
+#pragma unroll
+            for (int p = 0; p < 8; ++p)
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                    for (int q = 4 * h; q < 4 * h + 4; ++q) w[p][q] = cov_G<FAM>(sigma, w[p][q]);
+                    APM_WALL();
+                }
+            // The SE stage above gives birth to w row by row; here all 64 are live throughout, so
+            // the stage runs over the tile's two runs of 4 columns in turn (half the column
+            // operands and half a row of K and R at a time). theta_0 takes c M S, the length
+            // scales c M G. A row's 8 pairs are still added in order (sp[p] carries the row's
+            // sum from the first run into the second), then the 8 row sums in order: the SE
+            // stage's order. The lane's coordinates are redefined (to themselves) before each
+            // run, so that a run's addresses, masks and row operands are formed when it needs
+            // them and not held from the loops above or for the next run; with the walls this
+            // keeps the instantiation at 248 VGPRs without spills (the compiler otherwise hoists
+            // and shares them and spills up to 114 registers).
+            int trs = tr, tcs = tc;
+            const double* Kt = K.base + b * K.cstride + tj * 64;
+            const double* Rt = Rn.base + b * Rn.cstride + tj * 64;
+            double sp[8];
+#pragma unroll
+            for (int p = 0; p < 8; ++p) sp[p] = 0.0;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                asm volatile("" : "+v"(trs), "+v"(tcs));  // (per run: nothing kept for the next)
+                double ak[4], qk[4], gk[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int gj = tj * 64 + R8(tcs, 4 * h + q);
+                    ak[q] = ab[gj];
+                    qk[q] = qb[gj];
+                    gk[q] = gb[gj];
+                }
+#pragma unroll
+                for (int p = 0; p < 8; ++p) {
+                    const int gi = ti * 64 + R8(trs, p);
+                    const double* kr = Kt + (int64_t)gi * K.ld + 4 * tcs + 32 * h;
+                    const double* rr = Rt + (int64_t)gi * Rn.ld + 4 * tcs + 32 * h;
+                    const d2_t k0 = *reinterpret_cast<const d2_t*>(kr);
+                    const d2_t k1 = *reinterpret_cast<const d2_t*>(kr + 2);
+                    const d2_t r0 = *reinterpret_cast<const d2_t*>(rr);
+                    const d2_t r1 = *reinterpret_cast<const d2_t*>(rr + 2);
+                    const double kv[4] = {k0.x, k0.y, k1.x, k1.y};
+                    const double rv[4] = {r0.x, r0.y, r1.x, r1.y};
+                    const double ai = ab[gi], qi = qb[gi], gg = gb[gi];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int gj = tj * 64 + R8(tcs, 4 * h + q);
+                        const double m = 0.5 * (fma(ai, ak[q], rv[q]) + fma(qi, gk[q], gg * qk[q]));
+                        const double sv = (gi == gj) ? sigma : kv[q];
+                        const double cnt = (gi > gj) ? 2.0 : 1.0;
+                        const bool in = gi < n && gj <= gi;  // (gj <= gi < n)
+                        sp[p] += in ? cnt * (m * sv) : 0.0;
+                        w[p][4 * h + q] = in ? cnt * (m * w[p][4 * h + q]) : 0.0;
+                    }
+                    // (the next rows' loads are not to be hoisted over this row: no room)
+                    APM_WALL();
+                }
+            }
+#pragma unroll
+            for (int p = 0; p < 8; ++p) s0 += sp[p];
         }
-    } else {
+    } else if constexpr (FAM == APM_FAM_SE) {  // (a Matern family's w is zero already)
 #pragma unroll
         for (int p = 0; p < 8; ++p)
 #pragma unroll
@@ -226,17 +360,7 @@ __global__ __launch_bounds__(256) void k_grad_reduce(
     double iso = 0.0;  // (thread 0: the features' sums in order)
     for (int k0 = 0; k0 < d; k0 += GK) {
         const int kc = min(GK, d - k0);
-        __syncthreads();
-        if (tid < kc) itau[tid] = exp(-th[kind == 0 ? 1 : 1 + k0 + tid]);
-        __syncthreads();
-        for (int e = tid; e < 128 * GK; e += 256) {
-            const int r = e / GK, k = e % GK;  // consecutive lanes: consecutive features of a row
-            const int gi = si * 128 + r, gj = sj * 128 + r;
-            const double sc = (k < kc) ? itau[k] : 0.0;
-            xi[k][r] = (k < kc && gi < n) ? X[(int64_t)gi * ldx + k0 + k] * sc : 0.0;
-            xj[k][r] = (k < kc && gj < n) ? X[(int64_t)gj * ldx + k0 + k] * sc : 0.0;
-        }
-        __syncthreads();
+        GRAD_STAGE(k0, kc);
         for (int k = 0; k < kc; ++k) {
             double sk = 0.0;
             if (mine) {
@@ -269,7 +393,7 @@ __global__ __launch_bounds__(256) void k_grad_reduce(
             if (lane == 0) red[wv][k] = sk;
         }
         __syncthreads();
-        if (kind != 0) {
+        if (ard != 0) {
             if (tid < kc) pb[1 + k0 + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
         } else if (tid == 0) {
             for (int k = 0; k < kc; ++k) iso += ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
@@ -280,7 +404,7 @@ __global__ __launch_bounds__(256) void k_grad_reduce(
     __syncthreads();
     if (tid == 0) {
         pb[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
-        if (kind == 0) pb[1] = iso;
+        if (ard == 0) pb[1] = iso;
     }
 }
 
@@ -290,8 +414,11 @@ void launch_grad_reduce(MatB K, MatB Rn, const double* X, int64_t ldx, int n, in
                         double* part, int64_t pstride, int P, Live live, int nchains,
                         hipStream_t s) {
     const int ns = (nb + 1) / 2;
-    APM_LAUNCH(k_grad_reduce, dim3(ns * (ns + 1) / 2, nchains), dim3(256), 0, s, K, Rn, X, ldx, n,
-               d, nb, theta, tstride, kind, a, vstride, q, g, gstride, part, pstride, P, live);
+    const KernelKind kk = kernel_kind_of(kind);
+    APM_FAMILY_DISPATCH(kk.family,
+                        APM_LAUNCH(k_grad_reduce<FAM>, dim3(ns * (ns + 1) / 2, nchains), dim3(256), 0,
+                                   s, K, Rn, X, ldx, n, d, nb, theta, tstride, kk.iso ? 0 : 1, a,
+                                   vstride, q, g, gstride, part, pstride, P, live));
 }
 
 // grad[b][p] = the nst super-tile partials of (chain b, parameter p) added in tile order

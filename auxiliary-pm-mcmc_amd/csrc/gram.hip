@@ -2,6 +2,8 @@
 //
 //   isotropic_squared_exponential_kernel  kernels.pyx:12-49   K_ij = s exp(-|x_i-x_j|^2 / (2 tau^2))
 //   diagonal_squared_exponential_kernel   kernels.pyx:52-90   K_ij = s exp(-1/2 sum_k ((x_ik-x_jk)/tau_k)^2)
+//   Matern 3/2 and 5/2 (no reference counterpart): the same scaled squared distance
+//   through another epilogue (cov_S<FAM>, apm_internal.h), iso or ARD
 //   K_ii = s + eps. both != 0: both triangles written (the reference fills K[i,j] and K[j,i];
 //   the stand-alone apm_gram); both == 0: lower tiles only (the theta-call: every consumer on the
 //   device path reads K's lower tiles, so the upper half is never written - half the bytes).
@@ -29,9 +31,13 @@
 // (the same arithmetic as the reference's loop, kernels.pyx:80-88, up to the pre-scaling).
 // K2 (the concurrent chol(K)'s working copy, capi.cpp chol_k_begin) receives the tiles of tile
 // columns < k2cols only: the first outer panel's trailing update reads the rest from K itself.
+// FAM (APM_FAM_*) selects the epilogue that turns a pair's r^2 into its covariance (cov_S); the
+// distance loop, the LDS staging, the tiling and the stores are the same for every family.
+// ard: theta[1 + k] scales feature k (ARD), else theta[1] scales every feature (iso).
+template <int FAM>
 __global__ __launch_bounds__(256, 2) void k_gram(MatB K, const double* __restrict__ X, int64_t ldx,
                                                  int n, int d, const double* __restrict__ theta,
-                                                 int64_t tstride, int kind, double eps, Live live,
+                                                 int64_t tstride, int ard, double eps, Live live,
                                                  int both, MatB K2, int k2cols, int nb) {
     const int b = blockIdx.y;
     if (live.active[b] == 0 || live.status[b] != 0) return;
@@ -62,7 +68,7 @@ __global__ __launch_bounds__(256, 2) void k_gram(MatB K, const double* __restric
     for (int k0 = 0; k0 < d; k0 += GK) {
         const int kc = min(GK, d - k0);
         __syncthreads();
-        if (tid < kc) itau[tid] = exp(-th[kind == 0 ? 1 : 1 + k0 + tid]);
+        if (tid < kc) itau[tid] = exp(-th[ard ? 1 + k0 + tid : 1]);
         __syncthreads();
         for (int e = tid; e < 128 * GK; e += 256) {
             const int r = e / GK, k = e % GK;  // consecutive lanes: consecutive features of a row
@@ -108,7 +114,7 @@ __global__ __launch_bounds__(256, 2) void k_gram(MatB K, const double* __restric
             double val;
             if (gi < n && gj < n)
                 val = (gi == gj) ? sigma + eps
-                                 : (GRAM_ABL == 1 ? sigma * acc[p][q] : sigma * exp(-0.5 * acc[p][q]));
+                                 : (GRAM_ABL == 1 ? sigma * acc[p][q] : cov_S<FAM>(sigma, acc[p][q]));
             else
                 val = (gi == gj) ? 1.0 : 0.0;
             acc[p][q] = val;
@@ -143,6 +149,9 @@ void launch_gram(MatB K, const double* X, int64_t ldx, int n, int d, const doubl
                  int64_t tstride, int kind, double eps, int np, Live live, int nchains,
                  hipStream_t s, bool both, MatB K2, int k2cols) {
     const int nb = np / 64, ns = (nb + 1) / 2;
-    APM_LAUNCH(k_gram, dim3(ns * (ns + 1) / 2, nchains), dim3(256), 0, s, K, X, ldx, n, d,
-                       theta, tstride, kind, eps, live, (int)both, K2, k2cols, nb);
+    const KernelKind kk = kernel_kind_of(kind);
+    APM_FAMILY_DISPATCH(kk.family,
+                        APM_LAUNCH(k_gram<FAM>, dim3(ns * (ns + 1) / 2, nchains), dim3(256), 0, s, K,
+                                   X, ldx, n, d, theta, tstride, kk.iso ? 0 : 1, eps, live,
+                                   (int)both, K2, k2cols, nb));
 }

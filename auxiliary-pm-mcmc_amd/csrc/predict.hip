@@ -23,10 +23,12 @@
 // from it in the last bit. Every (row, column) value depends on its own pair of points only, and
 // the partial sums of mu* on the column position only: a chain's outputs do not depend on its
 // batch nor a test point's on its block.
+// FAM (APM_FAM_*) selects the epilogue (cov_S), ard the length scales, as in k_gram.
+template <int FAM>
 __global__ __launch_bounds__(256, 2) void k_gram_cross(
     MatB out, int64_t row0, const double* __restrict__ Xs, int ms, int mb,
     const double* __restrict__ X, int64_t ldx, int n, int d, int nb,
-    const double* __restrict__ theta, int64_t tstride, const double* __restrict__ sig, int kind,
+    const double* __restrict__ theta, int64_t tstride, const double* __restrict__ sig, int ard,
     const double* __restrict__ Ws, const double* __restrict__ avec, int64_t vstride,
     double* __restrict__ part, int64_t pstride, Live live, int plain) {
     const int b = blockIdx.y;
@@ -54,7 +56,7 @@ __global__ __launch_bounds__(256, 2) void k_gram_cross(
     for (int k0 = 0; k0 < d; k0 += GK) {
         const int kc = min(GK, d - k0);
         __syncthreads();
-        if (tid < kc) itau[tid] = exp(-th[kind == 0 ? 1 : 1 + k0 + tid]);
+        if (tid < kc) itau[tid] = exp(-th[ard ? 1 + k0 + tid : 1]);
         __syncthreads();
         for (int e = tid; e < 128 * GK; e += 256) {
             const int r = e / GK, k = e % GK;  // consecutive lanes: consecutive features of a row
@@ -94,7 +96,7 @@ __global__ __launch_bounds__(256, 2) void k_gram_cross(
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             const int gi = ti * 64 + R8(tr, p), gj = tj * 64 + R8(tc, q);
-            acc[p][q] = (gi < ms && gj < n) ? sigma * exp(-0.5 * acc[p][q]) : 0.0;
+            acc[p][q] = (gi < ms && gj < n) ? cov_S<FAM>(sigma, acc[p][q]) : 0.0;
         }
 
     if (plain) {  // apm_gram_cross: k* itself into an ms x n buffer (any ld: scalar stores)
@@ -147,8 +149,11 @@ void launch_gram_cross(MatB out, int64_t row0, const double* Xs, int ms, int mb,
                        int64_t vstride, double* part, int64_t pstride, Live live, int plain,
                        int nchains, hipStream_t s) {
     const int nsr = (mb + 1) / 2, nsc = (nb + 1) / 2;
-    APM_LAUNCH(k_gram_cross, dim3(nsr * nsc, nchains), dim3(256), 0, s, out, row0, Xs, ms, mb, X,
-               ldx, n, d, nb, theta, tstride, sig, kind, Ws, a, vstride, part, pstride, live, plain);
+    const KernelKind kk = kernel_kind_of(kind);
+    APM_FAMILY_DISPATCH(kk.family,
+                        APM_LAUNCH(k_gram_cross<FAM>, dim3(nsr * nsc, nchains), dim3(256), 0, s, out,
+                                   row0, Xs, ms, mb, X, ldx, n, d, nb, theta, tstride, sig,
+                                   kk.iso ? 0 : 1, Ws, a, vstride, part, pstride, live, plain));
 }
 
 // One wave per (chain, test row): the squared norm of the row of V^T = (W^1/2 . k*)^T L^-T over

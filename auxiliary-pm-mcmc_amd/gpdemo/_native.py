@@ -15,6 +15,9 @@ LIB_PATH = os.environ.get('APM_LIB', os.path.join(_PKG_ROOT, 'lib', 'libapm.so')
 
 # include/apm.h constants
 KERNEL_ISO, KERNEL_ARD, KERNEL_PRECOMPUTED = 0, 1, 2
+KERNEL_M32_ISO, KERNEL_M32_ARD, KERNEL_M52_ISO, KERNEL_M52_ARD = 3, 4, 5, 6
+# the kinds with one length scale (theta has 2 entries; the others' has d + 1)
+_ISO_KINDS = (KERNEL_ISO, KERNEL_M32_ISO, KERNEL_M52_ISO)
 EST_IS, EST_PRIORMC, EST_LAPLACE = 0, 1, 2
 APM_SUCCESS, APM_E_INVALID, APM_E_HIP, APM_E_NOMEM = 0, -1, -2, -3
 STATUS_OK, STATUS_CHOL_K, STATUS_CHOL_B, STATUS_CHOL_C, STATUS_MAXITER = 0, 1, 2, 3, 4
@@ -126,12 +129,13 @@ def default_device():
 
 
 def gram(kind, K, X, theta, epsilon, device=None):
-    """Fill K (any writable float64 (n, n) array) with the SE Gram matrix computed on the GPU."""
+    """Fill K (any writable float64 (n, n) array) with the Gram matrix of covariance kind `kind`
+    (SE or Matern, iso or ARD) computed on the GPU."""
     lib = load_library()
     X = _f64(X)
     theta = _f64(np.atleast_1d(theta))
     n, d = X.shape
-    need = 2 if kind == KERNEL_ISO else d + 1
+    need = 2 if kind in _ISO_KINDS else d + 1
     if theta.shape[0] < need:
         # kernels.pyx indexes theta[k+1] / theta[1] with bounds checking -> IndexError
         raise IndexError('Out of bounds on buffer access (axis 0)')
@@ -145,15 +149,15 @@ def gram(kind, K, X, theta, epsilon, device=None):
 
 
 def gram_cross(kind, X_test, X, theta, device=None):
-    """(m, n) cross-covariance k(X_test_i, X_j) of the SE kernel on the GPU: no epsilon, also
-    where a test point coincides with a training point."""
+    """(m, n) cross-covariance k(X_test_i, X_j) of covariance kind `kind` on the GPU: no epsilon,
+    also where a test point coincides with a training point."""
     lib = load_library()
     X, Xs = _f64(X), _f64(X_test)
     theta = _f64(np.atleast_1d(theta))
     n, d = X.shape
     if Xs.ndim != 2 or Xs.shape[1] != d:
         raise ValueError('X_test has shape {0}, expected (m, {1})'.format(Xs.shape, d))
-    if theta.shape[0] < (2 if kind == KERNEL_ISO else d + 1):
+    if theta.shape[0] < (2 if kind in _ISO_KINDS else d + 1):
         raise IndexError('Out of bounds on buffer access (axis 0)')
     Ks = np.empty((Xs.shape[0], n))
     _check(lib.apm_gram_cross(default_device() if device is None else device, kind, _ptr(Xs),

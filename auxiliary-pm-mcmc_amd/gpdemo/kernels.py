@@ -1,17 +1,29 @@
 # -*- coding: utf-8 -*-
-"""Squared-exponential Gram builders on the GPU (replace the reference's Cython kernels.pyx).
+"""Gram builders on the GPU: the squared-exponential kernels that replace the reference's Cython
+kernels.pyx, and the Matérn 3/2 and 5/2 families beside them.
 
-The two functions keep the reference signature ``f(K, X, theta, epsilon=1e-8)`` and fill the
+Every function keeps the reference signature ``f(K, X, theta, epsilon=1e-8)`` and fills the
 caller-owned ``K`` in place (kernels.pyx:12-49, :52-90); ``theta`` entries beyond the ones the
 kernel reads are ignored and a too-short ``theta`` raises ``IndexError`` as the bounds-checked
 Cython does. :func:`make_kernel_func` returns the ``kernel_func(K, X, theta)`` callable the
 estimators expect; the estimators recognise it and build K directly in device memory instead of
 round-tripping it through the host.
+
+With ``s = exp(theta[0])``, ``tau_k = exp(theta[k+1])`` (ARD) or ``exp(theta[1])`` for every k
+(isotropic) and ``r = sqrt(sum_k ((x_ik - x_jk) / tau_k)^2)``::
+
+    squared exponential   s exp(-r^2 / 2)
+    Matérn 3/2            s (1 + sqrt(3) r) exp(-sqrt(3) r)
+    Matérn 5/2            s (1 + sqrt(5) r + 5/3 r^2) exp(-sqrt(5) r)
+
+plus ``epsilon`` on the diagonal (one point set's Gram only).
 """
 from . import _native
 
 __all__ = ['isotropic_squared_exponential_kernel', 'diagonal_squared_exponential_kernel',
-           'make_kernel_func', 'SEKernelFunc']
+           'isotropic_matern32_kernel', 'diagonal_matern32_kernel',
+           'isotropic_matern52_kernel', 'diagonal_matern52_kernel',
+           'make_kernel_func', 'SEKernelFunc', 'MaternKernelFunc']
 
 
 def isotropic_squared_exponential_kernel(K, X, theta, epsilon=1e-8):
@@ -22,6 +34,26 @@ def isotropic_squared_exponential_kernel(K, X, theta, epsilon=1e-8):
 def diagonal_squared_exponential_kernel(K, X, theta, epsilon=1e-8):
     """K[i,j] = exp(theta[0]) exp(-1/2 sum_k ((x_ik - x_jk) / exp(theta[k+1]))^2) + eps [i == j]."""
     _native.gram(_native.KERNEL_ARD, K, X, theta, epsilon)
+
+
+def isotropic_matern32_kernel(K, X, theta, epsilon=1e-8):
+    """Matérn 3/2 with one length scale exp(theta[1]), + epsilon [i == j]."""
+    _native.gram(_native.KERNEL_M32_ISO, K, X, theta, epsilon)
+
+
+def diagonal_matern32_kernel(K, X, theta, epsilon=1e-8):
+    """Matérn 3/2 with a length scale exp(theta[k+1]) per feature (ARD), + epsilon [i == j]."""
+    _native.gram(_native.KERNEL_M32_ARD, K, X, theta, epsilon)
+
+
+def isotropic_matern52_kernel(K, X, theta, epsilon=1e-8):
+    """Matérn 5/2 with one length scale exp(theta[1]), + epsilon [i == j]."""
+    _native.gram(_native.KERNEL_M52_ISO, K, X, theta, epsilon)
+
+
+def diagonal_matern52_kernel(K, X, theta, epsilon=1e-8):
+    """Matérn 5/2 with a length scale exp(theta[k+1]) per feature (ARD), + epsilon [i == j]."""
+    _native.gram(_native.KERNEL_M52_ARD, K, X, theta, epsilon)
 
 
 class SEKernelFunc(object):
@@ -41,5 +73,34 @@ class SEKernelFunc(object):
         return 'SEKernelFunc({0!r}, epsilon={1!r})'.format(self.kind, self.epsilon)
 
 
+_MATERN_KINDS = {'matern32_iso': _native.KERNEL_M32_ISO, 'matern32_ard': _native.KERNEL_M32_ARD,
+                 'matern52_iso': _native.KERNEL_M52_ISO, 'matern52_ard': _native.KERNEL_M52_ARD}
+
+
+class MaternKernelFunc(object):
+    """``kernel_func(K, X, theta)`` for 'matern32_iso', 'matern32_ard', 'matern52_iso' or
+    'matern52_ard'. Like :class:`SEKernelFunc` it carries ``native_kind`` and ``epsilon``, which
+    is what sends the estimators, ``LaplacePredictor`` and ``LaplaceGradient`` down the device
+    path."""
+
+    def __init__(self, kind, epsilon=1e-8):
+        if kind not in _MATERN_KINDS:
+            raise ValueError('kind must be one of {0}'.format(sorted(_MATERN_KINDS)))
+        self.kind = kind
+        self.epsilon = float(epsilon)
+        self.native_kind = _MATERN_KINDS[kind]
+
+    def __call__(self, K, X, theta):
+        _native.gram(self.native_kind, K, X, theta, self.epsilon)
+
+    def __repr__(self):
+        return 'MaternKernelFunc({0!r}, epsilon={1!r})'.format(self.kind, self.epsilon)
+
+
 def make_kernel_func(kind, epsilon=1e-8):
-    return SEKernelFunc(kind, epsilon)
+    """'iso' | 'ard' (SE) or 'matern32_iso' | 'matern32_ard' | 'matern52_iso' | 'matern52_ard'."""
+    if kind in _MATERN_KINDS:
+        return MaternKernelFunc(kind, epsilon)
+    if kind in ('iso', 'ard'):
+        return SEKernelFunc(kind, epsilon)
+    raise ValueError("kind must be 'iso', 'ard' or one of {0}".format(sorted(_MATERN_KINDS)))

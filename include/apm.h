@@ -58,6 +58,19 @@ extern "C" {
 #define APM_KERNEL_ISO 0         /* kernels.pyx:12-49, theta = (log sigma, log tau) */
 #define APM_KERNEL_ARD 1         /* kernels.pyx:52-90, theta = (log sigma, log tau_1..tau_D) */
 #define APM_KERNEL_PRECOMPUTED 2 /* K supplied by the caller (apm_theta_eval_K) */
+/* Matern covariance functions, built on the device like the two SE kernels (no reference
+ * counterpart: kernels.pyx has the SE family only). Same theta layout as ISO / ARD: s =
+ * exp(theta_0), tau_k = exp(theta_{k+1}) (ARD, d + 1 entries) or exp(theta_1) for every k (ISO, 2
+ * entries), r = sqrt(sum_k ((x_ik - x_jk)/tau_k)^2):
+ *   Matern 3/2  S = s (1 + sqrt3 r) exp(-sqrt3 r)
+ *   Matern 5/2  S = s (1 + sqrt5 r + 5/3 r^2) exp(-sqrt5 r)
+ * with the SE kernels' epsilon rule: K = S + epsilon I on one point set's Gram only, none on
+ * apm_gram_cross / k*, prior variance k** = s. Accepted wherever ISO / ARD are: apm_create,
+ * apm_gram, apm_gram_cross, apm_theta_eval (all estimators), apm_predict, apm_laplace_grad. */
+#define APM_KERNEL_M32_ISO 3
+#define APM_KERNEL_M32_ARD 4
+#define APM_KERNEL_M52_ISO 5
+#define APM_KERNEL_M52_ARD 6
 
 /* estimators */
 #define APM_EST_IS 0       /* LogMarginalLikelihoodApproxPosteriorISEstimator */
@@ -66,6 +79,7 @@ extern "C" {
 
 typedef struct apm_ctx apm_ctx;
 
+/* 2: the Matern kinds APM_KERNEL_M32_* / APM_KERNEL_M52_* (1: SE and PRECOMPUTED only) */
 int apm_version(void);
 int apm_device_count(void);
 const char *apm_global_error(void);
@@ -106,7 +120,8 @@ int apm_theta_eval_K(apm_ctx *ctx, int estimator, const double *K, int64_t ldk, 
 /* Laplace predictive at m test inputs Xs (m x d, ldxs) for `count` thetas (count <= max_batch):
  * Gram -> fp64 Newton (apm_set_newton settings) -> mean/var/prob, each count x m with row stride
  * ldo (any of the three may be NULL). status[i]: APM_STATUS_* of chain i (outputs of a failed
- * chain are NaN); n_iter[i] (may be NULL): Newton iterations. Needs an ISO or ARD context.
+ * chain are NaN); n_iter[i] (may be NULL): Newton iterations. Needs an ISO or ARD context of
+ * any family (SE, Matern 3/2, Matern 5/2), not a PRECOMPUTED one.
  * mean = k*^T a, var = s - |L^-1 (W^1/2 . k*)|^2 with s = exp(theta_0) (no epsilon on k* or k**:
  * kernels.pyx adds it to the diagonal of one point set's Gram only), prob = Phi(mean /
  * sqrt(1 + var)); W, L, a of the last Newton iteration (lpa.py:81-112). Nothing is clamped.
@@ -118,7 +133,7 @@ int apm_predict(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ldt,
  * (count <= max_batch): Gram -> fp64 Newton (apm_set_newton settings) -> lml[i] (may be NULL) and
  * grad row i (count x P, row stride ldg >= P = apm_theta_len). status[i]: APM_STATUS_* of chain i
  * (lml and the grad row of a failed chain are NaN); n_iter[i] (may be NULL): Newton iterations.
- * Needs an ISO or ARD context. No reference counterpart. With W, W^1/2, L = chol(I + W^1/2 K
+ * Needs an ISO or ARD context of any family, not a PRECOMPUTED one. No reference counterpart. With W, W^1/2, L = chol(I + W^1/2 K
  * W^1/2), a of the last Newton iteration and the mode f = K a (lpa.py:81-106):
  *   v = phi(f)/Phi(y f), g = y v, d3 = -[(2v + y f)(-f v - y v^2) + y v],
  *   R = Z^T Z with Z = L^-1 diag(W^1/2), dS_i = K_ii - |L^-1 (W^1/2 . K[:, i])|^2,
@@ -126,7 +141,10 @@ int apm_predict(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ldt,
  *   grad_j = sum_ik M_ik (dK/dtheta_j)_ik,
  * dK/dtheta_0 = S, the covariance function WITHOUT epsilon (its diagonal is exp(theta_0): the
  * jitter kernels.pyx adds does not depend on theta), dK/dtheta_{k+1} = S_ik ((x_ik - x_jk) /
- * tau_k)^2 (ARD) or the sum over k of these (ISO); K = S + epsilon I everywhere else. This is the
+ * tau_k)^2 (ARD) or the sum over k of these (ISO); K = S + epsilon I everywhere else. For a
+ * Matern kind the length-scale derivative is G_ik ((x_ik - x_jk) / tau_k)^2 with G = 3 s
+ * exp(-sqrt3 r) (3/2) or G = 5/3 s (1 + sqrt5 r) exp(-sqrt5 r) (5/2): finite at r = 0, zero
+ * diagonal; dK/dtheta_0 = S as for SE. This is the
  * derivative at the exact mode: at a loose diff_f_tol it is approximate.
  * lml[i] is bitwise the value apm_theta_eval(APM_EST_LAPLACE) returns for the same theta and
  * Newton settings: that call always takes this fp64 Newton path, so no setting is needed.
