@@ -6,10 +6,9 @@ import math
 
 import numpy as np
 import pytest
-import scipy.linalg as la
-from scipy.special import log_ndtr, ndtr
 
 import apm_oracle as orc
+from predict_restatement import predictive
 
 pytestmark = pytest.mark.gpu
 
@@ -36,29 +35,7 @@ def _assert_gram_close(K, Kref):
     assert not bad.any(), (np.abs(K - Kref)[bad].max(), bad.sum())
 
 
-def _oracle(K, Ks, y, sigma, tol=1e-4, max_iters=1000):
-    """Newton loop of latent_posterior_approximations.py:81-99, then the predictive from the
-    last iteration's W, L, a: mu = Ks a, var = sigma - |L^-1 (W^1/2 . ks)|^2, Phi(mu/sqrt(1+var))."""
-    n = y.shape[0]
-    f, it = np.zeros(n), 0
-    while True:
-        v = np.exp(-0.5 * f ** 2 - log_ndtr(y * f) - 0.5 * np.log(2 * np.pi))
-        grad = v * y
-        W = v ** 2 + grad * f
-        Ws = np.sqrt(W)
-        L = la.cholesky(np.eye(n) + Ws[:, None] * K * Ws[None, :], lower=True)
-        b = W * f + grad
-        a = b - Ws * la.cho_solve((L, True), Ws * K.dot(b))
-        f_new = K.dot(a)
-        it += 1
-        done = np.mean((f_new - f) ** 2) < tol
-        f = f_new
-        if done or it >= max_iters:
-            break
-    mu = Ks.dot(a)
-    V = la.solve_triangular(L, (Ks * Ws[None, :]).T, lower=True)
-    var = sigma - (V * V).sum(0)
-    return dict(mean=mu, var=var, prob=ndtr(mu / np.sqrt(1.0 + var)), n_iter=it, f=f, a=a)
+_oracle = predictive  # (the restatement, shared with test_gpu_laplace_edges.py)
 
 
 def _make_case(n, d, m, kind, seed):

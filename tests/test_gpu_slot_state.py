@@ -433,3 +433,46 @@ def test_leading_dimensions_through_the_c_abi(nat):
         np.testing.assert_array_equal(a, b)
     v = eval_k(n)[0]  # the caller's K is the library's own Gram at thetas[1]
     assert abs(v - ref[0][1]) <= 1e-9 * max(1., abs(v)), (v, ref[0][1])
+
+    # apm_predict: m = 130 test rows in two blocks (np = 128), two chains of a max_batch = 3
+    # context into three-row outputs: the third row is padding too
+    m = 130
+    Xs = np.random.RandomState(6).normal(size=(m, D))
+
+    def predict(ldxs, ldo, with_mean=True):
+        Xsb = _padded(Xs, ldxs)
+        h = lib.apm_create(0, nat.KERNEL_ARD, p(X), n, D, D, p(y), 1e-8, s, 3, 1, 1)
+        assert h
+        outs = [np.full((3, ldo), SENTINEL) for _ in range(3)]
+        st, nit = np.full(3, -1, np.int32), np.full(3, -1, np.int64)
+        assert lib.apm_predict(h, 2, p(thetas), P, p(Xsb), m, ldxs,
+                               p(outs[0]) if with_mean else None, p(outs[1]), p(outs[2]), ldo,
+                               p(st), p(nit)) == 0
+        lib.apm_destroy(h)
+        assert list(st) == [0, 0, -1] and nit[2] == -1 and (nit[:2] > 0).all()
+        assert _padding_intact(Xsb, D)
+        for o in outs:
+            assert _padding_intact(o, m) and (o[2] == SENTINEL).all()
+        if not with_mean:
+            assert (outs[0] == SENTINEL).all()
+        return [o[:2, :m].copy() for o in outs] + [nit[:2].copy()]
+
+    pref = predict(D, m)
+    assert all(np.isfinite(o).all() for o in pref)
+    for a, b in zip(predict(D + 3, m + 4), pref):
+        np.testing.assert_array_equal(a, b)
+    for a, b in zip(predict(D + 3, m + 4, with_mean=False)[1:], pref[1:]):
+        np.testing.assert_array_equal(a, b)
+
+    # apm_gram_cross: ldx is the row stride of both point sets
+    def gram_cross(ldx, ldk):
+        Xb, Xsb = _padded(X, ldx), _padded(Xs, ldx)
+        Kb = np.full((m, ldk), SENTINEL)
+        assert lib.apm_gram_cross(0, nat.KERNEL_ARD, p(Xsb), m, p(Xb), n, D, ldx, p(thetas[1]), P,
+                                  p(Kb), ldk) == 0
+        assert _padding_intact(Kb, n) and _padding_intact(Xb, D) and _padding_intact(Xsb, D)
+        return Kb[:, :n].copy()
+
+    Ks = gram_cross(D, n)
+    assert np.isfinite(Ks).all() and (Ks > 0.0).all()
+    np.testing.assert_array_equal(gram_cross(D + 3, n + 7), Ks)

@@ -33,6 +33,28 @@ def test_restatement_vs_central_differences(n, d, kind, seed):
         assert err <= 1e-6
 
 
+def test_edge_case_seeds_keep_their_newton_margins():
+    """The inputs of test_gpu_laplace_edges.py (tests/edge_cases.py), checked without a device:
+    at every size and theta it uses, the restatement's last Newton diff is <= 1e-14 / 100 and the
+    one before >= 100 x 1e-14 (the gradient's tolerance), and the first diff below 1e-4 (the
+    predictor's and apm_laplace's) is <= 1e-4 / 3, the one before >= 3e-4: device and restatement
+    cannot disagree on an iteration count at either tolerance."""
+    import edge_cases as ec
+    keys = [(None, 'ard', n) for n in ec.SIZES] + sorted(ec.MATERN)
+    for family, kind, n in keys:
+        c = ec.case(n, family, kind)
+        assert len(c['thetas']) == (3 if n <= 513 else 2)
+        for th in c['thetas']:
+            diffs = gr.newton(ec.gram(c, th), c['y'], ec.GRAD_TOL)['diffs']
+            k = ec.fit_iterations(diffs)
+            print('edge margins {0}: {1} iterations, last diffs {2:.2e} {3:.2e}; {4} at 1e-4, '
+                  'diffs {5:.2e} {6:.2e}'.format((family, kind, n, float(th[0])), len(diffs), diffs[-2],
+                                                  diffs[-1], k, diffs[k - 2], diffs[k - 1]))
+            assert diffs[-1] <= ec.GRAD_TOL / 100.0 and diffs[-2] >= 100.0 * ec.GRAD_TOL
+            assert k >= 2 and diffs[k - 1] <= ec.FIT_TOL / 3.0 and diffs[k - 2] >= 3.0 * ec.FIT_TOL
+            assert ec.margins_hold(diffs)
+
+
 def test_restatement_epsilon_rule_is_visible():
     """With epsilon = 1e-2 the wrong reading (epsilon kept on dK/dtheta_0's diagonal) moves
     grad[0] by epsilon * trace(M), far above the central-difference error."""
