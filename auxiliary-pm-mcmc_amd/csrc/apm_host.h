@@ -1,0 +1,411 @@
+// What the host orchestration units share: the context, the cross-stream edges, error and
+// profiling plumbing, and the functions one unit calls in another. The kernel launchers are in
+// apm_internal.h; the C-ABI (include/apm.h) is implemented in capi.cpp.
+//   host_ctx.cpp      context allocation, environment knobs, stream skew, profiling, read-back,
+//                     per-call uploads, fp64 factors of wide slots
+//   host_chol64.cpp   update-list caches, the fp64 two-level Cholesky schedule (two forms)
+//   host_newton.cpp   fp32 Newton factorisation with its lookahead, the Newton loop, fp64 rerun
+//   host_theta.cpp    the theta-call: concurrent chol(K), posterior factor, guard, ICM check
+//   host_laplace.cpp  apm_laplace's covariance, the predictive and gradient paths
+// Everything shared has hidden visibility: the library exports the apm_* functions only.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <functional>
+#include <initializer_list>
+#include <map>
+#include <string>
+#include <tuple>
+#include <utility>
+#include <vector>
+
+#include "../../include/apm.h"
+#include "apm_internal.h"
+
+#define HIPC(x)                                                                              \
+    do {                                                                                     \
+        hipError_t e_ = (x);                                                                 \
+        if (e_ != hipSuccess)                                                                \
+            throw HipError{std::string(#x) + ": " + hipGetErrorString(e_)};                  \
+    } while (0)
+
+namespace apm_host __attribute__((visibility("hidden"))) {
+
+struct ProfRec {
+    hipEvent_t a, b;
+    int kind;
+    double work;
+};
+
+// per chain: the trace(C) below which the reference's route to chol(C) is checked (icm_check):
+// C's mean diagonal below APM_ICM_Q^-1 of K's largest diagonal entry, i.e. K - V^T V cancels
+// ~log10(APM_ICM_Q) digits or more (1e-7 of K_ii at the golden ICM theta icm_a, 1e-5 at icm_b;
+// ~1/4 at configs[2]'s sigma = e^18.5, and no chain of the bench's stationary states: unchecked)
+#define APM_ICM_Q 1.0e3
+
+// The cross-stream edges of a theta-call, one event each (DESIGN.md §11 names the producer and
+// the consumer of every one). No event is recorded again before the wait that names its previous
+// record has been enqueued: the per-panel edges are indexed by panel; the Newton lookahead's
+// per-panel pair is recorded once per factorisation, and a factorisation starts only after the
+// previous one's last far update was joined into the main stream.
+struct Edges {
+    hipEvent_t gram_k = nullptr;       // main -> s2: the Gram wrote K (and BL's first panel)
+    hipEvent_t cholk_done = nullptr;   // s2 -> main: L_K final in BL, its log-det in ldet + nb
+    hipEvent_t y2 = nullptr;           // main -> s2: L_K J formed in BL (k_form_y2_rev)
+    hipEvent_t bottom_done = nullptr;  // s2 -> main: the fp32 bottom block (S32) final
+    std::vector<hipEvent_t> cholk_rel; // main -> s2, per chol(K) panel: its release (no data)
+    std::vector<hipEvent_t> lp_panel;  // main -> s2, per panel of L': tiles and inverses final
+    std::vector<hipEvent_t> df;        // main -> s3, per Newton panel: its columns + planes final
+    std::vector<hipEvent_t> far;       // s3 -> main, per Newton panel: its far update done
+    std::vector<hipEvent_t*> all() {
+        std::vector<hipEvent_t*> v{&gram_k, &cholk_done, &y2, &bottom_done};
+        for (auto* w : {&cholk_rel, &lp_panel, &df, &far})
+            for (hipEvent_t& e : *w) v.push_back(&e);
+        return v;
+    }
+};
+
+// a device-resident update list (tile, super-tile or quad-tile order) and its length
+typedef std::pair<unsigned*, int> DevList;
+typedef std::map<std::tuple<int, int, int, int, int, int>, DevList> ListCache;
+
+// The pinned staging buffers, every field max_batch (B) entries long. The per-call uploads are
+// single copies that rely on a field's neighbours, on the host as on the device:
+//   hpin: [slots | ubufs] int64 (-> d_slots | d_ubufs), [h3ok | h3post | invok] int (-> h3ok ..),
+//         one int of padding per chain, [icm thresholds] double (-> icm_thr)
+//   hblk: the 7 B words of the d_i3 block (apm_u_normal / apm_u_combine), fields of StageBlk
+//   hx:   the read-back buffer, sized for a theta-call's [logf double | status | n_iter | wide]
+struct StagePin {
+    int64_t B;
+    size_t slots() const { return 0; }
+    size_t ubufs() const { return slots() + sizeof(int64_t) * B; }
+    size_t h3ok() const { return ubufs() + sizeof(int64_t) * B; }
+    size_t h3post() const { return h3ok() + sizeof(int) * B; }
+    size_t invok() const { return h3post() + sizeof(int) * B; }
+    size_t icm() const { return invok() + 2 * sizeof(int) * B; }
+    size_t bytes() const { return icm() + sizeof(double) * B; }
+};
+enum StageBlk {  // word offsets, in units of B: ubufs / dst share the first field
+    BLK_I3 = 0, BLK_A = 1, BLK_B = 2, BLK_CA = 3, BLK_CB = 4, BLK_SEEDS = 5, BLK_CTRS = 6,
+    BLK_FIELDS = 7
+};
+inline size_t read_back_bytes(int64_t B) { return (sizeof(double) + 3 * sizeof(int)) * B; }
+
+}  // namespace apm_host
+
+struct __attribute__((visibility("hidden"))) apm_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int kind = 0, n = 0, d = 0, np = 0, nb = 0, P = 0, S = 0, sp = 0;
+    int max_batch = 0, n_slots = 0, n_ubufs = 0;
+    // tiles per outer panel of the fp64 factorisations and of the Newton matrix (<= 14: the
+    // dataflow panel's progress word packs the column step in 4 bits, 15 = failed;
+    // rhs_row_update32 covers a depth of 16 tiles; the explicit-inverse panels need 8)
+    static constexpr int outer = 8, outer32 = 8;
+    static constexpr int symv_tpw = 2;  // K x: lower tiles per workgroup (launch_symv)
+    std::vector<int> slot_refs;  // owners of each cache slot (apm_cache_*; 0 = free)
+    std::vector<int> slot_wide;  // host mirror of Sl.wide (read back with each theta-call)
+    // fp64 factors of the wide slots: one np x np buffer attached per wide slot (Sl.L64 is the
+    // device copy of l64_h), returned to l64_free when its slot is rewritten narrow
+    std::vector<double*> l64_h, l64_free;
+    double** l64_d = nullptr;
+    double eps = 1e-8, tol = 1e-4;
+    int64_t max_iters = 1000;
+    std::string err;
+    // device data
+    double *X = nullptr, *y = nullptr, *theta = nullptr;
+    MatB K{}, A{};
+    double *Dinv = nullptr, *ldet = nullptr, *out = nullptr, *partial = nullptr;
+    int64_t dstride = 0, lstride = 0, pstride = 0;
+    NewtonVecs v{};
+    double* vecbase = nullptr;
+    double* rvec = nullptr;   // 3 refinement vectors per chain (mixed-precision Newton)
+    double* sympart = nullptr;  // symmetric K x partials: nb*nb*64 per chain (launch_symv)
+    int64_t sstride = 0;
+    bool mixed = true;        // APM_MIXED=0: fp64 Newton factorisation (development knob)
+    int n_refine = 3;         // maximum refinement steps per solve
+    double refine_tol = 1e-3; // acceptance of a refinement step (k_refine_check)
+    int *active = nullptr, *status = nullptr, *n_iter = nullptr;
+    int* refining = nullptr;  // chains still refining their Newton solve
+    double* refine_prev = nullptr;  // max|d| of the previous refinement step per chain
+    int64_t n_refine_steps = 0, n_fp64_rerun = 0;  // statistics (apm_prof_read APM_PROF_STATS)
+    int64_t n_icm_check = 0;  // chains whose C was formed the reference's way (icm_check)
+    int64_t n_guard = 0;      // chains failed by the guard (APM_STATUS_GUARD)
+    // APM_ICM_Q: the threshold of the check of the reference's chol(C) (icm_check; test knob: a
+    // huge value checks every chain, 0 checks none)
+    double icm_q = APM_ICM_Q;
+    int64_t *d_slots = nullptr, *d_ubufs = nullptr, *d_i3 = nullptr;  // d_ubufs = d_slots + B
+    // pinned host staging of the per-call uploads (one H2D of slots + ubufs; the per-chain
+    // flags and icm thresholds): layout StagePin
+    char* hpin = nullptr;
+    int64_t* hblk = nullptr;  // pinned mirror of the d_i3 .. d_ctrs block (StageBlk)
+    double* hth = nullptr;    // pinned theta staging (B x P)
+    // read-back buffer: mapped, coherent pinned host memory (read_back_bytes) written by k_export,
+    // dx its device address
+    unsigned* hx = nullptr;
+    unsigned* dx = nullptr;
+    double *d_ca = nullptr, *d_cb = nullptr;
+    uint64_t *d_seeds = nullptr, *d_ctrs = nullptr;
+    double* U64 = nullptr;
+    SlotSet Sl{};
+    UPool Up{};
+    std::vector<void*> allocs;
+    // K's upper triangle holds valid data (host-uploaded K); otherwise every K x product uses the
+    // symmetric lower-tile kernel (launch_symv)
+    bool k_full = false;
+    // profiling
+    int prof = 0;  // apm_prof_enable level
+    std::vector<hipEvent_t> evpool;
+    size_t evnext = 0;
+    std::vector<apm_host::ProfRec> recs;
+    // update lists per launch shape, built once, kept on the device (cached_list): 64x64 tiles
+    // and 128x128 super-tiles keyed by (i0, R, j0, jend, gap lo, gap hi), the super-tiles with a
+    // row tile of its own (solo) apart, the lookahead's extended lists keyed by (i0, R, j0, jend,
+    // rhs, jext), the 256x256 quad tiles by (i0, R, j0, jend)
+    apm_host::ListCache tile_lists, super_lists, super_lists_solo, super_lists_ext;
+    std::map<std::tuple<int, int, int, int>, apm_host::DevList> quad_lists;
+    bool h3 = true;       // APM_H3=0: fp32 operands in the fp32 factorisations' outer updates
+    bool h3_now = false;  // some chain of the current theta-call may use fp16x3 updates
+    bool h3_all = false;  // ... and every chain may (the quad-tile far updates need that)
+    bool h3post_all = false;  // every chain takes fp16x3 operands in the posterior bottom block
+    int* h3ok = nullptr;  // per chain: fp16x3 allowed (range check on theta_0, chol32.hip)
+    int* h3post = nullptr;  // the same for the posterior factor's fp32 bottom block (h3ok + B)
+    // per chain: explicit-inverse Newton panels allowed (h3ok + 2B): their fp16x3 operands are
+    // Schur-complement entries of B, bounded by max B_ii <= 1 + K_ii (not by sqrt(B_ii) as the
+    // walk's solved entries are), so the range check is on 1 + K_ii itself (chol32.hip)
+    int* invok = nullptr;
+    bool inv_any = false, inv_all = false;
+    double* icm_thr = nullptr;  // per chain: SlotSet::icm_thr
+    // the bottom block of the posterior factor [[J M J],[L_K J]] (the TRSM that yields chol(C) J)
+    // in fp32 panel by panel beside the fp64 factorisation of J M J (postcov.hip); chains whose
+    // trace(C) exceeds Sl.post_q are recomputed in fp64 (n_post64 counts them)
+    int* hmask = nullptr;  // pinned: the chains of such a recomputation
+    int64_t n_post64 = 0;
+    // the Newton factorisation's dataflow launches also write the panel's fp16x3 operand planes
+    // (Planes16), which the trailing updates stage with LDS-DMA (two buffers by panel parity: the
+    // lookahead's far update reads panel K's while the dataflow launch of K + 1 writes its own)
+    unsigned short* planes = nullptr;
+    int64_t plane_cs = 0;  // halves per chain and buffer
+    // explicit-inverse panels (chol32.hip k_zinv_* / k_panel_inv_gemm32): the dataflow launch
+    // walks the diagonal block and the right-hand-side row only; Z = inv(L_D) per chain (fp32
+    // scratch zt: Z, Z^T, T^T; fp16x3 planes zplanes) and one GEMM per row tile below
+    float* zt = nullptr;
+    unsigned short* zplanes = nullptr;
+    // per (chain, row tile) progress words, then [dataflow timeouts][TRSV timeouts][ticket]
+    unsigned long long* dfprog = nullptr;
+    unsigned long long df_fact = 0;        // factorisations so far (the words' monotonic base)
+    // the arrival-ticket counter of the main stream's hand-over kernels (SpinCtl): reset at the
+    // start of every theta-call, ticket_base = the tickets the call's launches have drawn so far
+    unsigned long long ticket_base = 0;
+    int spin_df = 1 << 22, spin_trsv = 1 << 20;  // poll bounds (APM_SPIN_LIMIT: tests only)
+    // chains whose work the roofline accounting credits (Newton: the unconverged ones after the
+    // previous convergence read; update_flops x live_n instead of x count)
+    int live_n = 0;
+    // chol(K) of the mixed-precision IS theta-call on a low-priority second stream, concurrent
+    // with the Newton iterations, and the fp32 bottom block of the posterior factor on the same
+    // stream; the far part of each Newton trailing update on stream3 beside the next panel's
+    // dataflow launch (one-panel lookahead, chol_range32)
+    hipStream_t stream2 = nullptr;
+    hipStream_t stream3 = nullptr;
+    // pacing of the concurrent chol(K) (feed_chol_k): panels it may still release in this Newton
+    // iteration, from the previous theta-call's iteration count (newton_last; 0: no pacing)
+    int cholk_quota = 1 << 30, newton_last = 0;
+    apm_host::Edges ev;  // one event per cross-stream edge
+    int skew = 0;  // APM_SKEW (tests only): delay kernels in front of launches (skew_point), bit 2
+                   // drops the bottom_done wait
+    // per-chain guard data (k_guard_*): [1/2 log|B| of the last Newton factor][1/2 log|K|]
+    // [residuals r1 .. r4 of the last theta-call]
+    double* guard = nullptr;
+    double* guard_rows = nullptr;  // the slot writer's row residuals of C_chol g = f_post (B x np)
+    int *active2 = nullptr, *status2 = nullptr;
+    // chol(K) is enqueued one outer panel at a time, each released when the main stream enters a
+    // single-workgroup-per-chain TRSV (3/4 of the CUs idle) - see feed_chol_k
+    int cholk_next = -1, cholk_count = 0;
+    // the Gram wrote only the first outer panel's tile columns into chol(K)'s working copy: the
+    // first trailing update then reads its old tiles from K (out of place, k_chol_update_t128 S)
+    bool cholk_partial = false;
+    // the predictive path (apm_predict), allocated at its first call: one block of test inputs
+    // (np x d), the mu* partials (max_batch x nb x np), the three outputs (max_batch x np each) and
+    // behind them the chains' s = exp(theta_0) as the host computes it (max_batch)
+    double *pxs = nullptr, *ppart = nullptr, *pmean = nullptr, *pvar = nullptr, *pprob = nullptr;
+    double* psig = nullptr;
+    // the gradient path (apm_laplace_grad), allocated at its first call: six vectors per chain
+    // (dS, g, s2, t = K s2, u = -R t, q; max_batch x np each), the super-tile partials
+    // (max_batch x ns (ns + 1) / 2 x P) and the gradients (max_batch x P)
+    double *gvec = nullptr, *gpart = nullptr, *gout = nullptr;
+};
+
+namespace apm_host __attribute__((visibility("hidden"))) {
+
+template <class T>
+T* dalloc(apm_ctx* c, size_t count) {  // (at least one element)
+    void* p = nullptr;
+    if (count == 0) count = 1;
+    hipError_t e = hipMalloc(&p, count * sizeof(T));
+    if (e != hipSuccess)
+        throw HipError{"hipMalloc(" + std::to_string(count * sizeof(T)) +
+                       " bytes): " + hipGetErrorString(e)};
+    c->allocs.push_back(p);
+    return static_cast<T*>(p);
+}
+
+// ---- host_ctx.cpp ---------------------------------------------------------------------------
+void init_ctx(apm_ctx* c, int device, int kind, const double* X, int64_t n, int64_t d,
+              int64_t ldx, const double* y, double eps, int64_t S, int64_t max_batch,
+              int64_t n_slots, int64_t n_ubufs);
+void free_ctx(apm_ctx* c);
+
+struct SkewState {  // APM_SKEW (tests only): the calling thread's skew_point setting
+    int mode = 0;
+    hipStream_t main = nullptr, s2 = nullptr, s3 = nullptr;
+};
+struct SkewScope {  // an API entry point's launches belong to context c
+    SkewState prev;
+    explicit SkewScope(const apm_ctx* c);
+    ~SkewScope();
+};
+
+hipEvent_t next_event(apm_ctx* c);  // from the context's pool (apm_prof_read's reset returns them)
+struct ProfScope {  // times what is enqueued on s (default: the main stream) during its lifetime
+    apm_ctx* c;
+    int kind;
+    double work;
+    hipStream_t s;
+    hipEvent_t a{}, b{};
+    bool on = false;
+    ProfScope(apm_ctx* c_, int k, double w, hipStream_t s_ = nullptr)
+        : c(c_), kind(k), work(w), s(s_ ? s_ : c_->stream) {
+        // the all-updates kinds time every in-panel launch: detailed level (2) only
+        const bool all_upd = kind == APM_PROF_CHOL_UPDATE || kind == APM_PROF_CHOL_UPDATE32;
+        if (kind >= 0 && c->prof >= (all_upd ? 2 : 1)) {
+            on = true;
+            a = next_event(c);
+            b = next_event(c);
+            HIPC(hipEventRecord(a, s));
+        }
+    }
+    ~ProfScope() {
+        if (on && hipEventRecord(b, s) == hipSuccess)
+            c->recs.push_back(ProfRec{a, b, kind, work});
+    }
+};
+
+inline void sync(apm_ctx* c) { HIPC(hipStreamSynchronize(c->stream)); }
+
+// Read back up to four small per-chain device arrays (after the work enqueued so far on the
+// main stream) and wait: one k_export launch into the mapped host buffer, a stream
+// synchronisation, host copies.
+struct RB {
+    const void* src;
+    int bytes;
+    void* host;
+};
+void read_back(apm_ctx* c, std::initializer_list<RB> l);
+
+// the fields of hpin (StagePin)
+inline StagePin pin_of(const apm_ctx* c) { return StagePin{c->max_batch}; }
+inline int64_t* pin_slots(apm_ctx* c) {
+    return reinterpret_cast<int64_t*>(c->hpin + pin_of(c).slots());
+}
+inline int64_t* pin_ubufs(apm_ctx* c) {
+    return reinterpret_cast<int64_t*>(c->hpin + pin_of(c).ubufs());
+}
+inline int* pin_h3(apm_ctx* c) { return reinterpret_cast<int*>(c->hpin + pin_of(c).h3ok()); }
+inline int* pin_h3post(apm_ctx* c) { return reinterpret_cast<int*>(c->hpin + pin_of(c).h3post()); }
+inline int* pin_inv(apm_ctx* c) { return reinterpret_cast<int*>(c->hpin + pin_of(c).invok()); }
+inline double* pin_icm(apm_ctx* c) { return reinterpret_cast<double*>(c->hpin + pin_of(c).icm()); }
+inline int64_t* blk_field(apm_ctx* c, StageBlk f) { return c->hblk + (int64_t)f * c->max_batch; }
+
+void upload_idx(apm_ctx* c, int count, const int64_t* slots, const int64_t* ubufs);
+void upload_h3(apm_ctx* c, int count);
+// the thetas of a call (count x P, row stride ldt) -> pinned staging -> device; returns the
+// staged copy
+const double* upload_thetas(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt);
+// the identity-padded copy of a host K (n x n, row stride ldk) -> chain 0's K, both triangles
+// (k_full), staged in Kp, which the caller keeps until its next sync; returns max |K_ii|
+double upload_padded_K(apm_ctx* c, const double* K, int64_t ldk, std::vector<double>& Kp);
+void attach_l64(apm_ctx* c, int64_t slot);
+void detach_l64(apm_ctx* c, int64_t slot);
+void upload_l64(apm_ctx* c);
+
+inline Live live_of(apm_ctx* c) { return Live{c->active, c->status}; }
+
+// ---- host_chol64.cpp ------------------------------------------------------------------------
+// Where a factorisation runs: stream, liveness, diagonal-inverse / log-det arrays. The main path
+// uses the context stream; chol(K) of the IS theta-call runs concurrently on the low-priority
+// second stream with its own liveness and the upper halves of Dinv / ldet (theta_eval_impl).
+struct Exec {
+    hipStream_t s;
+    Live lv;
+    double* Dinv;
+    double* ldet;
+    int live_n;  // chains credited by the roofline accounting
+};
+inline Exec main_exec(apm_ctx* c) {
+    return Exec{c->stream, live_of(c), c->Dinv, c->ldet, c->live_n};
+}
+
+// Row tiles [lo, hi) known to be zero in panel column k (skipped by panel and update).
+struct Gap {
+    int lo, hi;
+};
+typedef Gap (*GapFn)(int k, int nb);
+inline Gap no_gap(int, int) { return Gap{0, 0}; }
+// [[J M J],[L_K J]] factorisation (postcov.hip): row tile nb+I of L_K J is zero in every column
+// tile k < nb-1-I, so at column k only bottom rows >= 2nb-1-k are nonzero.
+inline Gap y_gap(int k, int nb) { return Gap{nb, std::max(nb, 2 * nb - 1 - k)}; }
+
+double update_flops(int i0, int R, int j0, int jend, int kc, Gap g, bool syrk_lower = false);
+DevList tile_list(apm_ctx* c, int i0, int R, int j0, int jend, Gap g);
+DevList super_list(apm_ctx* c, int i0, int R, int j0, int jend, Gap g, int solo = -1);
+DevList super_list_ext(apm_ctx* c, int i0, int R, int j0, int jend, int rhs, int jext);
+DevList quad_list(apm_ctx* c, int i0, int R, int j0, int jend);
+void tracked_update(apm_ctx* c, MatB M, int k0, int kc, int i0, int R, int j0, int jend, Gap g,
+                    int plus, int count, int fuse_k = -1, int fail_code = 0,
+                    const Exec* ex = nullptr, const MatB* src = nullptr);
+
+// what the two forms of the fp64 schedule rarely need; a call site names what it sets
+struct SolveOpts {
+    const Exec* ex = nullptr;  // where it runs (default: main_exec)
+    GapFn gap = no_gap;        // row tiles known to be zero per panel column
+};
+struct FactorOpts : SolveOpts {
+    // the first outer update reads its old tiles from here (out of place) instead of from M
+    const MatB* first_src = nullptr;
+    // after_panel(K, Kend): called (host side) once the panel's columns are final, before its
+    // outer update is enqueued (the posterior factor's fp32 bottom block follows the panels)
+    std::function<void(int, int)> after_panel;
+};
+void chol_factor(apm_ctx* c, MatB M, int k0, int k1, int R, int Cb, int fail_code, int count,
+                 const FactorOpts& o = FactorOpts());
+void chol_solve_rows(apm_ctx* c, MatB M, int k1, int row_start, int R, int Cb, int count,
+                     const SolveOpts& o = SolveOpts());
+
+// ---- host_newton.cpp ------------------------------------------------------------------------
+unsigned long long* spin_words(apm_ctx* c);  // [dataflow timeouts][TRSV timeouts][ticket]
+void reset_tickets(apm_ctx* c);
+void newton(apm_ctx* c, int count, std::vector<int>& st_h, bool mixed, int live0);
+void newton_is(apm_ctx* c, int count, std::vector<int>& st_h);
+
+// ---- host_theta.cpp -------------------------------------------------------------------------
+void feed_chol_k(apm_ctx* c);
+void drain_chol_k(apm_ctx* c);
+void u_eval_device(apm_ctx* c, int count, bool wide);
+void theta_eval_impl(apm_ctx* c, int est, int count, bool gram, double* out_logf, int* status,
+                     int64_t* nops);
+
+// ---- host_laplace.cpp -----------------------------------------------------------------------
+void augmented(apm_ctx* c, int count);
+// a Laplace theta-call (Gram, fp64 Newton, LML into lml: count doubles) whose OK chains are then
+// made live again (they left the Newton loop with active = 0) for the passes that reuse the last
+// Newton factor; returns their number
+int laplace_then_live(apm_ctx* c, int count, double* lml, int* status, int64_t* n_iter);
+void predict_buffers(apm_ctx* c);
+void predict_block(apm_ctx* c, int count, const double* xs, int ms);
+void grad_buffers(apm_ctx* c);
+void grad_block(apm_ctx* c, int count);
+
+}  // namespace apm_host

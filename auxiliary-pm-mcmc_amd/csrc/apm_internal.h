@@ -1,6 +1,9 @@
-// Internal launcher interface between the kernel translation units and capi.cpp.
+// Internal launcher interface between the kernel translation units and the host orchestration
+// (host_*.cpp, capi.cpp; their shared declarations are in apm_host.h).
 // Nothing here is part of the public C-ABI (include/apm.h).
 #pragma once
+#include <string>
+
 #include "apm_common.h"
 
 // A batched fp64 matrix: chain b's element (r, c) lives at base[b*cstride + r*ld + c].
@@ -75,8 +78,6 @@ void launch_philox_test(const uint32_t* in, uint32_t* out, int64_t n, hipStream_
 // ---- chol32.hip: mixed-precision Newton solve (fp32 factor of B + fp64 refinement) -----------
 void launch_chol_diag32(MatF A, int k, float* Dinv, int64_t dstride, double* ldet,
                         int64_t lstride, Live live, int fail_code, int nchains, hipStream_t s);
-void launch_chol_panel32(MatF A, int k, int i0, int R, int glo, int ghi, const float* Dinv,
-                         int64_t dstride, Live live, int nchains, hipStream_t s);
 // Bounded in-launch hand-overs of the Newton solve (k_chol_panel_df32, k_trsv32_mw). HIP promises
 // no dispatch order, so a workgroup's logical index is the ticket it draws from a monotonic
 // arrival counter when it starts (a ticket exists only for a workgroup that is running): a
@@ -355,7 +356,7 @@ struct SlotSet {
     double post_q;      // trace(C) above which an fp32 bottom block is recomputed in fp64
                         // (APM_POST32_Q; postcov.hip)
     const double* icm_thr;  // per chain: trace(C) below which bit 3 of chain_wide asks the host
-                            // for the reference-route check of chol(C) (capi.cpp icm_check)
+                            // for the reference-route check of chol(C) (host_theta.cpp icm_check)
 };
 // trace(L L^T) above which a slot's u-path runs in fp64: the fp32 L.U moves
 // log f by ~1e-10 x trace (11 nats at trace 1.15e11, sigma = e^18.5; < 1e-6 nats at the trace
@@ -454,18 +455,27 @@ void launch_guard_check(const double* ldet, int64_t lstride, int nb, const doubl
                         const double* fvec, int fail_code, Live live, int nchains,
                         hipStream_t s);
 
-// ---- stream skew (tests only; capi.cpp skew_point, APM_SKEW) ------------------------------
+// ---- launching (stream skew: tests only; host_ctx.cpp skew_point, APM_SKEW) ----------------
 // Every launch goes through APM_LAUNCH, which first lets skew_point enqueue a delay kernel on the
-// launch's stream when the calling thread's context asked for it: a cross-stream edge without
-// its wait then reads stale data deterministically instead of by chance.
+// launch's stream when the calling thread's context asked for it (a cross-stream edge without
+// its wait then reads stale data deterministically instead of by chance), and which throws a
+// HipError when the launch is refused: the C-ABI entry point that enqueued it returns APM_E_HIP.
+struct __attribute__((visibility("hidden"))) HipError {
+    std::string msg;
+};
+static inline void throw_if_launch_failed() {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) throw HipError{std::string("kernel launch: ") + hipGetErrorString(e)};
+}
 #ifdef APM_TOOL_NO_SKEW  // stand-alone development benches that include a .hip file directly
 inline void skew_point(hipStream_t) {}
 #else
 void skew_point(hipStream_t s);
 #endif
-void launch_delay(int us, hipStream_t s);
+void launch_delay(int us, hipStream_t s);  // (skew_point's own kernel: launched without it)
 #define APM_LAUNCH(kern, grid, block, lds, st, ...)                      \
     do {                                                                 \
         skew_point(st);                                                  \
         hipLaunchKernelGGL(kern, grid, block, lds, st, __VA_ARGS__);     \
+        throw_if_launch_failed();                                        \
     } while (0)

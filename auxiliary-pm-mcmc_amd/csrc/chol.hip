@@ -450,7 +450,7 @@ __device__ __forceinline__ void update_t128_body(MatB A, int k0, int kc, unsigne
     // the loop so that no wait for it lands inside (see k_chol_update32_t128)
     const int li = mine ? oi : (wr ? ra1 : ra0), lj = mine ? oj : (wc ? cb1 : cb0);
     // (S.base: out of place - the old tile comes from S, e.g. K for the first trailing update of
-    // chol(K), whose working copy holds the first outer panel only: capi.cpp chol_k_begin)
+    // chol(K), whose working copy holds the first outer panel only: host_theta.cpp chol_k_begin)
     const int64_t cld = S.base ? S.ld : A.ld;
     const double* Cw = (S.base ? S.base + b * S.cstride : Ab) + (int64_t)(li * 64) * cld + lj * 64;
 #pragma unroll
@@ -655,16 +655,19 @@ void launch_marker(int id, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------- chol(K) retry
-// DESIGN.md §3.4 (capi.cpp retry_chol_k): a chain whose blocked factorisation of K failed
-// (fail[b] == code) has K's lower triangle factored again, unblocked, in LAPACK's dpotf2 order -
-// left-looking column by column, L_jj = sqrt(K_jj - L_j,:j . L_j,:j), then
-// L_ij = (K_ij - L_i,:j . L_j,:j) / L_jj - each dot product with four interleaved fma
-// accumulators summed pairwise, as OpenBLAS's unrolled ddot does inside the dpotf2 that decides
-// the reference's LinAlgError (estimators.py:206). At the reference's two
-// InvalidCovarianceMatrixError thetas (tests/golden/icm_k.npz) this order passes on the
-// reference's own K where the blocked factorisation, whose panels multiply by inverted diagonal
-// tiles, rounds K to indefinite; the chain then reaches the reference-route check of chol(C) as
-// in the reference. One workgroup per chain (row j of L staged in LDS); success clears fail[b]
+// DESIGN.md §3.4 (host_theta.cpp theta_eval_impl): a chain whose blocked factorisation of K
+// failed (fail[b] == code) has K's lower triangle factored again, unblocked and left-looking
+// column by column, L_jj = sqrt(K_jj - L_j,:j . L_j,:j), then
+// L_ij = (K_ij - L_i,:j . L_j,:j) / L_jj, each dot product with four interleaved fma
+// accumulators summed pairwise. This is a different rounding order from the blocked one, not
+// the reference's: OpenBLAS's potf2 accumulates column by column with GEMV and multiplies by
+// 1 / L_jj, and its dpotrf factors larger matrices blocked. That it agrees with the reference's
+// LinAlgError decision (estimators.py:206) is pinned only at the reference's two
+// InvalidCovarianceMatrixError thetas (icm_a / icm_b, tests/golden/icm_k.npz): there this order
+// passes on the reference's own K where the blocked factorisation, whose panels multiply by
+// inverted diagonal tiles, rounds K to indefinite, and the chain then reaches the reference-route
+// check of chol(C) as in the reference. One workgroup per chain (row j of L staged in LDS);
+// success clears fail[b]
 // and writes L (zeros above the diagonal inside diagonal tiles) and the per-tile log-diagonal
 // sums. No inverses of diagonal tiles are written: the IS theta-call's consumers of L_K (the
 // tile-parallel L_K^T a and the posterior factor's Y2 / L_K J pass) do not read them.

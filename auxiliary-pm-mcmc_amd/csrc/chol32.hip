@@ -197,37 +197,6 @@ __device__ __forceinline__ void tile_gemm_nt32(f4_t (&acc)[2][2], const float* _
 }
 
 // ------------------------------------------------------------------------------- panel, update
-__global__ __launch_bounds__(256) void k_chol_panel32(MatF A, int k, int i0, int glo, int ghi,
-                                                      const float* Dinv, int64_t dstride,
-                                                      Live live) {
-    const int b = blockIdx.y;
-    if (!live32(live, b)) return;
-    int i = i0 + blockIdx.x;
-    if (i >= glo) i += ghi - glo;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wr = w >> 1, wc = w & 1;
-    float* At = A.base + b * A.cstride + (int64_t)(i * 64) * A.ld + k * 64;
-    const float* D = Dinv + b * dstride + (int64_t)k * 4096;
-    __shared__ GemmSmem32 sm;
-    f4_t acc[2][2];
-#pragma unroll
-    for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-        for (int bj = 0; bj < 2; ++bj) acc[bi][bj] = f4_t{0.f, 0.f, 0.f, 0.f};
-    tile_gemm_nt32<false>(acc, At, A.ld, D, 64, 64, sm, nullptr, 0);  // A_ik * inv(L_kk)^T
-    tile32_store(acc, At, A.ld, wr, wc, lane);
-}
-
-void launch_chol_panel32(MatF A, int k, int i0, int R, int glo, int ghi, const float* Dinv,
-                         int64_t dstride, Live live, int nchains, hipStream_t s) {
-    glo = std::max(glo, i0);
-    ghi = std::min(ghi, R);
-    if (ghi <= glo) glo = ghi = R;
-    const int rows = (R - i0) - (ghi - glo);
-    if (rows <= 0) return;
-    APM_LAUNCH(k_chol_panel32, dim3(rows, nchains), dim3(256), 0, s, A, k, i0, glo, ghi,
-                       Dinv, dstride, live);
-}
-
 // Same XCD-aware work mapping as k_chol_update (chol.hip).
 __device__ __forceinline__ long xcd_remap32(long L, long total) {
     const long xcd = L & 7, q = total >> 3, r = total & 7;
@@ -318,7 +287,8 @@ void launch_chol_update32(MatF A, int k0, int kc, const unsigned* tiles, int nti
 // already factored): workgroup (row tile i, chain b) walks its row through the panel's columns,
 // for column k the left-looking update A_ik -= L_i[K:k] L_k[K:k]^T (the in-panel k_chol_update32
 // step, same operands, same code) and then either the diagonal factorisation (i == k; diag.h) or
-// the panel TRSM A_ik <- A_ik inv(L_kk)^T (k_chol_panel32's product, same accumulation order).
+// the panel TRSM A_ik <- A_ik inv(L_kk)^T (tile_gemm_nt32 over the whole tile, the accumulation
+// order of the per-column panel launch it replaced).
 // Results are bitwise those of the launch sequence it replaces (2 launches per column), whose
 // dependent-launch boundaries and the diagonal tile's latency at the tail of every update launch
 // were ~110 us per column.
@@ -590,7 +560,7 @@ __global__ __launch_bounds__(256, BULK ? DF_BULK_WPE : DF_WPE) void k_chol_panel
             DF_STAMP(7);
             return;
         }
-        // panel TRSM: A_ik inv(L_kk)^T, the updated tile and inv(L_kk) staged as k_chol_panel32's
+        // panel TRSM: A_ik inv(L_kk)^T, the updated tile and inv(L_kk) staged as tile_gemm_nt32's
         // two 32-deep slices (A operand: acc; B operand: inv(L_kk) row-major)
 #pragma unroll
         for (int bi = 0; bi < 2; ++bi)
@@ -744,7 +714,7 @@ __device__ __forceinline__ void rhs_row_update32(float* Ab, int64_t ld, int ti, 
                                                  bool cv1, int k0, int kc, int tid) {
     const int lane = tid & 63, w = tid >> 6;
     if (!(w < 2 ? cv0 : cv1)) return;
-    const int K = 64 * kc;  // <= 64 * 14 (OUTER32 is clamped to 14 tiles: capi.cpp init_ctx)
+    const int K = 64 * kc;  // <= 64 * 14 (OUTER32 is clamped to 14 tiles: apm_host.h apm_ctx::outer32)
     constexpr int QM = 4;
     float* crow = Ab + (int64_t)(ti * 64) * ld;
     const float* arow = crow + k0 * 64;
@@ -2152,7 +2122,7 @@ __global__ __launch_bounds__(256) void k_refine(int mode, const double* __restri
 // is accepted when max|d_k|^2 <= tol^2 max|x| max|d_{k-1}| — for the first step exactly
 // max|d| <= tol max|x| (refined error ~ tol^2 relative). Accepted chains leave the refining mask;
 // after the last allowed step the others get status = fail_code, which sends them to the fp64
-// rerun (capi.cpp newton_is): the fp32 factor is too inaccurate for them (extreme theta).
+// rerun (host_newton.cpp newton_is): the fp32 factor is too inaccurate for them (extreme theta).
 // prev[b] keeps max|d_{k-1}|.
 __global__ __launch_bounds__(256) void k_refine_check(const double* __restrict__ x,
                                                       const double* __restrict__ d,

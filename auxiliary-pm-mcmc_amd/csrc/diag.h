@@ -170,7 +170,7 @@ __device__ __forceinline__ void ld16(typename V4<R>::t& acc, const R* src, int l
 // 16x16x16 f64-MFMA products on LDS operands. The inverse is kept transposed in the unused upper
 // triangle of T (X_ab, a > b, in block (b, a); the strictly lower part of X_aa in the upper part of
 // diagonal block (a, a); its diagonal in xdg): 36 KB of LDS, so that the kernel fits next to three
-// padded update workgroups on a CU (lookahead, capi.cpp).
+// padded update workgroups on a CU (lookahead, host_newton.cpp chol_range32).
 // Tile storage is fp64 (MatB) or fp32 (MatF, the mixed-precision Newton factorisation).
 __device__ __forceinline__ d2_t ld2(const double* p) { return *reinterpret_cast<const d2_t*>(p); }
 __device__ __forceinline__ d2_t ld2(const float* p) {

@@ -1,6 +1,6 @@
 // Gradient of the Laplace log marginal likelihood with respect to theta: the
-// kernels around the two Schur-complement passes that capi.cpp's grad_block borrows from the
-// Cholesky (chol_range on the bottom rows of the work matrix against the last Newton factor).
+// kernels around the two Schur-complement passes that host_laplace.cpp's grad_block borrows from the
+// Cholesky (chol_solve_rows on the bottom rows of the work matrix against the last Newton factor).
 //
 //   v = phi(f)/Phi(y f),  g = y v,  d3 = -[(2v + y f)(-f v - y v^2) + y v]      (f = K a, the mode)
 //   dS_i = K_ii - |L^-1 (W^1/2 . K[:, i])|^2,  s2 = 1/2 dS . d3

@@ -29,7 +29,7 @@
 // 64 (subtract, fma) pairs, so the LDS reads stay at half the VALU issue (a 4x4 block per lane
 // tied them). Features are pre-scaled by 1/tau_k while staged; the sum runs over k in order
 // (the same arithmetic as the reference's loop, kernels.pyx:80-88, up to the pre-scaling).
-// K2 (the concurrent chol(K)'s working copy, capi.cpp chol_k_begin) receives the tiles of tile
+// K2 (the concurrent chol(K)'s working copy, host_theta.cpp chol_k_begin) receives the tiles of tile
 // columns < k2cols only: the first outer panel's trailing update reads the rest from K itself.
 // FAM (APM_FAM_*) selects the epilogue that turns a pair's r^2 into its covariance (cov_S); the
 // distance loop, the LDS staging, the tiling and the stores are the same for every family.

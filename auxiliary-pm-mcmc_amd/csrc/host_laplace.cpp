@@ -1,0 +1,105 @@
+// What follows a Laplace fit on its last fp64 Newton factor: apm_laplace's covariance, the
+// predictive distribution at test inputs and the gradient of the log marginal likelihood, each
+// a pass of chol_solve_rows over free rows of the work matrix.
+#include "apm_host.h"
+
+namespace apm_host {
+
+// apm_laplace's covariance C = K - V^T V (lpa.py:111-112) in the bottom-right of A: the
+// augmented matrix [[B,.],[K W^1/2, K]] with the last fp64 Newton factor in its top-left
+void augmented(apm_ctx* c, int count) {
+    const Live lv = live_of(c);
+    HIPC(hipMemsetD32Async(c->active, 1, count, c->stream));
+    launch_form_aug(c->K, c->A, c->v, c->np, lv, count, c->stream);
+    const int nb = c->nb;
+    chol_solve_rows(c, c->A, nb, /*row_start=*/nb, /*R=*/2 * nb + 1, /*Cb=*/2 * nb, count);
+}
+
+int laplace_then_live(apm_ctx* c, int count, double* lml, int* status, int64_t* n_iter) {
+    // L, inv(L_kk), W^1/2, a and the mode of each chain's last iteration stay in A / Dinv / the
+    // Newton vectors
+    theta_eval_impl(c, APM_EST_LAPLACE, count, true, lml, status, n_iter);
+    int ok = 0;
+    for (int b = 0; b < count; ++b) ok += status[b] == APM_STATUS_OK;
+    if (ok) {
+        // converged chains left the Newton loop with active = 0 (as augmented())
+        HIPC(hipMemsetD32Async(c->active, 1, count, c->stream));
+        c->live_n = ok;
+    }
+    return ok;
+}
+
+// Laplace predictive (predict.hip) of one block of ms <= np test inputs (packed
+// ms x d at xs) for the chains left live by an fp64 Laplace theta-call: W^1/2 . k* into the free
+// rows [np, np + 64 mb) of A and mu*'s partials, the panel solves and outer updates of those
+// rows against the last Newton factor (as augmented(), without the bottom-right SYRK), the row
+// reduction; outputs in pmean / pvar / pprob (row stride np). predict_buffers() first.
+void predict_buffers(apm_ctx* c) {
+    if (c->pxs) return;
+    const int64_t np = c->np, B = c->max_batch;
+    c->pxs = dalloc<double>(c, np * std::max(c->d, 1));
+    c->ppart = dalloc<double>(c, B * c->nb * np);
+    c->pmean = dalloc<double>(c, 3 * B * np + B);
+    c->pvar = c->pmean + B * np;
+    c->pprob = c->pvar + B * np;
+    c->psig = c->pprob + B * np;
+}
+
+void predict_block(apm_ctx* c, int count, const double* xs, int ms) {
+    const Live lv = live_of(c);
+    const int nb = c->nb, mb = (ms + 63) / 64;
+    const int64_t np = c->np;
+    HIPC(hipMemcpyAsync(c->pxs, xs, sizeof(double) * ms * c->d, hipMemcpyHostToDevice, c->stream));
+    launch_gram_cross(c->A, np, c->pxs, ms, mb, c->X, c->d, c->n, c->d, nb, c->theta, c->P,
+                      c->psig, c->kind, c->v.Ws, c->v.a, c->v.vstride, c->ppart, nb * np, lv, 0,
+                      count, c->stream);
+    chol_solve_rows(c, c->A, nb, /*row_start=*/nb, /*R=*/nb + mb, /*Cb=*/nb, count);
+    launch_predict_reduce(c->A, np, ms, mb, nb, c->psig, c->ppart, nb * np, c->pmean,
+                          c->pvar, c->pprob, np, lv, count, c->stream);
+}
+
+// Gradient of the Laplace LML w.r.t. theta (gradient.hip) for the chains left live
+// by an fp64 Laplace theta-call, in two passes over the bottom rows [np, 2np) of A against the
+// last Newton factor (chol_solve_rows, as augmented() and predict_block use it):
+//   1. K W^1/2 in the bottom-left (k_form_aug), panel solves -> V^T; its row norms give dS, then
+//      g, s2 and t = K s2;
+//   2. diag(W^1/2) in the bottom-left and zeros in the bottom-right's lower tiles, panel solves
+//      and trailing updates -> Z^T and -Z^T Z = -R; q = s2 + (-R) t;
+// then the fused contraction of M against dK/dtheta_j (k_grad_reduce) and the sum of its
+// super-tile partials into gout (count x P). grad_buffers() first.
+void grad_buffers(apm_ctx* c) {
+    if (c->gvec) return;
+    const int64_t np = c->np, B = c->max_batch, ns = (c->nb + 1) / 2;
+    c->gvec = dalloc<double>(c, 6 * B * np);
+    c->gpart = dalloc<double>(c, B * (ns * (ns + 1) / 2) * c->P);
+    c->gout = dalloc<double>(c, B * c->P);
+}
+
+void grad_block(apm_ctx* c, int count) {
+    const Live lv = live_of(c);
+    const int nb = c->nb, ns = (nb + 1) / 2, nst = ns * (ns + 1) / 2;
+    const int64_t np = c->np, B = c->max_batch;
+    double *dS = c->gvec, *g = dS + B * np, *s2 = g + B * np, *t = s2 + B * np, *u = t + B * np,
+           *q = u + B * np;
+    launch_form_aug(c->K, c->A, c->v, c->np, lv, count, c->stream, /*lower_only=*/!c->k_full);
+    chol_solve_rows(c, c->A, nb, /*row_start=*/nb, /*R=*/2 * nb, /*Cb=*/nb, count);
+    launch_grad_rows(c->A, c->K, c->n, nb, c->v.f, c->y, c->v.vstride, dS, g, s2, np, lv, count,
+                     c->stream);
+    launch_symv(c->K, s2, np, t, np, c->sympart, c->sstride, c->np, MatF{}, nullptr, 0, lv, count,
+                c->stream, c->symv_tpw);
+    launch_grad_fill(c->A, c->v.Ws, c->v.vstride, nb, lv, count, c->stream);
+    chol_solve_rows(c, c->A, nb, /*row_start=*/nb, /*R=*/2 * nb, /*Cb=*/2 * nb, count);
+    const MatB Rn{c->A.base + np * c->A.ld + np, c->A.ld, c->A.cstride};  // -R, lower tiles
+    launch_symv(Rn, t, np, u, np, c->sympart, c->sstride, c->np, MatF{}, nullptr, 0, lv, count,
+                c->stream, c->symv_tpw);
+    launch_grad_q(s2, u, q, np, c->n, c->np, lv, count, c->stream);
+    {   // bytes: the lower triangles of R and K (the inputs and vectors are small beside them)
+        ProfScope ps(c, APM_PROF_GRAD_REDUCE, 8.0 * (double)c->n * (c->n + 1) * c->live_n);
+        launch_grad_reduce(c->K, Rn, c->X, c->d, c->n, c->d, nb, c->theta, c->P, c->kind, c->v.a,
+                           c->v.vstride, q, g, np, c->gpart, (int64_t)nst * c->P, c->P, lv, count,
+                           c->stream);
+    }
+    launch_grad_sum(c->gpart, (int64_t)nst * c->P, nst, c->P, c->gout, lv, count, c->stream);
+}
+
+}  // namespace apm_host

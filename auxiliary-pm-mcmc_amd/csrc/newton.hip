@@ -537,4 +537,5 @@ __global__ __launch_bounds__(64) void k_delay(long long ticks) {
 
 void launch_delay(int us, hipStream_t s) {
     hipLaunchKernelGGL(k_delay, dim3(1), dim3(64), 0, s, (long long)us * 100);
+    throw_if_launch_failed();
 }

@@ -1,5 +1,5 @@
 // Laplace predictive distribution at test inputs: the two kernels around the
-// panel solves that capi.cpp's predict_block borrows from the Cholesky (chol_range on the test
+// panel solves that host_laplace.cpp's predict_block borrows from the Cholesky (chol_solve_rows on the test
 // rows only).
 //
 //   k*_c = s exp(-1/2 sum_k ((x*_k - x_ck)/tau_k)^2)   no epsilon: kernels.pyx adds it to the

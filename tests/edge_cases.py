@@ -1,5 +1,5 @@
 """Inputs of tests/test_gpu_laplace_edges.py: sizes at the panel boundaries of the solve-only form
-of chol_range (capi.cpp), the data seeds, and the condition those seeds were chosen by. A plain
+of the fp64 schedule (host_chol64.cpp chol_solve_rows), the data seeds, and the condition those seeds were chosen by. A plain
 module, shared with test_grad_host.py, which asserts the condition without a device.
 
 nb = ceil(N / 64) tile rows, outer panels of 8 tiles: N = 65 and 128 (nb = 2: the first depth-2

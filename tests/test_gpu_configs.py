@@ -196,7 +196,7 @@ def test_config2_stationary_states_match_fp64_newton(nat, monkeypatch):
 
 
 def test_config2_reference_route_check_passes_everywhere(nat, monkeypatch):
-    """The reference-route check of chol(C) (capi.cpp icm_check) forced on
+    """The reference-route check of chol(C) (host_theta.cpp icm_check) forced on
     every chain (APM_ICM_Q=1: trace(C) < n K_ii holds for every chain, C being below K) at
     configs[2]'s four thetas, sigma = e^18.5 included: C = K - V^T V of the last Newton
     iteration factors on every chain (status 0, as in the reference, which returned values

@@ -10,7 +10,7 @@
 * InvalidCovarianceMatrixError (estimators.py:208-215): the reference raises it where its
   explicitly formed C = K - V^T V is numerically indefinite. The estimate's route factors
   M = I + L_K^T W L_K (SPD for any W >= 0); chains whose C is small
-  against K also form C the reference's way (capi.cpp icm_check) and fail as the reference does,
+  against K also form C the reference's way (host_theta.cpp icm_check) and fail as the reference does,
   after chol(K) has been retried in LAPACK's order where the blocked factorisation rounds K to
   indefinite (DESIGN.md §3.4);
 * cross-stream edges (APM_SKEW) and the device-side guard (APM_STATUS_GUARD).
@@ -119,7 +119,7 @@ def test_invalid_covariance_raises_where_the_reference_raises(nat, name):
     factored again in LAPACK's dpotf2 order (chol.hip k_chol_unblocked: the order of the
     reference's own LinAlgError check, estimators.py:206), which passes as the reference's does;
     then, C being small against K, the library forms C the reference's way (C = K - V^T V from
-    the last Newton iteration's fp64 B factor, capi.cpp icm_check), whose Cholesky fails as the
+    the last Newton iteration's fp64 B factor, host_theta.cpp icm_check), whose Cholesky fails as the
     reference's does (a property of the route: it fails under 1-ulp perturbations of B as well,
     profiles/r05_icm_route_study.txt), and the chain reports APM_STATUS_CHOL_C."""
     e = golden('errors')
@@ -261,7 +261,7 @@ def _stationary_calls(nat, monkeypatch, shifts=(0, 7), B=64, **env):
 
 
 def test_stream_skew_is_bitwise_neutral(nat, monkeypatch):
-    """Every cross-stream edge of a theta-call is an event of its own (capi.cpp Edges: Gram ->
+    """Every cross-stream edge of a theta-call is an event of its own (apm_host.h Edges: Gram ->
     chol(K), chol(K) -> posterior, L_K J -> fp32 bottom block, each panel of L' -> its bottom
     panel, bottom -> slot writer, each Newton panel -> its far update and back). APM_SKEW puts a
     delay kernel in front of every launch on the secondary streams (1: 1 ms each), on the main
@@ -356,7 +356,7 @@ def test_guard_residuals_are_rounding_sized(nat, monkeypatch):
 
 def test_chol_k_pacing_is_bitwise_neutral(nat):
     """The concurrent chol(K) releases its panels over the Newton iterations the context's
-    previous theta-call took (capi.cpp newton: cholk_quota), so its schedule depends on what the
+    previous theta-call took (host_newton.cpp newton: cholk_quota), so its schedule depends on what the
     context did before. A sequence of stationary states (7-8 iterations) -> theta* (fewer: panels
     left for the drain before the posterior) -> stationary again (paced from the short call) must
     give, call by call, the bitwise values of a fresh context (no previous call: no pacing)."""

@@ -156,7 +156,7 @@ def test_wide_slot_fp64_path_vs_golden(nat, monkeypatch):
 
 
 def test_wide_buffers_follow_slots(nat, monkeypatch):
-    """fp64 factors are attached to slots only while they are wide (capi.cpp attach_l64 /
+    """fp64 factors are attached to slots only while they are wide (host_ctx.cpp attach_l64 /
     detach_l64): a slot that turns narrow gives its buffer back, the next wide slot takes it, and
     every cached u-call afterwards equals a fresh context's - in a batch of wide and narrow
     chains, across the IS (fp32 bottom + fp64 rerun) and PriorMC writers."""

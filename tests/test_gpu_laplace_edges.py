@@ -1,5 +1,5 @@
-"""Predictive, gradient and apm_laplace's covariance at the panel boundaries of chol_range's
-solve-only form (capi.cpp: factor_diag = false, row_start = nb), which predict_block, grad_block
+"""Predictive, gradient and apm_laplace's covariance at the panel boundaries of the fp64 schedule's
+solve-only form (host_chol64.cpp chol_solve_rows, row_start = nb), which predict_block, grad_block
 and augmented() run the work matrix through: N = 65, 128, 512, 513, 1024, 1025, 1089 (nb = 2, 2,
 8, 9, 16, 17, 18; tests/edge_cases.py says what each size reaches), test-row counts mb = 1, 2, 3,
 nb and a second block of one row, against the numpy/scipy restatements (grad_restatement,

@@ -5,7 +5,7 @@ The full-size tests compare estimates; an estimate is a log-mean over samples of
 so one wrong tile of the factor, a wrong cst or one dropped sample column moves it by less than
 its 5e-4 nats tolerance. Here every lower entry of the slot's factor, its g row and cst are
 compared with the oracle at the block counts nb = ceil(N / 64) where the code takes another path
-(capi.cpp: one 8-block outer panel, the first trailing block, the first partial-Gram copy, the
+(host_chol64.cpp, host_newton.cpp, host_theta.cpp: one 8-block outer panel, the first trailing block, the first partial-Gram copy, the
 first far update, the explicit-inverse panel, odd super-tile counts), and the sample loop of
 k_ugemm / k_ugemm64 / k_lme is pinned with probe columns at its block edges (ugemm.hip).
 
