@@ -82,7 +82,10 @@ class _BatchedChains(object):
     auxiliary draw) and ``ub_prop`` (proposed u)."""
 
     def __init__(self, X, y, n_chains, n_imp, prior, kernel='ard', epsilon=1e-8,
-                 max_slice_iters=1000, seed=0, estimator='is', device=None, first_chain=0):
+                 max_slice_iters=1000, seed=0, estimator='is', device=None, first_chain=0,
+                 likelihood='probit'):
+        _native.likelihood_code(likelihood)  # ('probit' | 'logit'; ValueError otherwise)
+        self.likelihood = likelihood
         self.n_chains = int(n_chains)
         self.n_imp = int(n_imp)
         self.prior = dict(prior)
@@ -92,7 +95,7 @@ class _BatchedChains(object):
         kind = _KERNEL_KINDS.get(kernel, _native.KERNEL_ISO)
         C = self.n_chains
         self.ctx = _native.Context(X, y, kind, epsilon, n_imp, max_batch=C, n_slots=2 * C,
-                                   n_ubufs=3 * C, device=device)
+                                   n_ubufs=3 * C, device=device, likelihood=likelihood)
         self.P = self.ctx.theta_len
         self.slot_cur = np.arange(C, dtype=np.int64)
         self.slot_prop = np.arange(C, 2 * C, dtype=np.int64)
@@ -373,10 +376,10 @@ class BatchedAPMEllSSPlusRandDirSliceSampler(_BatchedChains):
 
     def __init__(self, X, y, n_chains, n_imp, prior, kernel='ard', epsilon=1e-8, w=1.,
                  max_steps_out=0, max_slice_iters=1000, seed=0, estimator='is', device=None,
-                 first_chain=0):
+                 first_chain=0, likelihood='probit'):
         super(BatchedAPMEllSSPlusRandDirSliceSampler, self).__init__(
             X, y, n_chains, n_imp, prior, kernel, epsilon, max_slice_iters, seed, estimator,
-            device, first_chain)
+            device, first_chain, likelihood=likelihood)
         self.w = float(w)
         self.max_steps_out = int(max_steps_out)
         C = self.n_chains
@@ -745,10 +748,10 @@ class BatchedAPMEllSSPlusMHSampler(_BatchedMHMixin, _BatchedChains):
 
     def __init__(self, X, y, n_chains, n_imp, prior, prop_scales, kernel='ard', epsilon=1e-8,
                  metropolis=False, max_slice_iters=1000, seed=0, estimator='is', device=None,
-                 first_chain=0):
+                 first_chain=0, likelihood='probit'):
         super(BatchedAPMEllSSPlusMHSampler, self).__init__(
             X, y, n_chains, n_imp, prior, kernel, epsilon, max_slice_iters, seed, estimator,
-            device, first_chain)
+            device, first_chain, likelihood=likelihood)
         self._init_mh(prop_scales, metropolis)
 
     def _mh_theta(self):
@@ -780,10 +783,11 @@ class BatchedPMMHSampler(_BatchedMHMixin, _BatchedChains):
     (``sampler.log_f_estimator = log_f_estimator_main`` in the notebook)."""
 
     def __init__(self, X, y, n_chains, n_imp, prior, prop_scales, kernel='iso', epsilon=1e-8,
-                 metropolis=False, seed=0, estimator='is', device=None, first_chain=0):
+                 metropolis=False, seed=0, estimator='is', device=None, first_chain=0,
+                 likelihood='probit'):
         super(BatchedPMMHSampler, self).__init__(
             X, y, n_chains, n_imp, prior, kernel, epsilon, 1000, seed, estimator, device,
-            first_chain)
+            first_chain, likelihood=likelihood)
         self._init_mh(prop_scales, metropolis)
 
     def set_estimator(self, estimator):
@@ -849,10 +853,10 @@ class BatchedAPMMetIndPlusSeqSliceSampler(BatchedAPMEllSSPlusRandDirSliceSampler
 
     def __init__(self, X, y, n_chains, n_imp, prior, ws, kernel='ard', epsilon=1e-8,
                  max_steps_out=0, max_slice_iters=1000, seed=0, estimator='is', device=None,
-                 first_chain=0):
+                 first_chain=0, likelihood='probit'):
         super(BatchedAPMMetIndPlusSeqSliceSampler, self).__init__(
             X, y, n_chains, n_imp, prior, kernel, epsilon, 1., max_steps_out, max_slice_iters,
-            seed, estimator, device, first_chain)
+            seed, estimator, device, first_chain, likelihood=likelihood)
         self.ws = np.array(np.broadcast_to(np.asarray(ws, dtype=np.float64), (self.P,)))
 
     def _u_update(self, chains=None):
@@ -888,10 +892,11 @@ class BatchedAPMEllSSPlusEllSSSampler(BatchedAPMEllSSPlusRandDirSliceSampler):
     RandomState (drawn first, as samplers.py:1163), on the asynchronous schedule."""
 
     def __init__(self, X, y, n_chains, n_imp, theta_prior_std, kernel='ard', epsilon=1e-8,
-                 max_slice_iters=1000, seed=0, estimator='is', device=None, first_chain=0):
+                 max_slice_iters=1000, seed=0, estimator='is', device=None, first_chain=0,
+                 likelihood='probit'):
         super(BatchedAPMEllSSPlusEllSSSampler, self).__init__(
             X, y, n_chains, n_imp, {}, kernel, epsilon, 1., 0, max_slice_iters, seed, estimator,
-            device, first_chain)
+            device, first_chain, likelihood=likelihood)
         self.theta_prior_std = np.array(np.broadcast_to(
             np.asarray(theta_prior_std, dtype=np.float64), (self.P,)))
         C = self.n_chains

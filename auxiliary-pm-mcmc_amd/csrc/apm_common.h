@@ -51,6 +51,91 @@ __device__ __forceinline__ double log_ndtr_mixed(double z) {
     return (double)log1pf(-0.5f * erfcf(zf * rs2));
 }
 
+// ---------------------------------------------------------------------------------------------
+// The likelihood p(y | f) of a latent value, y in {-1, +1}: a template parameter
+// LIK of the five kernels that evaluate it (k_newton_prep, k_laplace_lml, k_grad_rows, the u-path
+// epilogue of k_ugemm / k_ugemm64, k_predict_reduce) and a launch-time switch of their launchers,
+// as the covariance family FAM is. The values are include/apm.h's.
+//   probit  p = Phi(y f)          v = phi(f)/Phi(y f), grad = y v, W = v^2 + grad f
+//   logit   p = sigma(y f)        t = y f, grad = y sigma(-t), W = sigma(t) sigma(-t) in (0, 1/4]
+#define APM_LIK_PROBIT 0
+#define APM_LIK_LOGIT 1
+#define APM_LIK_DISPATCH(lik, ...)                                                    \
+    switch (lik) {                                                                    \
+        case APM_LIK_LOGIT: { constexpr int LIK = APM_LIK_LOGIT; __VA_ARGS__; } break; \
+        default: { constexpr int LIK = APM_LIK_PROBIT; __VA_ARGS__; } break;          \
+    }
+
+// sigma(u) = 1/(1 + e^-u) without overflow or cancellation on the whole line
+__device__ __forceinline__ double sigmoid_d(double u) {
+    const double e = exp(-fabs(u));
+    const double r = 1.0 / (1.0 + e);
+    return u >= 0.0 ? r : e * r;
+}
+
+// log sigma(t): -log1p(e^-t) for t >= 0, t - log1p(e^t) for t < 0 (accurate on the whole line,
+// as log_ndtr_d)
+__device__ __forceinline__ double log_sigmoid_d(double t) {
+    if (t < 0.0) return t - log1p(exp(t));
+    return -log1p(exp(-t));
+}
+
+// log sigma(t) with the linear part t of the negative branch in fp64 and the remainder
+// log1p(e^-|t|) in (0, log 2] in fp32 (log_ndtr_mixed's twin for the u-path epilogue)
+__device__ __forceinline__ double log_sigmoid_mixed(double t) {
+    const float tf = (float)t;
+    if (t < 0.0) return t - (double)log1pf(expf(tf));
+    return -(double)log1pf(expf(-tf));
+}
+
+// log p(y | f) at t = y f
+template <int LIK>
+__device__ __forceinline__ double lik_logp(double t) {
+    if constexpr (LIK == APM_LIK_LOGIT) return log_sigmoid_d(t);
+    else return log_ndtr_d(t);
+}
+template <int LIK>
+__device__ __forceinline__ double lik_logp_mixed(double t) {
+    if constexpr (LIK == APM_LIK_LOGIT) return log_sigmoid_mixed(t);
+    else return log_ndtr_mixed(t);
+}
+
+// grad = d log p / df and W = -d^2 log p / df^2 at f (lpa.py:86-88 for the probit). The logit's
+// sigma(-t) is 1/(1 + e^t) itself, never 1 - sigma(t).
+struct LikGW {
+    double grad, W;
+};
+template <int LIK>
+__device__ __forceinline__ LikGW lik_grad_W(double f, double yi) {
+    if constexpr (LIK == APM_LIK_LOGIT) {
+        const double t = yi * f;
+        const double sm = sigmoid_d(-t);
+        return LikGW{yi * sm, sigmoid_d(t) * sm};
+    } else {
+        const double vv = exp(-0.5 * f * f - log_ndtr_d(yi * f) - 0.91893853320467274178);
+        const double grad = vv * yi;
+        return LikGW{grad, vv * vv + grad * f};
+    }
+}
+
+// grad and the third derivative d3 = d^3 log p / df^3 = -dW/df at f (gradient.hip); the logit's
+// 1 - 2 sigma(t) is formed as sigma(-t) - sigma(t)
+struct LikGD3 {
+    double grad, d3;
+};
+template <int LIK>
+__device__ __forceinline__ LikGD3 lik_grad_d3(double fi, double yi) {
+    if constexpr (LIK == APM_LIK_LOGIT) {
+        const double t = yi * fi;
+        const double sp = sigmoid_d(t), sm = sigmoid_d(-t);
+        return LikGD3{yi * sm, -yi * (sp * sm) * (sm - sp)};
+    } else {
+        const double v = exp(-0.5 * fi * fi - log_ndtr_d(yi * fi) - 0.91893853320467274178);
+        const double d3 = -((2.0 * v + yi * fi) * (-fi * v - yi * v * v) + yi * v);
+        return LikGD3{yi * v, d3};
+    }
+}
+
 // wave64 reductions
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll

@@ -113,6 +113,7 @@ struct __attribute__((visibility("hidden"))) apm_ctx {
     std::vector<double*> l64_h, l64_free;
     double** l64_d = nullptr;
     double eps = 1e-8, tol = 1e-4;
+    int lik = APM_LIK_PROBIT;  // apm_set_likelihood: p(y|f) of every later call on the context
     int64_t max_iters = 1000;
     std::string err;
     // device data

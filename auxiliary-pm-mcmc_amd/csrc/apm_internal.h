@@ -277,16 +277,18 @@ void launch_gram_cross(MatB out, int64_t row0, const double* Xs, int ms, int mb,
 // per chain and test row r < ms: mean = sum_tj part[tj][r] (in order), var = sig[b] - |row r of V^T|^2
 // over columns [0, 64 nb) of A's rows [row0, ..), prob = Phi(mean / sqrt(1 + var)); each output
 // out[b * ostride + r]. Nothing is clamped.
-void launch_predict_reduce(MatB A, int64_t row0, int ms, int mb, int nb, const double* sig,
-                           const double* part, int64_t pstride, double* mean,
+// lik (APM_LIK_*): the logit's prob is the Gauss-Hermite average of sigma (gh_table.h)
+void launch_predict_reduce(int lik, MatB A, int64_t row0, int ms, int mb, int nb,
+                           const double* sig, const double* part, int64_t pstride, double* mean,
                            double* var, double* prob, int64_t ostride, Live live, int nchains,
                            hipStream_t s);
 
 // ---- gradient.hip: gradient of the Laplace LML w.r.t. theta ---------------
 // per chain and row r < 64 nb: dS = K_rr - |row np + r of A over columns [0, 64 nb)|^2,
 // g = y phi(f)/Phi(y f), s2 = 1/2 dS d3 (third derivative of log p at f); zeros for r >= n.
-// Each output out[b * gstride + r]; f per chain with stride vstride.
-void launch_grad_rows(MatB A, MatB K, int n, int nb, const double* f, const double* y,
+// Each output out[b * gstride + r]; f per chain with stride vstride. lik (APM_LIK_*): g and d3
+// are the likelihood's (lik_grad_d3, apm_common.h)
+void launch_grad_rows(int lik, MatB A, MatB K, int n, int nb, const double* f, const double* y,
                       int64_t vstride, double* dS, double* g, double* s2, int64_t gstride,
                       Live live, int nchains, hipStream_t s);
 // A's rows [np, 2np) x columns [0, np) <- diag(Ws) (whole tiles), and zeros in the lower tiles of
@@ -320,8 +322,9 @@ struct NewtonVecs {     // all per chain, stride vstride (>= np)
     double* z;          // TRSV result
     int64_t vstride;
 };
-void launch_newton_prep(NewtonVecs v, const double* y, int n, int np, Live live, int nchains,
-                        hipStream_t s);
+// lik (APM_LIK_*, apm_common.h): the likelihood whose grad / W / log p the launch evaluates
+void launch_newton_prep(int lik, NewtonVecs v, const double* y, int n, int np, Live live,
+                        int nchains, hipStream_t s);
 void launch_gemv(MatB M, const double* x, int64_t xstride, double* out, int64_t ostride, int np,
                  Live live, int nchains, hipStream_t s);
 void launch_form_B(MatB K, MatB A, NewtonVecs v, int np, Live live, int nchains, hipStream_t s);
@@ -331,8 +334,8 @@ void launch_newton_check(NewtonVecs v, int n, int np, double tol, int* active, c
 void launch_copy_lower(MatB src, MatB dst, int np, Live live, int nchains, hipStream_t s);
 void launch_form_aug(MatB K, MatB A, NewtonVecs v, int np, Live live, int nchains,
                      hipStream_t s, bool lower_only = false);
-// per chain: out[b] = -0.5 a.f + sum_n log_ndtr(y f) - 0.5*sum(ldet[0..nb))*2
-void launch_laplace_lml(NewtonVecs v, const double* y, int n, const double* ldet,
+// per chain: out[b] = -0.5 a.f + sum_n log p(y|f) - 0.5*sum(ldet[0..nb))*2
+void launch_laplace_lml(int lik, NewtonVecs v, const double* y, int n, const double* ldet,
                         int64_t lstride, int nb, double* out, Live live, int nchains,
                         hipStream_t s);
 
@@ -431,7 +434,7 @@ void launch_u_combine(UPool P, const int64_t* dst, const int64_t* a, const int64
                       hipStream_t s);
 // partial[b][i][s] = sum over rows of row-block i of t(n,s) (i < nb), partial[b][nb][s] = g^T u_s
 // wide: also launch the f64 MFMA twin for the call's wide slots (k_ugemm64)
-void launch_ugemm(SlotSet S, const int64_t* slots, UPool P, const int64_t* ubufs,
+void launch_ugemm(int lik, SlotSet S, const int64_t* slots, UPool P, const int64_t* ubufs,
                   const double* y, int n, int np, double* partial, int64_t pstride,
                   const int* status, int nchains, bool wide, hipStream_t s);
 void launch_lme(const double* partial, int64_t pstride, int nb, int S, int sp, SlotSet Sl,

@@ -7,7 +7,7 @@
 
 #include "apm_host.h"
 
-#define APM_VERSION 2
+#define APM_VERSION 3
 
 using namespace apm_host;
 
@@ -85,6 +85,15 @@ int apm_set_newton(apm_ctx* ctx, double diff_f_tol, int64_t max_iters) {
     ctx->max_iters = max_iters;
     return APM_SUCCESS;
 }
+
+int apm_set_likelihood(apm_ctx* ctx, int lik) {
+    if (!ctx || (lik != APM_LIK_PROBIT && lik != APM_LIK_LOGIT))
+        return fail(ctx, APM_E_INVALID, "apm_set_likelihood: bad arguments");
+    ctx->lik = lik;
+    return APM_SUCCESS;
+}
+
+int apm_likelihood(const apm_ctx* ctx) { return ctx ? ctx->lik : APM_E_INVALID; }
 
 void* apm_stream(apm_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 
@@ -482,8 +491,17 @@ int apm_laplace_grad(apm_ctx* c, int64_t count, const double* thetas, int64_t ld
 int apm_laplace(int device, const double* K, int64_t n, int64_t ldk, const double* y,
                 int calc_cov, int calc_lml, double diff_f_tol, int64_t max_iters, double* f_out,
                 double* C_out, int64_t ldc, double* lml_out, int64_t* n_iter_out, int* status) {
+    return apm_laplace_lik(device, APM_LIK_PROBIT, K, n, ldk, y, calc_cov, calc_lml, diff_f_tol,
+                           max_iters, f_out, C_out, ldc, lml_out, n_iter_out, status);
+}
+
+int apm_laplace_lik(int device, int lik, const double* K, int64_t n, int64_t ldk, const double* y,
+                    int calc_cov, int calc_lml, double diff_f_tol, int64_t max_iters,
+                    double* f_out, double* C_out, int64_t ldc, double* lml_out,
+                    int64_t* n_iter_out, int* status) {
     if (!K || !y || n <= 0 || ldk < n || !f_out || !status || max_iters < 0 ||
-        (calc_cov && (!C_out || ldc < n)) || (calc_lml && !lml_out))
+        (calc_cov && (!C_out || ldc < n)) || (calc_lml && !lml_out) ||
+        (lik != APM_LIK_PROBIT && lik != APM_LIK_LOGIT))
         return fail(nullptr, APM_E_INVALID, "apm_laplace: bad arguments");
     std::lock_guard<std::mutex> lk(g_mu);
     auto key = std::make_tuple(device, n, (int64_t)0, (int)APM_KERNEL_PRECOMPUTED);
@@ -501,6 +519,7 @@ int apm_laplace(int device, const double* K, int64_t n, int64_t ldk, const doubl
         }
         c->tol = diff_f_tol;
         c->max_iters = max_iters;
+        c->lik = lik;  // (the shape's cached context serves both likelihoods)
         const int np = c->np;
         std::vector<double> Kp;  // (alive until the syncs below)
         upload_padded_K(c, K, ldk, Kp);
@@ -518,8 +537,8 @@ int apm_laplace(int device, const double* K, int64_t n, int64_t ldk, const doubl
         if (st[0] != APM_STATUS_OK) return APM_SUCCESS;
         HIPC(hipMemcpyAsync(f_out, c->v.f, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
         if (calc_lml) {
-            launch_laplace_lml(c->v, c->y, (int)n, c->ldet, c->lstride, c->nb, c->out, live_of(c),
-                               1, c->stream);
+            launch_laplace_lml(c->lik, c->v, c->y, (int)n, c->ldet, c->lstride, c->nb, c->out,
+                               live_of(c), 1, c->stream);
             HIPC(hipMemcpyAsync(lml_out, c->out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
         }
         if (calc_cov) {

@@ -694,7 +694,7 @@ struct __attribute__((aligned(16))) GemmSmemH3 {
 // matrices (numpy emulation, N = 1024, sigma = 1 .. e^4) the factor's residual |LL^T - B| is
 // unchanged and the refinement contraction rises from ~3e-6 to ~1e-5, far below the 1e-3 of the
 // acceptance test. fp16's range bounds the operands (entries of L, |L_ij| <= sqrt(B_ii) <=
-// sqrt(B_ii) = sqrt(1 + W_i K_ii) <= sqrt(1 + e^theta_0 + eps), probit W < 1): the host flags
+// sqrt(B_ii) = sqrt(1 + W_i K_ii) <= sqrt(1 + e^theta_0 + eps): probit W < 1, logit W <= 1/4): the host flags
 // the chains with theta_0 < 19 (entries < 1.4e4 < 65504) in h3ok; the others take the fp32
 // path inside the same launch, so a chain's result does not depend on its batch. The appended
 // right-hand-side row (forward solve of W^1/2 K b, unbounded) stays fp32: super-tiles reaching

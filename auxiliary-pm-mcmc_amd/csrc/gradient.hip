@@ -3,6 +3,7 @@
 // Cholesky (chol_solve_rows on the bottom rows of the work matrix against the last Newton factor).
 //
 //   v = phi(f)/Phi(y f),  g = y v,  d3 = -[(2v + y f)(-f v - y v^2) + y v]      (f = K a, the mode)
+//   (the probit; the logit: g = y sigma(-y f), d3 = -y W (1 - 2 sigma(y f)) - lik_grad_d3)
 //   dS_i = K_ii - |L^-1 (W^1/2 . K[:, i])|^2,  s2 = 1/2 dS . d3
 //   R = Z^T Z with Z = L^-1 diag(W^1/2),  q = s2 - R (K s2)
 //   M = 1/2 a a^T - 1/2 R + 1/2 (q g^T + g q^T)
@@ -33,6 +34,7 @@ __device__ __forceinline__ bool live_g(const Live& lv, int b) {
 // matrix over its first 64 nb columns (the row of (K W^1/2) L^-T; 16-byte loads, consecutive
 // lanes consecutive pieces, each lane its pieces in order, then the wave's butterfly) and K's own
 // diagonal entry, then g_r and s2_r at the mode. Rows >= n get exact zeros.
+template <int LIK>
 __global__ __launch_bounds__(256) void k_grad_rows(MatB A, MatB K, int n, int nb,
                                                    const double* __restrict__ f,
                                                    const double* __restrict__ y, int64_t vstride,
@@ -60,18 +62,17 @@ __global__ __launch_bounds__(256) void k_grad_rows(MatB A, MatB K, int n, int nb
     if (lane != 0) return;
     const double ds = K.base[b * K.cstride + (int64_t)r * K.ld + r] - s;
     const double fi = f[b * vstride + r], yi = y[r];
-    const double v = exp(-0.5 * fi * fi - log_ndtr_d(yi * fi) - 0.91893853320467274178);
-    const double d3 = -((2.0 * v + yi * fi) * (-fi * v - yi * v * v) + yi * v);
+    const LikGD3 l = lik_grad_d3<LIK>(fi, yi);
     dS[o] = ds;
-    g[o] = yi * v;
-    s2[o] = 0.5 * ds * d3;
+    g[o] = l.grad;
+    s2[o] = 0.5 * ds * l.d3;
 }
 
-void launch_grad_rows(MatB A, MatB K, int n, int nb, const double* f, const double* y,
+void launch_grad_rows(int lik, MatB A, MatB K, int n, int nb, const double* f, const double* y,
                       int64_t vstride, double* dS, double* g, double* s2, int64_t gstride,
                       Live live, int nchains, hipStream_t s) {
-    APM_LAUNCH(k_grad_rows, dim3((64 * nb + 3) / 4, nchains), dim3(256), 0, s, A, K, n, nb, f, y,
-               vstride, dS, g, s2, gstride, live);
+    APM_LIK_DISPATCH(lik, APM_LAUNCH(k_grad_rows<LIK>, dim3((64 * nb + 3) / 4, nchains), dim3(256),
+                                     0, s, A, K, n, nb, f, y, vstride, dS, g, s2, gstride, live));
 }
 
 // Right-hand side of the second pass: rows [np, 2np) x columns [0, np) of the work matrix

@@ -77,8 +77,9 @@ void upload_idx(apm_ctx* c, int count, const int64_t* slots, const int64_t* ubuf
 // pin_inv, the layout of the device block h3ok .. h3ok + 3B, uploaded with one copy, and the icm
 // thresholds in pin_icm) -> device. fp16x3 operands (chol32.hip): the walk's and
 // the trailing updates' operands are solved entries of L, |L_ij| <= sqrt(B_ii) <= sqrt(1 + K_ii)
-// (probit W < 1); the explicit-inverse panel also splits Schur-complement entries of B itself,
-// |A_ij| <= max B_ii <= 1 + K_ii, so its flag asks 1 + K_ii < 2^15 (fp16 overflows at 65504).
+// (probit W < 1, logit W <= 1/4); the explicit-inverse panel also splits Schur-complement
+// entries of B itself, |A_ij| <= max B_ii <= 1 + K_ii, so its flag asks 1 + K_ii < 2^15 (fp16
+// overflows at 65504).
 // h3_now = any chain flagged (else the fp32-operand kernels launch), inv_any / inv_all likewise.
 void upload_h3(apm_ctx* c, int count) {
     int* h = pin_h3(c);

@@ -54,7 +54,7 @@ void predict_block(apm_ctx* c, int count, const double* xs, int ms) {
                       c->psig, c->kind, c->v.Ws, c->v.a, c->v.vstride, c->ppart, nb * np, lv, 0,
                       count, c->stream);
     chol_solve_rows(c, c->A, nb, /*row_start=*/nb, /*R=*/nb + mb, /*Cb=*/nb, count);
-    launch_predict_reduce(c->A, np, ms, mb, nb, c->psig, c->ppart, nb * np, c->pmean,
+    launch_predict_reduce(c->lik, c->A, np, ms, mb, nb, c->psig, c->ppart, nb * np, c->pmean,
                           c->pvar, c->pprob, np, lv, count, c->stream);
 }
 
@@ -83,8 +83,8 @@ void grad_block(apm_ctx* c, int count) {
            *q = u + B * np;
     launch_form_aug(c->K, c->A, c->v, c->np, lv, count, c->stream, /*lower_only=*/!c->k_full);
     chol_solve_rows(c, c->A, nb, /*row_start=*/nb, /*R=*/2 * nb, /*Cb=*/nb, count);
-    launch_grad_rows(c->A, c->K, c->n, nb, c->v.f, c->y, c->v.vstride, dS, g, s2, np, lv, count,
-                     c->stream);
+    launch_grad_rows(c->lik, c->A, c->K, c->n, nb, c->v.f, c->y, c->v.vstride, dS, g, s2, np, lv,
+                     count, c->stream);
     launch_symv(c->K, s2, np, t, np, c->sympart, c->sstride, c->np, MatF{}, nullptr, 0, lv, count,
                 c->stream, c->symv_tpw);
     launch_grad_fill(c->A, c->v.Ws, c->v.vstride, nb, lv, count, c->stream);

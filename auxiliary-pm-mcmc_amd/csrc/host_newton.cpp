@@ -224,7 +224,7 @@ void newton(apm_ctx* c, int count, std::vector<int>& st_h, bool mixed, int live0
             const int its = std::max<int>(1, c->newton_last - (int)it);
             c->cholk_quota = (left + its - 1) / its;
         }
-        launch_newton_prep(c->v, c->y, c->n, c->np, lv, count, c->stream);
+        launch_newton_prep(c->lik, c->v, c->y, c->n, c->np, lv, count, c->stream);
         if (mixed) {  // K b and the fp32 B (+ its right-hand side) in one pass over K's lower half
             launch_symv(c->K, c->v.b, c->v.vstride, c->v.Kb, c->v.vstride, c->sympart, c->sstride,
                         c->np, b32_of(c), c->v.Ws, c->v.vstride, lv, count, c->stream,

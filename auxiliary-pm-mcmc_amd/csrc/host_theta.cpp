@@ -2,7 +2,7 @@
 //
 // theta-call (ApproxPosteriorIS, gpdemo/estimators.py:203-241), per batch of chains, one stream:
 //   Gram -> Newton loop { prep, K b, form B|rhs, chol(B) (+ forward solve), L^T solve, a, K a,
-//   check } -> augmented chol [[B,.],[K W^1/2, K],[0, f_post^T]] -> slot -> L.U + probit -> LME
+//   check } -> augmented chol [[B,.],[K W^1/2, K],[0, f_post^T]] -> slot -> L.U + likelihood -> LME
 // The only host syncs are one per Newton iteration (convergence flags) and one at the end.
 #include "apm_host.h"
 
@@ -23,8 +23,8 @@ namespace apm_host {
 void u_eval_device(apm_ctx* c, int count, bool wide) {
     {
         ProfScope ps(c, APM_PROF_UGEMM, (double)c->n * (c->n + 1) * c->S * count);
-        launch_ugemm(c->Sl, c->d_slots, c->Up, c->d_ubufs, c->y, c->n, c->np, c->partial,
-                     c->pstride, c->status, count, wide, c->stream);
+        launch_ugemm(c->lik, c->Sl, c->d_slots, c->Up, c->d_ubufs, c->y, c->n, c->np,
+                     c->partial, c->pstride, c->status, count, wide, c->stream);
     }
     launch_lme(c->partial, c->pstride, c->nb, c->S, c->sp, c->Sl, c->d_slots, c->out, c->status,
                count, c->stream);
@@ -370,8 +370,8 @@ void theta_eval_impl(apm_ctx* c, int est, int count, bool gram, double* out_logf
                               count, c->stream);  // 1/2 log|K| (chol(K) on stream2: ldet + nb)
         }
         if (est == APM_EST_LAPLACE) {
-            launch_laplace_lml(c->v, c->y, c->n, c->ldet, c->lstride, c->nb, c->out, lv, count,
-                               c->stream);
+            launch_laplace_lml(c->lik, c->v, c->y, c->n, c->ldet, c->lstride, c->nb, c->out, lv,
+                               count, c->stream);
         } else {
             post_cov_lk(c, count, ov);
             launch_slot_write(c->A, c->v, c->ldet, c->lstride, c->nb, c->Sl, c->d_slots,

@@ -4,6 +4,8 @@
 //   v = phi(f)/Phi(yf) (:86), grad = v y, W = v^2 + grad f (:87-88), B = I + W^1/2 K W^1/2 (:89-91),
 //   L = chol(B) (:92), b = W f + grad (:93), a = b - W^1/2 L^-T L^-1 W^1/2 K b (:94), f <- K a (:95),
 //   stop when mean((f_new - f)^2) < tol (:96-97).
+// grad, W and the LML's log p(y|f) are the likelihood's (LIK, apm_common.h): the lines above are
+// the probit's; the logit has grad = y sigma(-y f), W = sigma(y f) sigma(-y f).
 // The forward solve L^-1 (W^1/2 K b) is produced by the Cholesky itself: W^1/2 K b is appended as an
 // extra row below B, so the factorisation of the (np+64) x np trapezoid returns it in that row.
 #include "apm_internal.h"
@@ -13,6 +15,7 @@ __device__ __forceinline__ bool live_b(const Live& lv, int b) {
 }
 
 // ------------------------------------------------------------------------------- vectors
+template <int LIK>
 __global__ __launch_bounds__(256) void k_newton_prep(NewtonVecs v, const double* __restrict__ y,
                                                      int n, int np, Live live) {
     const int b = blockIdx.y;
@@ -23,21 +26,20 @@ __global__ __launch_bounds__(256) void k_newton_prep(NewtonVecs v, const double*
     double W = 0.0, Ws = 0.0, bb = 0.0;
     if (i < n) {
         const double f = v.f[o], yi = y[i];
-        const double vv = exp(-0.5 * f * f - log_ndtr_d(yi * f) - 0.91893853320467274178);
-        const double grad = vv * yi;
-        W = vv * vv + grad * f;
+        const LikGW l = lik_grad_W<LIK>(f, yi);
+        W = l.W;
         Ws = sqrt(W);
-        bb = W * f + grad;
+        bb = W * f + l.grad;
     }
     v.W[o] = W;
     v.Ws[o] = Ws;
     v.b[o] = bb;
 }
 
-void launch_newton_prep(NewtonVecs v, const double* y, int n, int np, Live live, int nchains,
-                        hipStream_t s) {
-    APM_LAUNCH(k_newton_prep, dim3((np + 255) / 256, nchains), dim3(256), 0, s, v, y, n,
-                       np, live);
+void launch_newton_prep(int lik, NewtonVecs v, const double* y, int n, int np, Live live,
+                        int nchains, hipStream_t s) {
+    APM_LIK_DISPATCH(lik, APM_LAUNCH(k_newton_prep<LIK>, dim3((np + 255) / 256, nchains),
+                                     dim3(256), 0, s, v, y, n, np, live));
 }
 
 // out = M x for a full np x np row-major M; one wave per row, 16-byte loads
@@ -236,6 +238,7 @@ void launch_form_aug(MatB K, MatB A, NewtonVecs v, int np, Live live, int nchain
 }
 
 // Laplace LML (latent_posterior_approximations.py:103-106), with -sum log L_ii = -sum_k ldet[k]
+template <int LIK>
 __global__ __launch_bounds__(256) void k_laplace_lml(NewtonVecs v, const double* __restrict__ y,
                                                      int n, const double* ldet, int64_t lstride,
                                                      int nb, double* out, Live live) {
@@ -247,7 +250,7 @@ __global__ __launch_bounds__(256) void k_laplace_lml(NewtonVecs v, const double*
     double s1 = 0.0, s2 = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) {
         s1 += a[i] * f[i];
-        s2 += log_ndtr_d(y[i] * f[i]);
+        s2 += lik_logp<LIK>(y[i] * f[i]);
     }
     s1 = block_sum_d(s1, red);
     __syncthreads();
@@ -259,11 +262,11 @@ __global__ __launch_bounds__(256) void k_laplace_lml(NewtonVecs v, const double*
     }
 }
 
-void launch_laplace_lml(NewtonVecs v, const double* y, int n, const double* ldet,
+void launch_laplace_lml(int lik, NewtonVecs v, const double* y, int n, const double* ldet,
                         int64_t lstride, int nb, double* out, Live live, int nchains,
                         hipStream_t s) {
-    APM_LAUNCH(k_laplace_lml, dim3(nchains), dim3(256), 0, s, v, y, n, ldet, lstride, nb,
-                       out, live);
+    APM_LIK_DISPATCH(lik, APM_LAUNCH(k_laplace_lml<LIK>, dim3(nchains), dim3(256), 0, s, v, y, n,
+                                     ldet, lstride, nb, out, live));
 }
 
 // ------------------------------------------------------------------------------- cache slots

@@ -8,6 +8,7 @@
 //   pi*  = Phi(mu* / sqrt(1 + var*))
 // with W, L, a of the last Newton iteration (latent_posterior_approximations.py:81-112).
 #include "apm_internal.h"
+#include "gh_table.h"
 
 #define GK 32         // features per LDS chunk (k_gram's)
 #define GP (128 + 2)  // LDS row pitch in doubles (k_gram's)
@@ -160,6 +161,16 @@ void launch_gram_cross(MatB out, int64_t row0, const double* Xs, int ms, int mb,
 // the 64 nb columns (16-byte loads, consecutive lanes consecutive pieces; each lane its pieces in
 // order, then the wave's butterfly), mu* from the tile-column partials in order, and the probit
 // average through erfc, whose lower tail keeps its relative accuracy (Phi(z) = erfc(-z/sqrt2)/2).
+// The logit has no closed form: pi* = sum_q w_q sigma(mu* + sqrt(2 var*) x_q) over the
+// Gauss-Hermite table (gh_table.h), one pair of nodes +-x_q per lane and the
+// wave's butterfly, a fixed order. With a_q = sqrt(2 var*) x_q >= 0:
+//   mu* <  0:  sum_q w_q [sigma(mu* + a_q) + sigma(mu* - a_q)]          (every term positive: the
+//                                                                        lower tail stays relative)
+//   mu* >= 0:  1/2 + sum_q w_q [sigma(mu* + a_q) - sigma(a_q - mu*)]    (sigma(u) = 1 - sigma(-u),
+//                                                                        2 sum_q w_q = 1)
+// so an uninformed test point (mu* = 0 exactly) returns 0.5 bitwise, whatever its variance. A
+// variance <= 0 (nothing is clamped) takes a_q = 0: sigma(mu*).
+template <int LIK>
 __global__ __launch_bounds__(256) void k_predict_reduce(
     MatB A, int64_t row0, int ms, int mb, int nb, const double* __restrict__ sig,
     const double* __restrict__ part, int64_t pstride, double* __restrict__ mean,
@@ -176,21 +187,41 @@ __global__ __launch_bounds__(256) void k_predict_reduce(
         s = fma(v.y, v.y, s);
     }
     s = wave_sum_d(s);
-    if (lane != 0) return;
-    const double* pb = part + b * pstride + r;
-    double mu = 0.0;
-    for (int tj = 0; tj < nb; ++tj) mu += pb[(int64_t)tj * (64 * mb)];
-    const double v = sig[b] - s;
-    const double z = mu / sqrt(1.0 + v);
-    mean[b * ostride + r] = mu;
-    var[b * ostride + r] = v;
-    prob[b * ostride + r] = 0.5 * erfc(-z * 0.70710678118654752440);
+    if constexpr (LIK == APM_LIK_LOGIT) {  // (every lane has s; the wave stays whole)
+        const double* pb = part + b * pstride + r;
+        double mu = 0.0;
+        for (int tj = 0; tj < nb; ++tj) mu += pb[(int64_t)tj * (64 * mb)];
+        const double v = sig[b] - s;
+        const double sd = v > 0.0 ? sqrt(2.0 * v) : 0.0;
+        double acc = 0.0;
+        for (int q = lane; q < APM_GH_PAIRS; q += 64) {
+            const double a = sd * APM_GH_X[q];
+            const double up = sigmoid_d(mu + a);
+            acc += APM_GH_W[q] * (mu < 0.0 ? up + sigmoid_d(mu - a) : up - sigmoid_d(a - mu));
+        }
+        acc = wave_sum_d(acc);
+        if (lane != 0) return;
+        mean[b * ostride + r] = mu;
+        var[b * ostride + r] = v;
+        prob[b * ostride + r] = mu < 0.0 ? acc : 0.5 + acc;
+    } else {
+        if (lane != 0) return;
+        const double* pb = part + b * pstride + r;
+        double mu = 0.0;
+        for (int tj = 0; tj < nb; ++tj) mu += pb[(int64_t)tj * (64 * mb)];
+        const double v = sig[b] - s;
+        const double z = mu / sqrt(1.0 + v);
+        mean[b * ostride + r] = mu;
+        var[b * ostride + r] = v;
+        prob[b * ostride + r] = 0.5 * erfc(-z * 0.70710678118654752440);
+    }
 }
 
-void launch_predict_reduce(MatB A, int64_t row0, int ms, int mb, int nb, const double* sig,
-                           const double* part, int64_t pstride, double* mean,
+void launch_predict_reduce(int lik, MatB A, int64_t row0, int ms, int mb, int nb,
+                           const double* sig, const double* part, int64_t pstride, double* mean,
                            double* var, double* prob, int64_t ostride, Live live, int nchains,
                            hipStream_t s) {
-    APM_LAUNCH(k_predict_reduce, dim3((ms + 3) / 4, nchains), dim3(256), 0, s, A, row0, ms, mb, nb,
-               sig, part, pstride, mean, var, prob, ostride, live);
+    APM_LIK_DISPATCH(lik, APM_LAUNCH(k_predict_reduce<LIK>, dim3((ms + 3) / 4, nchains), dim3(256),
+                                     0, s, A, row0, ms, mb, nb, sig, part, pstride, mean, var,
+                                     prob, ostride, live));
 }

@@ -1,8 +1,8 @@
-// Importance-sampling u-path: f_s = f_post + L U (fp32 MFMA), probit epilogue, log-mean-exp.
+// Importance-sampling u-path: f_s = f_post + L U (fp32 MFMA), likelihood epilogue, log-mean-exp.
 //
 // Replaces gpdemo/estimators.py:221-241 (ApproxPosteriorIS, theta- and cached u-calls) and
 // :323-325 (PriorMC) in the algebraically identical, self-consistent form of DESIGN.md §3.2:
-//   log w_s = sum_n [log Phi(y_n f_sn) + 1/2 W_n f_sn^2 - z_n f_sn] + cst,
+//   log w_s = sum_n [log p(y_n|f_sn) + 1/2 W_n f_sn^2 - z_n f_sn] + cst,   (p = Phi(y f) or sigma(y f))
 //   z = C^-1 f_post = a + W f_post,  cst = 1/2 f_post^T z - 1/2 log|B|   (IS)
 //   W = 0, z = 0, cst = 0                                               (PriorMC)
 // i.e. the reference's log p(y|f) + log p(f) - log q(f) evaluated AT the computed f_s (with
@@ -134,14 +134,17 @@ void launch_u_combine(UPool P, const int64_t* dst, const int64_t* a, const int64
 // C/D lane l, reg r -> (row = (l>>4)*4 + r, col = l&15)
 #define UP 65  // LDS row pitch (floats) of the staged U tile: conflict-free B-fragment reads
 
-// one entry of the per-sample sum: log Phi(y f) + 1/2 W f^2 - z f, the large terms in fp64
+// one entry of the per-sample sum: log p(y | f) + 1/2 W f^2 - z f, the large terms in fp64
+// (probit: log Phi(y f), logit: log sigma(y f))
+template <int LIK>
 __device__ __forceinline__ double is_term(double f, double y, double W, double z) {
-    return log_ndtr_mixed(y * f) + (0.5 * W * f - z) * f;
+    return lik_logp_mixed<LIK>(y * f) + (0.5 * W * f - z) * f;
 }
 
 // One 64 x 64 output tile (row block i, sample block sb) per workgroup, waves 32 x 32 (a 64 x 128
 // tile that read L once per two sample blocks was measured slower from 8 chains up: half the
 // workgroups, 2 instead of 4 per CU - DESIGN.md §5).
+template <int LIK>
 __global__ __launch_bounds__(256) void k_ugemm(SlotSet S, const int64_t* __restrict__ slots,
                                                UPool P, const int64_t* __restrict__ ubufs,
                                                const double* __restrict__ y, int n, int np,
@@ -252,7 +255,7 @@ __global__ __launch_bounds__(256) void k_ugemm(SlotSet S, const int64_t* __restr
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = i * 64 + 32 * wr + 16 * bi + kq * 4 + r;
-                if (row < n) d += is_term(fp[row] + (double)acc[bi][bj][r], y[row], Wv[row], zv[row]);
+                if (row < n) d += is_term<LIK>(fp[row] + (double)acc[bi][bj][r], y[row], Wv[row], zv[row]);
             }
         d += __shfl_xor(d, 16, 64);
         d += __shfl_xor(d, 32, 64);
@@ -271,6 +274,7 @@ __global__ __launch_bounds__(256) void k_ugemm(SlotSet S, const int64_t* __restr
 // the fp64 U buffer: where the entries of f_s are large (sigma = e^18.5: |f_s| ~ 1e4), the fp32
 // rounding of L and U alone moves log f by ~10 nats. Rare (extreme theta),
 // so plainly staged: 64x64 output tile per workgroup, L and U slices of 16 through LDS.
+template <int LIK>
 __global__ __launch_bounds__(256) void k_ugemm64(SlotSet S, const int64_t* __restrict__ slots,
                                                  UPool P, const int64_t* __restrict__ ubufs,
                                                  const double* __restrict__ y, int n, int np,
@@ -331,7 +335,7 @@ __global__ __launch_bounds__(256) void k_ugemm64(SlotSet S, const int64_t* __res
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = i * 64 + 32 * wr + 16 * bi + kq + 4 * r;
-                if (row < n) d += is_term(fp[row] + acc[bi][bj][r], y[row], Wv[row], zv[row]);
+                if (row < n) d += is_term<LIK>(fp[row] + acc[bi][bj][r], y[row], Wv[row], zv[row]);
             }
         d += __shfl_xor(d, 16, 64);
         d += __shfl_xor(d, 32, 64);
@@ -345,16 +349,18 @@ __global__ __launch_bounds__(256) void k_ugemm64(SlotSet S, const int64_t* __res
     if (tid < 64) pb[(int64_t)i * sp + sb * 64 + tid] = csum[0][tid] + csum[1][tid];
 }
 
-void launch_ugemm(SlotSet S, const int64_t* slots, UPool P, const int64_t* ubufs,
+void launch_ugemm(int lik, SlotSet S, const int64_t* slots, UPool P, const int64_t* ubufs,
                   const double* y, int n, int np, double* partial, int64_t pstride,
                   const int* status, int nchains, bool wide, hipStream_t s) {
     const int nb = np / 64, nsb = P.sp / 64;
     const long total = (long)nb * nsb * nchains;
-    APM_LAUNCH(k_ugemm, dim3((unsigned)total), dim3(256), 0, s, S, slots, P, ubufs, y, n,
-                       np, partial, pstride, status, nsb, nchains);
+    APM_LIK_DISPATCH(lik, APM_LAUNCH(k_ugemm<LIK>, dim3((unsigned)total), dim3(256), 0, s, S,
+                                     slots, P, ubufs, y, n, np, partial, pstride, status, nsb,
+                                     nchains));
     if (wide)
-        APM_LAUNCH(k_ugemm64, dim3((unsigned)(nb * nsb), nchains), dim3(256), 0, s, S,
-                           slots, P, ubufs, y, n, np, partial, pstride, status, nsb);
+        APM_LIK_DISPATCH(lik, APM_LAUNCH(k_ugemm64<LIK>, dim3((unsigned)(nb * nsb), nchains),
+                                         dim3(256), 0, s, S, slots, P, ubufs, y, n, np, partial,
+                                         pstride, status, nsb));
 }
 
 // logsumexp_s(lw_s) - log S per chain

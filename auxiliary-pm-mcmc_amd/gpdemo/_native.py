@@ -19,6 +19,8 @@ KERNEL_M32_ISO, KERNEL_M32_ARD, KERNEL_M52_ISO, KERNEL_M52_ARD = 3, 4, 5, 6
 # the kinds with one length scale (theta has 2 entries; the others' has d + 1)
 _ISO_KINDS = (KERNEL_ISO, KERNEL_M32_ISO, KERNEL_M52_ISO)
 EST_IS, EST_PRIORMC, EST_LAPLACE = 0, 1, 2
+LIK_PROBIT, LIK_LOGIT = 0, 1
+_LIKELIHOODS = {'probit': LIK_PROBIT, 'logit': LIK_LOGIT}
 APM_SUCCESS, APM_E_INVALID, APM_E_HIP, APM_E_NOMEM = 0, -1, -2, -3
 STATUS_OK, STATUS_CHOL_K, STATUS_CHOL_B, STATUS_CHOL_C, STATUS_MAXITER = 0, 1, 2, 3, 4
 STATUS_GUARD = 5
@@ -51,6 +53,8 @@ _SIGS = {
     'apm_padded_n': (_i64, [_p]),
     'apm_theta_len': (_i64, [_p]),
     'apm_set_newton': (_i, [_p, _d, _i64]),
+    'apm_set_likelihood': (_i, [_p, _i]),
+    'apm_likelihood': (_i, [_p]),
     'apm_stream': (_p, [_p]),
     'apm_u_upload': (_i, [_p, _i64, _p, _i64]),
     'apm_u_download': (_i, [_p, _i64, _p, _i64]),
@@ -69,6 +73,8 @@ _SIGS = {
     'apm_predict': (_i, [_p, _i64, _p, _i64, _p, _i64, _i64, _p, _p, _p, _i64, _p, _p]),
     'apm_laplace_grad': (_i, [_p, _i64, _p, _i64, _p, _p, _i64, _p, _p]),
     'apm_laplace': (_i, [_i, _p, _i64, _i64, _p, _i, _i, _d, _i64, _p, _p, _i64, _p, _p, _p]),
+    'apm_laplace_lik': (_i, [_i, _i, _p, _i64, _i64, _p, _i, _i, _d, _i64, _p, _p, _i64, _p, _p,
+                             _p]),
     'apm_prof_enable': (_i, [_p, _i]),
     'apm_prof_marker': (_i, [_p, _i]),
     'apm_prof_read': (_i, [_p, _i, _p, _p, _p, _i]),
@@ -121,6 +127,15 @@ def _check(rc, ctx=None):
         raise NativeError('libapm error {0}: {1}'.format(rc, msg.decode(errors='replace')))
 
 
+def likelihood_code(likelihood):
+    """APM_LIK_* of ``'probit'`` / ``'logit'``; anything else is a ValueError (raised before any
+    device is touched, so a misspelt likelihood never falls back to the probit)."""
+    try:
+        return _LIKELIHOODS[likelihood]
+    except (KeyError, TypeError):
+        raise ValueError("likelihood must be 'probit' or 'logit', got {0!r}".format(likelihood))
+
+
 def default_device():
     return int(os.environ.get('APM_DEVICE', os.environ.get('LOCAL_RANK', '0')))
 
@@ -166,7 +181,8 @@ def gram_cross(kind, X_test, X, theta, device=None):
     return Ks
 
 
-def laplace(K, y, calc_cov, calc_lml, diff_f_tol, max_iters, device=None):
+def laplace(K, y, calc_cov, calc_lml, diff_f_tol, max_iters, device=None, likelihood='probit'):
+    lik = likelihood_code(likelihood)
     lib = load_library()
     K = _f64(K)
     y = _f64(y)
@@ -176,9 +192,13 @@ def laplace(K, y, calc_cov, calc_lml, diff_f_tol, max_iters, device=None):
     lml = np.zeros(1)
     nit = np.zeros(1, dtype=np.int64)
     st = np.zeros(1, dtype=np.int32)
-    _check(lib.apm_laplace(default_device() if device is None else device, _ptr(K), n, n, _ptr(y),
-                           int(bool(calc_cov)), int(bool(calc_lml)), float(diff_f_tol),
-                           int(max_iters), _ptr(f), _ptr(C), n, _ptr(lml), _ptr(nit), _ptr(st)))
+    dev = default_device() if device is None else device
+    tail = (_ptr(K), n, n, _ptr(y), int(bool(calc_cov)), int(bool(calc_lml)), float(diff_f_tol),
+            int(max_iters), _ptr(f), _ptr(C), n, _ptr(lml), _ptr(nit), _ptr(st))
+    if lik == LIK_PROBIT:  # (the entry point the reference's function maps onto)
+        _check(lib.apm_laplace(dev, *tail))
+    else:
+        _check(lib.apm_laplace_lik(dev, lik, *tail))
     return f, C, float(lml[0]), int(nit[0]), int(st[0])
 
 
@@ -250,10 +270,13 @@ class _SlotPool(object):
 
 
 class Context(object):
-    """A device-resident problem (X, y, kernel) with workspaces for up to `max_batch` chains."""
+    """A device-resident problem (X, y, kernel, likelihood) with workspaces for up to
+    `max_batch` chains. The likelihood (``'probit'`` / ``'logit'``) is fixed for the context's
+    life: every cache slot it writes is read back under the same one."""
 
     def __init__(self, X, y, kernel_kind, epsilon, n_imp, max_batch=1, n_slots=4, n_ubufs=4,
-                 device=None):
+                 device=None, likelihood='probit'):
+        lik = likelihood_code(likelihood)
         lib = load_library()
         self.lib = lib
         self.device = default_device() if device is None else device
@@ -274,6 +297,9 @@ class Context(object):
         if not self._h:
             raise NativeError('apm_create failed: ' +
                               (lib.apm_global_error() or b'').decode(errors='replace'))
+        self.likelihood = likelihood
+        if lik != LIK_PROBIT:  # (the library's default)
+            _check(lib.apm_set_likelihood(self._h, lik), self._h)
         self.slots = _SlotPool(self)
         self.ubufs = _Pool(int(n_ubufs))
         # calls per batch size (bench.py reports the timed region's; launch shapes depend on it)

@@ -1,10 +1,13 @@
 # -*- coding: utf-8 -*-
-"""Estimators of log p(y | theta, X) for probit GP classification, evaluated on the MI355X.
+"""Estimators of log p(y | theta, X) for GP classification (probit or logit likelihood),
+evaluated on the MI355X.
 
 Drop-in for the reference's ``gpdemo/estimators.py``: the three classes keep their constructor
 arguments, ``__call__`` signatures, return values, ``n_cubic_ops`` accounting and exceptions.
 The work runs in libapm.so (include/apm.h) in fp64 (Gram, Newton/Laplace, Cholesky factors)
-with the importance-sampling product L.U in fp32 MFMA.
+with the importance-sampling product L.U in fp32 MFMA. ``likelihood=`` (not in
+the reference, which has the probit only) selects ``'probit'`` (default) or ``'logit'``
+(DESIGN.md §15).
 
 ``cached_results`` / ``K_chol`` become :class:`DeviceCache` handles: opaque references to a
 device-resident cache slot that is released when the handle is garbage-collected. Passing one
@@ -123,7 +126,9 @@ def _raise_for_status(status, ctx, n_iter_cap=1000):
 class _Problem(object):
     """Device contexts for one (X, y, kernel) problem, created lazily per number of draws."""
 
-    def __init__(self, X, y, kernel_func, n_slots=8):
+    def __init__(self, X, y, kernel_func, n_slots=8, likelihood='probit'):
+        _native.likelihood_code(likelihood)
+        self.likelihood = likelihood
         self.X = X
         self.y = np.asarray(y, dtype=np.float64)
         self.kind, self.eps = _kernel_spec(kernel_func)
@@ -138,17 +143,18 @@ class _Problem(object):
         c = self._ctxs.get(n_imp)
         if c is None:
             c = _native.Context(self.X, self.y, self.kind, self.eps, n_imp, max_batch=1,
-                                n_slots=self.n_slots, n_ubufs=1)
+                                n_slots=self.n_slots, n_ubufs=1, likelihood=self.likelihood)
             self._ctxs[n_imp] = c
         return c
 
 
 class _EstimatorBase(object):
-    def __init__(self, X, y, kernel_func):
+    def __init__(self, X, y, kernel_func, likelihood='probit'):
         self.X = X
         self.y = y
         self.kernel_func = kernel_func
-        self._prob = _Problem(X, y, kernel_func)
+        self.likelihood = likelihood
+        self._prob = _Problem(X, y, kernel_func, likelihood=likelihood)  # (ValueError if unknown)
         self._K = None if self._prob.device_gram else np.empty((X.shape[0], X.shape[0]))
         self.n_cubic_ops = 0
         _native.load_library()  # fail loudly here, not at the first call
@@ -180,14 +186,16 @@ class LogMarginalLikelihoodApproxPosteriorISEstimator(_EstimatorBase):
     """Unbiased importance-sampling estimate of p(y | theta, X) with the Laplace posterior as
     proposal (reference estimators.py:90-241). ``ns``: (n_data, n_imp_sample) N(0,1) draws."""
 
-    def __init__(self, X, y, kernel_func, post_approx_func):
+    def __init__(self, X, y, kernel_func, post_approx_func, likelihood='probit'):
+        _native.likelihood_code(likelihood)
         if not (getattr(post_approx_func, 'apm_fused', False) or
                 getattr(post_approx_func, '__name__', '') == 'laplace_approximation'):
             raise NotImplementedError(
                 'the device estimator fuses the Laplace approximation '
                 '(gpdemo.latent_posterior_approximations.laplace_approximation); got {0!r}'
                 .format(post_approx_func))
-        super(LogMarginalLikelihoodApproxPosteriorISEstimator, self).__init__(X, y, kernel_func)
+        super(LogMarginalLikelihoodApproxPosteriorISEstimator, self).__init__(
+            X, y, kernel_func, likelihood)
         self.post_approx_func = post_approx_func
 
     def __call__(self, ns, theta=None, cached_results=None):

@@ -1,6 +1,7 @@
 # -*- coding: utf-8 -*-
-"""Gradient of the Laplace log marginal likelihood of the probit GP classifier with respect to
-the kernel hyperparameters ``theta``, on the GPU.
+"""Gradient of the Laplace log marginal likelihood of the probit (or, with
+``likelihood='logit'``, logistic) GP classifier with respect to the kernel hyperparameters
+``theta``, on the GPU.
 
 ``LogMarginalLikelihoodLaplaceEstimator`` gives the Laplace approximation's log marginal
 likelihood at a ``theta``; :class:`LaplaceGradient` also says which way to move ``theta``: the
@@ -46,7 +47,8 @@ def add_gaussian_log_prior(thetas, lml, grad, prior_mean, prior_std):
 
 class LaplaceGradient(object):
     """Laplace log marginal likelihood and its gradient with respect to ``theta`` for the probit
-    GP classifier trained on ``(X, y)``, for batches of hyperparameter vectors.
+    (``likelihood='logit'``: logistic) GP classifier trained on ``(X, y)``, for batches of
+    hyperparameter vectors.
 
     ``kernel_func`` must be one of the two device kernels (``gpdemo.kernels.make_kernel_func``):
     the kernel's derivatives are built on the device, so a foreign callable raises
@@ -55,7 +57,9 @@ class LaplaceGradient(object):
     """
 
     def __init__(self, X, y, kernel_func, diff_f_tol=1e-14, max_iters=1000, max_batch=8,
-                 device=None):
+                 device=None, likelihood='probit'):
+        _native.likelihood_code(likelihood)
+        self.likelihood = likelihood
         kind, eps = _kernel_spec(kernel_func)
         if kind == _native.KERNEL_PRECOMPUTED:
             raise NotImplementedError(
@@ -67,7 +71,7 @@ class LaplaceGradient(object):
         self.max_iters = int(max_iters)
         # the gradient uses neither cache slots nor U buffers: one of each, one draw
         self._ctx = _native.Context(self.X, self.y, kind, eps, 1, max_batch=int(max_batch),
-                                    n_slots=1, n_ubufs=1, device=device)
+                                    n_slots=1, n_ubufs=1, device=device, likelihood=likelihood)
         self._ctx.set_newton(diff_f_tol, max_iters)
         self.n_iter = None
         self.status = None

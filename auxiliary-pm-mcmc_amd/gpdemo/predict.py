@@ -7,7 +7,10 @@ a test input ``x*`` the latent mean ``mu* = k*^T a``, the latent variance ``var*
 |L^-1 (W^1/2 . k*)|^2`` and the class probability ``pi* = Phi(mu* / sqrt(1 + var*))`` (Rasmussen
 & Williams, Alg. 3.2 with the probit's closed-form average). ``k*`` and ``k** = exp(theta_0)``
 carry no jitter: the reference's kernels add epsilon to the diagonal of one point set's Gram
-matrix only. The reference has no such function; everything runs in libapm.so (``apm_predict``,
+matrix only. With ``likelihood='logit'`` ``mu*`` and ``var*`` are the same expressions of the
+logit's Laplace fit and ``pi* = int sigma(x) N(x | mu*, var*) dx`` is a Gauss-Hermite average
+computed on the device. The reference has no such function; everything runs in
+libapm.so (``apm_predict``,
 DESIGN.md §12) and nothing but theta and the test inputs crosses the host boundary.
 
 :class:`LaplacePredictor` evaluates a set of theta samples (e.g. a saved run's, see
@@ -39,23 +42,36 @@ def posterior_average(prob, burn=0, thin=1):
     return _keep(prob, burn, thin).mean(0)
 
 
-def log_predictive_density(mean, var, y_test, burn=0, thin=1):
+def log_predictive_density(mean, var, y_test, burn=0, thin=1, likelihood='probit', prob=None):
     """Test log predictive density per point: the mean over the M test points of
     ``log(mean_t Phi(y* z_t))`` with ``z = mean / sqrt(1 + var)`` (T, M) and labels ``y*`` in
     {-1, +1}. ``log Phi`` through ``log_ndtr`` and a log-mean-exp over the samples, so that
-    confident predictions neither underflow to ``-inf`` nor round to 0."""
-    z = _keep(mean, burn, thin) / np.sqrt(1.0 + _keep(var, burn, thin))
+    confident predictions neither underflow to ``-inf`` nor round to 0. The logit's average has no
+    closed form: with ``likelihood='logit'`` the per-sample terms are ``log(prob)`` (y* = +1) and
+    ``log1p(-prob)`` (y* = -1) of the device's class probabilities ``prob`` (T, M), and ``mean``
+    / ``var`` are not read."""
+    _native.likelihood_code(likelihood)
     y = np.asarray(y_test, dtype=np.float64)
-    if y.shape != (z.shape[1],):
-        raise ValueError('y_test has shape {0}, expected ({1},)'.format(y.shape, z.shape[1]))
-    lp = log_ndtr(y[None, :] * z)
+    if likelihood == 'logit':
+        if prob is None:
+            raise ValueError("likelihood='logit' needs the device's prob")
+        p = _keep(prob, burn, thin)
+        if y.shape != (p.shape[1],):
+            raise ValueError('y_test has shape {0}, expected ({1},)'.format(y.shape, p.shape[1]))
+        with np.errstate(divide='ignore'):
+            lp = np.where(y[None, :] > 0, np.log(p), np.log1p(-p))
+    else:
+        z = _keep(mean, burn, thin) / np.sqrt(1.0 + _keep(var, burn, thin))
+        if y.shape != (z.shape[1],):
+            raise ValueError('y_test has shape {0}, expected ({1},)'.format(y.shape, z.shape[1]))
+        lp = log_ndtr(y[None, :] * z)
     top = lp.max(0)
     return float(np.mean(top + np.log(np.mean(np.exp(lp - top[None, :]), axis=0))))
 
 
 class LaplacePredictor(object):
-    """Predictive distribution at ``X_test`` (M, D) of the probit GP classifier trained on
-    ``(X, y)``, for batches of hyperparameter samples.
+    """Predictive distribution at ``X_test`` (M, D) of the GP classifier (``likelihood='probit'``
+    or ``'logit'``) trained on ``(X, y)``, for batches of hyperparameter samples.
 
     ``kernel_func`` must be one of the two device kernels (``gpdemo.kernels.make_kernel_func``):
     the cross-covariance is built on the device, so a foreign callable raises
@@ -64,7 +80,9 @@ class LaplacePredictor(object):
     """
 
     def __init__(self, X, y, kernel_func, X_test, diff_f_tol=1e-4, max_iters=1000, max_batch=8,
-                 device=None):
+                 device=None, likelihood='probit'):
+        _native.likelihood_code(likelihood)
+        self.likelihood = likelihood
         kind, eps = _kernel_spec(kernel_func)
         if kind == _native.KERNEL_PRECOMPUTED:
             raise NotImplementedError(
@@ -80,7 +98,7 @@ class LaplacePredictor(object):
         self.max_iters = int(max_iters)
         # prediction uses neither cache slots nor U buffers: one of each, one draw
         self._ctx = _native.Context(self.X, self.y, kind, eps, 1, max_batch=int(max_batch),
-                                    n_slots=1, n_ubufs=1, device=device)
+                                    n_slots=1, n_ubufs=1, device=device, likelihood=likelihood)
         self._ctx.set_newton(diff_f_tol, max_iters)
         self.n_iter = None
 
@@ -107,8 +125,8 @@ class LaplacePredictor(object):
     def log_predictive_density(self, thetas, y_test, burn=0, thin=1, on_error='raise'):
         """Mean test log predictive density of labels ``y_test`` (M,) in {-1, +1}."""
         th = np.atleast_2d(np.asarray(thetas, dtype=np.float64))[int(burn)::int(thin)]
-        mean, var, _ = self(th, on_error)
-        return log_predictive_density(mean, var, y_test)
+        mean, var, prob = self(th, on_error)
+        return log_predictive_density(mean, var, y_test, likelihood=self.likelihood, prob=prob)
 
     def close(self):
         self._ctx.close()

@@ -83,10 +83,15 @@ def log_prior_ard_batch(thetas, prior):
     return lp
 
 
-def synthetic_gp_data(n, d, seed, kind='ard', jitter=1e-6):
+def synthetic_gp_data(n, d, seed, kind='ard', jitter=1e-6, likelihood='probit'):
     """Synthetic probit GP-classification data (SURVEY.md §8d): X ~ N(0,1) then normalised;
     y = sign(f*) with f* a GP prior draw at log sigma = 0, log tau_k = log sqrt(d). The prior
-    draw uses the numpy Cholesky on the host (data preparation, not the hot path)."""
+    draw uses the numpy Cholesky on the host (data preparation, not the hot path).
+    ``likelihood='logit'`` draws the labels of a logistic model instead: y = +1 with probability
+    sigma(f*) (n more uniform draws from the same stream, after f*; X and f* are the probit
+    call's)."""
+    if likelihood not in ('probit', 'logit'):
+        raise ValueError("likelihood must be 'probit' or 'logit', got {0!r}".format(likelihood))
     rng = np.random.RandomState(seed)
     X, _, _ = normalise_inputs(rng.normal(size=(n, d)))
     tau = np.sqrt(d)
@@ -96,6 +101,8 @@ def synthetic_gp_data(n, d, seed, kind='ard', jitter=1e-6):
         s += diff ** 2
     K = np.exp(-0.5 * s) + jitter * np.eye(n)
     f = np.linalg.cholesky(K).dot(rng.normal(size=n))
+    if likelihood == 'logit':
+        return X, np.where(rng.uniform(size=n) < 1. / (1. + np.exp(-f)), 1., -1.)
     y = np.where(f >= 0, 1., -1.)
     return X, y
 

@@ -77,9 +77,20 @@ extern "C" {
 #define APM_EST_PRIORMC 1  /* LogMarginalLikelihoodPriorMCEstimator */
 #define APM_EST_LAPLACE 2  /* LogMarginalLikelihoodLaplaceEstimator */
 
+/* likelihoods p(y | f) of a label y in {-1, +1} (R&W §3.4; the reference has the probit only):
+ *   PROBIT  Phi(y f)     the default of every context and of apm_laplace
+ *   LOGIT   sigma(y f) = 1 / (1 + exp(-y f)); with t = y f:
+ *           log p = -log1p(exp(-t)) (t >= 0), t - log1p(exp(t)) (t < 0),
+ *           grad = d log p/df = y sigma(-t), W = -d^2 log p/df^2 = sigma(t) sigma(-t) in (0, 1/4],
+ *           d3 = d^3 log p/df^3 = -y W (1 - 2 sigma(t)); sigma(-t) is formed as 1/(1 + exp(t)),
+ *           never as 1 - sigma(t). */
+#define APM_LIK_PROBIT 0
+#define APM_LIK_LOGIT 1
+
 typedef struct apm_ctx apm_ctx;
 
-/* 2: the Matern kinds APM_KERNEL_M32_* / APM_KERNEL_M52_* (1: SE and PRECOMPUTED only) */
+/* 3: the likelihoods APM_LIK_* (apm_set_likelihood, apm_laplace_lik); 2: the Matern kinds
+ * APM_KERNEL_M32_* / APM_KERNEL_M52_* (1: SE and PRECOMPUTED only) */
 int apm_version(void);
 int apm_device_count(void);
 const char *apm_global_error(void);
@@ -94,6 +105,16 @@ int64_t apm_padded_n(const apm_ctx *ctx);
 int64_t apm_theta_len(const apm_ctx *ctx);
 /* Newton settings of laplace_approximation (diff_f_tol, max_iters); defaults 1e-4, 1000 */
 int apm_set_newton(apm_ctx *ctx, double diff_f_tol, int64_t max_iters);
+/* The likelihood (APM_LIK_*; default APM_LIK_PROBIT) of every later call on the context:
+ * apm_theta_eval (all three estimators), apm_theta_eval_K, apm_u_eval, apm_predict and
+ * apm_laplace_grad. APM_E_INVALID for an unknown value. A cache slot holds the state of the
+ * likelihood it was written under (W, z and cst of that likelihood's Laplace fit): reading it
+ * with apm_u_eval under the other one is the caller's error and is not detected. The IS estimate
+ * log w_s = sum_n [log p(y_n|f_sn) + 1/2 W_n f_sn^2 - z_n f_sn] + cst holds for either likelihood
+ * (W the one the proposal was built from); PriorMC is the same with W = z = 0. */
+int apm_set_likelihood(apm_ctx *ctx, int lik);
+/* the context's likelihood (negative on a null context) */
+int apm_likelihood(const apm_ctx *ctx);
 /* hipStream_t the context launches on (for device-side timing by the caller) */
 void *apm_stream(apm_ctx *ctx);
 
@@ -125,6 +146,13 @@ int apm_theta_eval_K(apm_ctx *ctx, int estimator, const double *K, int64_t ldk, 
  * mean = k*^T a, var = s - |L^-1 (W^1/2 . k*)|^2 with s = exp(theta_0) (no epsilon on k* or k**:
  * kernels.pyx adds it to the diagonal of one point set's Gram only), prob = Phi(mean /
  * sqrt(1 + var)); W, L, a of the last Newton iteration (lpa.py:81-112). Nothing is clamped.
+ * Under APM_LIK_LOGIT mean and var are the same expressions (with the logit's W, L, a) and prob
+ * = int sigma(x) N(x | mean, var) dx has no closed form: it is the Gauss-Hermite average
+ * sum_q w_q sigma(mean + sqrt(2 var) x_q) over the 400-node rule (its 128 central nodes; the
+ * others carry 3e-24 of the weight), summed in pairs +-x_q in a fixed order, so that mean = 0
+ * gives 0.5 bitwise. The rule is exact to 1e-12 for var <= 20 and to 2e-6 for var <= 100; at var
+ * = e^6 it is 4e-4 off. var <= 0 is returned as computed, and prob is then
+ * sigma(mean).
  * Uses the context's work matrix like every theta-call; cache slots are not touched. */
 int apm_predict(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ldt,
                 const double *Xs, int64_t m, int64_t ldxs, double *mean, double *var,
@@ -144,7 +172,9 @@ int apm_predict(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ldt,
  * tau_k)^2 (ARD) or the sum over k of these (ISO); K = S + epsilon I everywhere else. For a
  * Matern kind the length-scale derivative is G_ik ((x_ik - x_jk) / tau_k)^2 with G = 3 s
  * exp(-sqrt3 r) (3/2) or G = 5/3 s (1 + sqrt5 r) exp(-sqrt5 r) (5/2): finite at r = 0, zero
- * diagonal; dK/dtheta_0 = S as for SE. This is the
+ * diagonal; dK/dtheta_0 = S as for SE. Under APM_LIK_LOGIT the same formulas hold with the
+ * logit's g = y sigma(-y f) and d3 = -y W (1 - 2 sigma(y f)), W = sigma(y f) sigma(-y f) (and
+ * the logit's W, L, a, f). This is the
  * derivative at the exact mode: at a loose diff_f_tol it is approximate.
  * lml[i] is bitwise the value apm_theta_eval(APM_EST_LAPLACE) returns for the same theta and
  * Newton settings: that call always takes this fp64 Newton path, so no setting is needed.
@@ -182,6 +212,11 @@ int apm_gram_cross(int device, int kernel_kind, const double *Xs, int64_t m, con
 int apm_laplace(int device, const double *K, int64_t n, int64_t ldk, const double *y,
                 int calc_cov, int calc_lml, double diff_f_tol, int64_t max_iters, double *f_out,
                 double *C_out, int64_t ldc, double *lml_out, int64_t *n_iter_out, int *status);
+/* the same under likelihood lik (APM_LIK_*); apm_laplace is apm_laplace_lik(APM_LIK_PROBIT) */
+int apm_laplace_lik(int device, int lik, const double *K, int64_t n, int64_t ldk, const double *y,
+                    int calc_cov, int calc_lml, double diff_f_tol, int64_t max_iters,
+                    double *f_out, double *C_out, int64_t ldc, double *lml_out,
+                    int64_t *n_iter_out, int *status);
 
 /* ---- device-time accounting of the hot kernels (HIP events on the context stream) ------------ */
 #define APM_PROF_GRAM 0
