@@ -7,6 +7,7 @@
 //   host_newton.cpp   fp32 Newton factorisation with its lookahead, the Newton loop, fp64 rerun
 //   host_theta.cpp    the theta-call: concurrent chol(K), posterior factor, guard, ICM check
 //   host_laplace.cpp  apm_laplace's covariance, the predictive and gradient paths
+//   host_ep.cpp       the sweep loop of parallel expectation propagation (ep.hip)
 // Everything shared has hidden visibility: the library exports the apm_* functions only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -237,6 +238,11 @@ struct __attribute__((visibility("hidden"))) apm_ctx {
     // (dS, g, s2, t = K s2, u = -R t, q; max_batch x np each), the super-tile partials
     // (max_batch x ns (ns + 1) / 2 x P) and the gradients (max_batch x P)
     double *gvec = nullptr, *gpart = nullptr, *gout = nullptr;
+    // expectation propagation (apm_ep_eval / apm_ep_predict / apm_ep): the settings of apm_set_ep
+    // and the site and scratch vectors (EpVecs), allocated at the first EP call
+    double ep_damping = 0.8, ep_tol = 1e-8;
+    int64_t ep_max_sweeps = 100;
+    EpVecs ep{};
 };
 
 namespace apm_host __attribute__((visibility("hidden"))) {
@@ -408,5 +414,14 @@ void predict_buffers(apm_ctx* c);
 void predict_block(apm_ctx* c, int count, const double* xs, int ms);
 void grad_buffers(apm_ctx* c);
 void grad_block(apm_ctx* c, int count);
+
+// ---- host_ep.cpp ----------------------------------------------------------------------------
+void ep_buffers(apm_ctx* c);
+// Parallel EP on K as it stands in c->K (k_full says which triangles) for chains
+// [0, count): sets the liveness arrays, runs the sweeps and leaves each converged chain's state
+// of its last sweep in place (sites, var and logz in c->ep; S^1/2 in v.Ws, a in v.a, mu in v.f,
+// the factor in A / Dinv / ldet); host status per chain in st_h, sweeps in c->n_iter. The OK
+// chains are live again on return (active = 1), as after laplace_then_live; returns their number
+int ep_fit(apm_ctx* c, int count, std::vector<int>& st_h);
 
 }  // namespace apm_host

@@ -339,6 +339,32 @@ void launch_laplace_lml(int lik, NewtonVecs v, const double* y, int n, const dou
                         int64_t lstride, int nb, double* out, Live live, int nchains,
                         hipStream_t s);
 
+// ---- ep.hip: parallel expectation propagation for the probit ----------------
+struct EpVecs {         // all per chain, stride `stride` (>= np), but logz (one per chain)
+    double* tau;        // site precisions tau~ (zero for rows >= n)
+    double* nu;         // site precision-means nu~
+    double* ctau;       // the damped candidates of the current sweep
+    double* cnu;
+    double* var;        // marginal variances sigma^2 of the current sweep
+    double* lz;         // the rows' terms of log Z_EP
+    double* dm;         // (mu - mu_prev)^2
+    double* logz;       // log Z_EP of a converged chain
+    int* bad;           // the row's cavity precision was <= 0 or not finite
+    int64_t stride;
+};
+// W = tau~, W^1/2 = sqrt(tau~) and b = nu~ into the Newton vectors
+void launch_ep_prep(EpVecs e, NewtonVecs v, int np, Live live, int nchains, hipStream_t s);
+// per chain and row r < n, from row np + r of A over columns [0, 64 nb) (the solved row of V^T),
+// K_rr, mu = v.fnew and mu_prev = v.f: var, the damped candidate sites, lz, dm and bad
+void launch_ep_sites(MatB A, MatB K, int n, int nb, NewtonVecs v, const double* y, EpVecs e,
+                     double damping, Live live, int nchains, hipStream_t s);
+// per live chain: n_iter += 1; a bad cavity -> status = fail_code; from the second sweep on
+// mean(dm) < diff_tol -> logz = sum lz - sum ldet[0, nb), active = 0; else the candidates become
+// the sites; v.f <- v.fnew
+void launch_ep_chain(EpVecs e, NewtonVecs v, int n, int np, const double* ldet, int64_t lstride,
+                     int nb, double diff_tol, int fail_code, int* active, int* status,
+                     int* n_iter, int nchains, hipStream_t s);
+
 // cache slot: fp32 factor with an extra TB-row block (row np holds g^T for apm_slot_read; the
 // estimate does not use it), plus fp64 vectors of the self-consistent epilogue (ugemm.hip)
 struct SlotSet {

@@ -34,6 +34,64 @@ bool check_idx(apm_ctx* c, int64_t count, const int64_t* idx, int64_t lim, const
 std::mutex g_mu;
 std::map<std::tuple<int, int64_t, int64_t, int>, apm_ctx*> g_cache;
 
+// the predictive distribution of the live chains' state (S^1/2 or W^1/2 in v.Ws, a, the factor in
+// A) at the m test inputs, in blocks of the free rows of A; outputs count x m, row stride ldo
+void predict_all(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, const double* Xs,
+                 int64_t m, int64_t ldxs, double* mean, double* var, double* prob, int64_t ldo) {
+    predict_buffers(c);
+    std::vector<double> xs, sig((size_t)count);  // (alive until the blocks' syncs)
+    for (int64_t b = 0; b < count; ++b) sig[b] = std::exp(thetas[b * ldt]);
+    HIPC(hipMemcpyAsync(c->psig, sig.data(), sizeof(double) * count, hipMemcpyHostToDevice,
+                        c->stream));
+    for (int64_t r0 = 0; r0 < m; r0 += c->np) {
+        const int ms = (int)std::min<int64_t>(c->np, m - r0);
+        xs.resize((size_t)ms * c->d);
+        for (int i = 0; i < ms; ++i)
+            for (int k = 0; k < c->d; ++k) xs[(size_t)i * c->d + k] = Xs[(r0 + i) * ldxs + k];
+        predict_block(c, (int)count, xs.data(), ms);
+        const std::pair<double*, const double*> outs[3] = {
+            {mean, c->pmean}, {var, c->pvar}, {prob, c->pprob}};
+        for (const auto& o : outs)
+            if (o.first)
+                HIPC(hipMemcpy2DAsync(o.first + r0, sizeof(double) * ldo, o.second,
+                                      sizeof(double) * c->np, sizeof(double) * ms, count,
+                                      hipMemcpyDeviceToHost, c->stream));
+        sync(c);  // (xs is reused by the next block)
+    }
+}
+
+// the cached PRECOMPUTED context of a stand-alone call's shape (apm_laplace_lik, apm_ep), created
+// at the first call and given the call's labels
+void standalone_ctx(apm_ctx*& c, int device, int64_t n, const double* y) {
+    if (!c) {
+        c = new apm_ctx();
+        init_ctx(c, device, APM_KERNEL_PRECOMPUTED, nullptr, n, 0, 0, y, 1e-8, 1, 1, 1, 1);
+    } else {
+        HIPC(hipSetDevice(device));
+        std::vector<double> yp((size_t)c->np, 0.0);
+        for (int64_t i = 0; i < n; ++i) yp[i] = y[i];
+        HIPC(hipMemcpyAsync(c->y, yp.data(), sizeof(double) * c->np, hipMemcpyHostToDevice,
+                            c->stream));
+    }
+}
+
+// C = K - V^T V of chain 0's last factor (augmented(): the bottom-right of A, lower) -> both
+// triangles of C_out (n x n, ldc)
+void covariance_out(apm_ctx* c, double* C_out, int64_t ldc) {
+    const int np = c->np;
+    augmented(c, 1);
+    std::vector<double> Cb((size_t)np * np);
+    HIPC(hipMemcpy2DAsync(Cb.data(), sizeof(double) * np, c->A.base + (int64_t)np * c->A.ld + np,
+                          sizeof(double) * c->A.ld, sizeof(double) * np, np,
+                          hipMemcpyDeviceToHost, c->stream));
+    sync(c);
+    for (int64_t i = 0; i < c->n; ++i)
+        for (int64_t j = 0; j <= i; ++j) {
+            C_out[i * ldc + j] = Cb[(size_t)i * np + j];
+            C_out[j * ldc + i] = Cb[(size_t)i * np + j];
+        }
+}
+
 }  // namespace
 
 // =============================================================================== C-ABI
@@ -420,26 +478,7 @@ int apm_predict(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, co
         upload_thetas(c, count, thetas, ldt);
         std::vector<double> lml((size_t)count);
         if (laplace_then_live(c, (int)count, lml.data(), status, n_iter)) {
-            predict_buffers(c);
-            std::vector<double> xs, sig((size_t)count);  // (alive until the blocks' syncs)
-            for (int64_t b = 0; b < count; ++b) sig[b] = std::exp(thetas[b * ldt]);
-            HIPC(hipMemcpyAsync(c->psig, sig.data(), sizeof(double) * count, hipMemcpyHostToDevice,
-                                c->stream));
-            for (int64_t r0 = 0; r0 < m; r0 += c->np) {  // blocks of the free rows of A
-                const int ms = (int)std::min<int64_t>(c->np, m - r0);
-                xs.resize((size_t)ms * c->d);
-                for (int i = 0; i < ms; ++i)
-                    for (int k = 0; k < c->d; ++k) xs[(size_t)i * c->d + k] = Xs[(r0 + i) * ldxs + k];
-                predict_block(c, (int)count, xs.data(), ms);
-                const std::pair<double*, const double*> outs[3] = {
-                    {mean, c->pmean}, {var, c->pvar}, {prob, c->pprob}};
-                for (const auto& o : outs)
-                    if (o.first)
-                        HIPC(hipMemcpy2DAsync(o.first + r0, sizeof(double) * ldo, o.second,
-                                              sizeof(double) * c->np, sizeof(double) * ms, count,
-                                              hipMemcpyDeviceToHost, c->stream));
-                sync(c);  // (xs is reused by the next block)
-            }
+            predict_all(c, count, thetas, ldt, Xs, m, ldxs, mean, var, prob, ldo);
         }
         const double nan = std::numeric_limits<double>::quiet_NaN();
         for (int64_t b = 0; b < count; ++b)
@@ -507,20 +546,10 @@ int apm_laplace_lik(int device, int lik, const double* K, int64_t n, int64_t ldk
     auto key = std::make_tuple(device, n, (int64_t)0, (int)APM_KERNEL_PRECOMPUTED);
     apm_ctx*& c = g_cache[key];
     try {
-        if (!c) {
-            c = new apm_ctx();
-            init_ctx(c, device, APM_KERNEL_PRECOMPUTED, nullptr, n, 0, 0, y, 1e-8, 1, 1, 1, 1);
-        } else {
-            HIPC(hipSetDevice(device));
-            std::vector<double> yp((size_t)c->np, 0.0);
-            for (int64_t i = 0; i < n; ++i) yp[i] = y[i];
-            HIPC(hipMemcpyAsync(c->y, yp.data(), sizeof(double) * c->np, hipMemcpyHostToDevice,
-                                c->stream));
-        }
+        standalone_ctx(c, device, n, y);
         c->tol = diff_f_tol;
         c->max_iters = max_iters;
         c->lik = lik;  // (the shape's cached context serves both likelihoods)
-        const int np = c->np;
         std::vector<double> Kp;  // (alive until the syncs below)
         upload_padded_K(c, K, ldk, Kp);
         HIPC(hipMemsetD32Async(c->active, 1, 1, c->stream));
@@ -542,17 +571,189 @@ int apm_laplace_lik(int device, int lik, const double* K, int64_t n, int64_t ldk
             HIPC(hipMemcpyAsync(lml_out, c->out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
         }
         if (calc_cov) {
-            augmented(c, 1);  // bottom-right of A now holds C = K - V^T V (lower)
-            std::vector<double> Cb((size_t)np * np);
-            HIPC(hipMemcpy2DAsync(Cb.data(), sizeof(double) * np,
-                                  c->A.base + (int64_t)np * c->A.ld + np, sizeof(double) * c->A.ld,
-                                  sizeof(double) * np, np, hipMemcpyDeviceToHost, c->stream));
-            sync(c);
-            for (int64_t i = 0; i < n; ++i)
-                for (int64_t j = 0; j <= i; ++j) {
-                    C_out[i * ldc + j] = Cb[(size_t)i * np + j];
-                    C_out[j * ldc + i] = Cb[(size_t)i * np + j];
-                }
+            covariance_out(c, C_out, ldc);
+        }
+        sync(c);
+    } catch (const HipError& e) {
+        if (c) {
+            free_ctx(c);
+            c = nullptr;
+        }
+        return fail(nullptr, APM_E_HIP, e.msg);
+    }
+    return APM_SUCCESS;
+}
+
+// ---- expectation propagation (host_ep.cpp) -----------------------------------
+namespace {
+
+bool ep_settings_ok(double damping, double diff_tol, int64_t max_sweeps) {
+    return damping > 0.0 && damping <= 1.0 && diff_tol >= 0.0 && max_sweeps >= 1;
+}
+
+// the Gram of the call's thetas (K's lower tiles, as a Laplace theta-call) and the EP fit
+int ep_gram_fit(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt,
+                std::vector<int>& st_h) {
+    upload_thetas(c, count, thetas, ldt);
+    HIPC(hipMemsetD32Async(c->active, 1, count, c->stream));
+    HIPC(hipMemsetAsync(c->status, 0, sizeof(int) * count, c->stream));
+    c->k_full = false;
+    launch_gram(c->K, c->X, c->d, c->n, c->d, c->theta, c->P, c->kind, c->eps, c->np, live_of(c),
+                (int)count, c->stream, /*both=*/false);
+    return ep_fit(c, (int)count, st_h);
+}
+
+// count x n device vectors (row stride src_ld) -> host rows (row stride ldo), if asked for
+void ep_fetch(apm_ctx* c, double* dst, int64_t ldo, const double* src, int64_t src_ld,
+              int64_t count) {
+    if (dst)
+        HIPC(hipMemcpy2DAsync(dst, sizeof(double) * ldo, src, sizeof(double) * src_ld,
+                              sizeof(double) * c->n, count, hipMemcpyDeviceToHost, c->stream));
+}
+
+}  // namespace
+
+int apm_set_ep(apm_ctx* ctx, double damping, double diff_tol, int64_t max_sweeps) {
+    if (!ctx || !ep_settings_ok(damping, diff_tol, max_sweeps))
+        return fail(ctx, APM_E_INVALID, "apm_set_ep: bad arguments");
+    if (ctx->lik != APM_LIK_PROBIT)
+        return fail(ctx, APM_E_INVALID, "apm_set_ep: probit only (the logit's tilted moments need "
+                                        "quadrature)");
+    ctx->ep_damping = damping;
+    ctx->ep_tol = diff_tol;
+    ctx->ep_max_sweeps = max_sweeps;
+    return APM_SUCCESS;
+}
+
+int apm_ep_eval(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, double* logz,
+                double* mu, double* var, double* tau, double* nu, int64_t ldo, int* status,
+                int64_t* n_sweeps) {
+    if (!c) return fail(nullptr, APM_E_INVALID, "apm_ep_eval: null context");
+    if (c->lik != APM_LIK_PROBIT)
+        return fail(c, APM_E_INVALID, "apm_ep_eval: probit only (the logit's tilted moments need "
+                                      "quadrature)");
+    if (c->kind == APM_KERNEL_PRECOMPUTED)
+        return fail(c, APM_E_INVALID, "apm_ep_eval: needs an ISO or ARD context (apm_ep takes a "
+                                      "K of the caller's)");
+    if (count <= 0 || count > c->max_batch)
+        return fail(c, APM_E_INVALID, "apm_ep_eval: count outside [1, max_batch]");
+    if (!thetas || !status || ldt < c->P || ((mu || var || tau || nu) && ldo < c->n))
+        return fail(c, APM_E_INVALID, "apm_ep_eval: bad arguments");
+    const SkewScope skew(c);
+    try {
+        HIPC(hipSetDevice(c->device));
+        std::vector<int> st_h;
+        ep_gram_fit(c, count, thetas, ldt, st_h);
+        std::vector<int> it_h((size_t)count);
+        std::vector<double> lz((size_t)count);
+        HIPC(hipMemcpyAsync(it_h.data(), c->n_iter, sizeof(int) * count, hipMemcpyDeviceToHost,
+                            c->stream));
+        HIPC(hipMemcpyAsync(lz.data(), c->ep.logz, sizeof(double) * count, hipMemcpyDeviceToHost,
+                            c->stream));
+        ep_fetch(c, mu, ldo, c->v.f, c->v.vstride, count);
+        ep_fetch(c, var, ldo, c->ep.var, c->ep.stride, count);
+        ep_fetch(c, tau, ldo, c->ep.tau, c->ep.stride, count);
+        ep_fetch(c, nu, ldo, c->ep.nu, c->ep.stride, count);
+        sync(c);
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        for (int64_t b = 0; b < count; ++b) {
+            status[b] = st_h[b];
+            if (n_sweeps) n_sweeps[b] = it_h[b];
+            const bool good = st_h[b] == APM_STATUS_OK;
+            if (logz) logz[b] = good ? lz[b] : nan;
+            if (!good)
+                for (double* o : {mu, var, tau, nu})
+                    if (o) std::fill(o + b * ldo, o + b * ldo + c->n, nan);
+        }
+    } catch (const HipError& e) {
+        return fail(c, APM_E_HIP, e.msg);
+    }
+    return APM_SUCCESS;
+}
+
+int apm_ep_predict(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, const double* Xs,
+                   int64_t m, int64_t ldxs, double* mean, double* var, double* prob, int64_t ldo,
+                   int* status, int64_t* n_sweeps) {
+    if (!c) return fail(nullptr, APM_E_INVALID, "apm_ep_predict: null context");
+    if (c->lik != APM_LIK_PROBIT)
+        return fail(c, APM_E_INVALID, "apm_ep_predict: probit only (the logit's tilted moments "
+                                      "need quadrature)");
+    if (c->kind == APM_KERNEL_PRECOMPUTED)
+        return fail(c, APM_E_INVALID, "apm_ep_predict: needs an ISO or ARD context (the cross-"
+                                      "covariance is built on the device)");
+    if (m <= 0) return fail(c, APM_E_INVALID, "apm_ep_predict: m <= 0");
+    if (count <= 0 || count > c->max_batch)
+        return fail(c, APM_E_INVALID, "apm_ep_predict: count outside [1, max_batch]");
+    if (ldo < m) return fail(c, APM_E_INVALID, "apm_ep_predict: ldo < m");
+    if (!thetas || !Xs || !status || ldt < c->P || ldxs < c->d)
+        return fail(c, APM_E_INVALID, "apm_ep_predict: bad arguments");
+    const SkewScope skew(c);
+    try {
+        HIPC(hipSetDevice(c->device));
+        std::vector<int> st_h;
+        const int ok = ep_gram_fit(c, count, thetas, ldt, st_h);
+        std::vector<int> it_h((size_t)count);
+        HIPC(hipMemcpyAsync(it_h.data(), c->n_iter, sizeof(int) * count, hipMemcpyDeviceToHost,
+                            c->stream));
+        sync(c);
+        if (ok) {  // predict_block reads S^1/2 (v.Ws), a and the factor of each chain's last sweep
+            predict_all(c, count, thetas, ldt, Xs, m, ldxs, mean, var, prob, ldo);
+        }
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        for (int64_t b = 0; b < count; ++b) {
+            status[b] = st_h[b];
+            if (n_sweeps) n_sweeps[b] = it_h[b];
+            if (st_h[b] != APM_STATUS_OK)
+                for (double* o : {mean, var, prob})
+                    if (o) std::fill(o + b * ldo, o + b * ldo + m, nan);
+        }
+    } catch (const HipError& e) {
+        return fail(c, APM_E_HIP, e.msg);
+    }
+    return APM_SUCCESS;
+}
+
+int apm_ep(int device, const double* K, int64_t n, int64_t ldk, const double* y, int calc_cov,
+           double damping, double diff_tol, int64_t max_sweeps, double* mu_out, double* var_out,
+           double* tau_out, double* nu_out, double* C_out, int64_t ldc, double* logz_out,
+           int64_t* n_sweeps_out, int* status) {
+    if (!K || !y || n <= 0 || ldk < n || !status || !ep_settings_ok(damping, diff_tol, max_sweeps) ||
+        (calc_cov && (!C_out || ldc < n)))
+        return fail(nullptr, APM_E_INVALID, "apm_ep: bad arguments");
+    std::lock_guard<std::mutex> lk(g_mu);
+    auto key = std::make_tuple(device, n, (int64_t)0, (int)APM_KERNEL_PRECOMPUTED);
+    apm_ctx*& c = g_cache[key];  // (apm_laplace's cached context of the shape)
+    try {
+        standalone_ctx(c, device, n, y);
+        c->ep_damping = damping;
+        c->ep_tol = diff_tol;
+        c->ep_max_sweeps = max_sweeps;
+        c->lik = APM_LIK_PROBIT;  // (augmented() and the shared kernels read it)
+        std::vector<double> Kp;  // (alive until the syncs below)
+        upload_padded_K(c, K, ldk, Kp);
+        std::vector<int> st;
+        ep_fit(c, 1, st);
+        int it = 0;
+        HIPC(hipMemcpyAsync(&it, c->n_iter, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        sync(c);
+        *status = st[0];
+        if (n_sweeps_out) *n_sweeps_out = it;
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        if (st[0] != APM_STATUS_OK) {
+            if (logz_out) *logz_out = nan;
+            for (double* o : {mu_out, var_out, tau_out, nu_out})
+                if (o) std::fill(o, o + n, nan);
+            return APM_SUCCESS;
+        }
+        if (logz_out)
+            HIPC(hipMemcpyAsync(logz_out, c->ep.logz, sizeof(double), hipMemcpyDeviceToHost,
+                                c->stream));
+        ep_fetch(c, mu_out, n, c->v.f, c->v.vstride, 1);
+        ep_fetch(c, var_out, n, c->ep.var, c->ep.stride, 1);
+        ep_fetch(c, tau_out, n, c->ep.tau, c->ep.stride, 1);
+        ep_fetch(c, nu_out, n, c->ep.nu, c->ep.stride, 1);
+        if (calc_cov) {
+            covariance_out(c, C_out, ldc);
         }
         sync(c);
     } catch (const HipError& e) {

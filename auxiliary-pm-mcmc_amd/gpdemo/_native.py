@@ -24,10 +24,11 @@ _LIKELIHOODS = {'probit': LIK_PROBIT, 'logit': LIK_LOGIT}
 APM_SUCCESS, APM_E_INVALID, APM_E_HIP, APM_E_NOMEM = 0, -1, -2, -3
 STATUS_OK, STATUS_CHOL_K, STATUS_CHOL_B, STATUS_CHOL_C, STATUS_MAXITER = 0, 1, 2, 3, 4
 STATUS_GUARD = 5
+STATUS_EP_CAVITY = 6
 PROF_GRAM, PROF_CHOL_UPDATE, PROF_UGEMM, PROF_CHOL_UPDATE32, PROF_STATS = 0, 1, 2, 3, 4
 PROF_CHOL_UPDATE32_OUTER, PROF_CHOL_UPDATE_OUTER, PROF_DF_TIMEOUTS = 5, 6, 7
 PROF_POST32_OUTER, PROF_POST64_RERUNS, PROF_TRSV_TIMEOUTS = 8, 9, 10
-PROF_ICM_CHECKS, PROF_GUARD, PROF_GRAD_REDUCE, PROF_NKINDS = 11, 12, 13, 14
+PROF_ICM_CHECKS, PROF_GUARD, PROF_GRAD_REDUCE, PROF_EP_SITES, PROF_NKINDS = 11, 12, 13, 14, 15
 
 
 class NativeUnavailableError(RuntimeError):
@@ -72,6 +73,11 @@ _SIGS = {
     'apm_gram_cross': (_i, [_i, _i, _p, _i64, _p, _i64, _i64, _i64, _p, _i64, _p, _i64]),
     'apm_predict': (_i, [_p, _i64, _p, _i64, _p, _i64, _i64, _p, _p, _p, _i64, _p, _p]),
     'apm_laplace_grad': (_i, [_p, _i64, _p, _i64, _p, _p, _i64, _p, _p]),
+    'apm_set_ep': (_i, [_p, _d, _d, _i64]),
+    'apm_ep_eval': (_i, [_p, _i64, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _p]),
+    'apm_ep_predict': (_i, [_p, _i64, _p, _i64, _p, _i64, _i64, _p, _p, _p, _i64, _p, _p]),
+    'apm_ep': (_i, [_i, _p, _i64, _i64, _p, _i, _d, _d, _i64, _p, _p, _p, _p, _p, _i64, _p, _p,
+                    _p]),
     'apm_laplace': (_i, [_i, _p, _i64, _i64, _p, _i, _i, _d, _i64, _p, _p, _i64, _p, _p, _p]),
     'apm_laplace_lik': (_i, [_i, _i, _p, _i64, _i64, _p, _i, _i, _d, _i64, _p, _p, _i64, _p, _p,
                              _p]),
@@ -200,6 +206,25 @@ def laplace(K, y, calc_cov, calc_lml, diff_f_tol, max_iters, device=None, likeli
     else:
         _check(lib.apm_laplace_lik(dev, lik, *tail))
     return f, C, float(lml[0]), int(nit[0]), int(st[0])
+
+
+def ep(K, y, calc_cov, damping, diff_tol, max_sweeps, device=None):
+    """Stand-alone EP fit on a K of the caller's (include/apm.h apm_ep):
+    ``(mu, var, tau, nu, C, logz, n_sweeps, status)``, C None without calc_cov."""
+    lib = load_library()
+    K = _f64(K)
+    y = _f64(y)
+    n = K.shape[0]
+    mu, var, tau, nu = (np.empty(n) for _ in range(4))
+    C = np.empty((n, n)) if calc_cov else None
+    logz = np.zeros(1)
+    nsw = np.zeros(1, dtype=np.int64)
+    st = np.zeros(1, dtype=np.int32)
+    _check(lib.apm_ep(default_device() if device is None else device, _ptr(K), n, n, _ptr(y),
+                      int(bool(calc_cov)), float(damping), float(diff_tol), int(max_sweeps),
+                      _ptr(mu), _ptr(var), _ptr(tau), _ptr(nu), _ptr(C), n, _ptr(logz), _ptr(nsw),
+                      _ptr(st)))
+    return mu, var, tau, nu, C, float(logz[0]), int(nsw[0]), int(st[0])
 
 
 def selftest_tile(A, B, C, device=None):
@@ -414,6 +439,52 @@ class Context(object):
                 self._h, cnt, th[t0:].ctypes.data, th.shape[1], lml[t0:].ctypes.data,
                 grad[t0:].ctypes.data, P, st[t0:].ctypes.data, nit[t0:].ctypes.data), self._h)
         return lml, grad, st, nit
+
+    def set_ep(self, damping=0.8, diff_tol=1e-8, max_sweeps=100):
+        _check(self.lib.apm_set_ep(self._h, float(damping), float(diff_tol), int(max_sweeps)),
+               self._h)
+
+    def ep(self, thetas):
+        """Expectation-propagation fit for every row of thetas, `max_batch` at a time:
+        ``(logz (T,), mu, var, tau, nu (each (T, n)), status, n_sweeps)`` with NaN where
+        status != 0 (include/apm.h apm_ep_eval)."""
+        th = np.atleast_2d(_f64(thetas))
+        if th.shape[1] < self.theta_len:
+            raise IndexError('Out of bounds on buffer access (axis 0)')
+        T, n = th.shape[0], self.n
+        logz = np.full(T, np.nan)
+        mu, var, tau, nu = (np.full((T, n), np.nan) for _ in range(4))
+        st = np.zeros(T, dtype=np.int32)
+        nsw = np.zeros(T, dtype=np.int64)
+        for t0 in range(0, T, self.max_batch):
+            cnt = min(self.max_batch, T - t0)
+            _check(self.lib.apm_ep_eval(
+                self._h, cnt, th[t0:].ctypes.data, th.shape[1], logz[t0:].ctypes.data,
+                mu[t0:].ctypes.data, var[t0:].ctypes.data, tau[t0:].ctypes.data,
+                nu[t0:].ctypes.data, n, st[t0:].ctypes.data, nsw[t0:].ctypes.data), self._h)
+        return logz, mu, var, tau, nu, st, nsw
+
+    def ep_predict(self, thetas, X_test):
+        """EP predictive at X_test (m, d) for every row of thetas, `max_batch` at a time:
+        ``(mean, var, prob, status, n_sweeps)``, the first three (T, m) with NaN rows where
+        status != 0 (include/apm.h apm_ep_predict)."""
+        th = np.atleast_2d(_f64(thetas))
+        if th.shape[1] < self.theta_len:
+            raise IndexError('Out of bounds on buffer access (axis 0)')
+        Xs = _f64(X_test)
+        if Xs.ndim != 2 or Xs.shape[1] != self.d:
+            raise ValueError('X_test has shape {0}, expected (m, {1})'.format(Xs.shape, self.d))
+        T, m = th.shape[0], Xs.shape[0]
+        mean, var, prob = (np.full((T, m), np.nan) for _ in range(3))
+        st = np.zeros(T, dtype=np.int32)
+        nsw = np.zeros(T, dtype=np.int64)
+        for t0 in range(0, T, self.max_batch):
+            cnt = min(self.max_batch, T - t0)
+            _check(self.lib.apm_ep_predict(
+                self._h, cnt, th[t0:].ctypes.data, th.shape[1], _ptr(Xs), m, self.d,
+                mean[t0:].ctypes.data, var[t0:].ctypes.data, prob[t0:].ctypes.data, m,
+                st[t0:].ctypes.data, nsw[t0:].ctypes.data), self._h)
+        return mean, var, prob, st, nsw
 
     def u_eval(self, slots, ubufs):
         sl = np.ascontiguousarray(slots, dtype=np.int64)

@@ -16,9 +16,11 @@ back skips the O(N^3) work exactly as the reference's tuple does.
 import numpy as np
 
 from . import _native
-from .latent_posterior_approximations import MaximumIterationsExceededError
+from .latent_posterior_approximations import (MaximumIterationsExceededError,
+                                              raise_for_ep_status)
 
-__all__ = ['LogMarginalLikelihoodLaplaceEstimator', 'InvalidCovarianceMatrixError',
+__all__ = ['LogMarginalLikelihoodLaplaceEstimator', 'LogMarginalLikelihoodEPEstimator',
+           'InvalidCovarianceMatrixError',
            'LogMarginalLikelihoodApproxPosteriorISEstimator',
            'LogMarginalLikelihoodPriorMCEstimator', 'DeviceCache', 'DeviceInvariantError']
 
@@ -180,6 +182,39 @@ class LogMarginalLikelihoodLaplaceEstimator(_EstimatorBase):
         _raise_for_status(int(st[0]), ctx)
         self.n_cubic_ops += int(nops[0])
         return float(out[0])
+
+
+class LogMarginalLikelihoodEPEstimator(_EstimatorBase):
+    """Deterministic (biased) expectation-propagation estimate ``log Z_EP`` of
+    log p(y | theta, X) for the probit likelihood. No reference counterpart; the
+    call signature is the Laplace estimator's, so it can stand wherever that one does (e.g. as
+    the deterministic target of PM-MH). ``n_cubic_ops`` grows by 2 per sweep, one factorisation
+    and one matrix triangular solve: the project's own accounting. ``damping``, ``diff_tol`` and
+    ``max_sweeps`` are the EP settings; ``likelihood='logit'`` raises ``NotImplementedError``
+    (its tilted moments need quadrature)."""
+
+    def __init__(self, X, y, kernel_func, likelihood='probit', damping=0.8, diff_tol=1e-8,
+                 max_sweeps=100):
+        if _native.likelihood_code(likelihood) != _native.LIK_PROBIT:
+            raise NotImplementedError('expectation propagation is implemented for the probit '
+                                      'likelihood only')
+        super(LogMarginalLikelihoodEPEstimator, self).__init__(X, y, kernel_func, likelihood)
+        self.ep_settings = (float(damping), float(diff_tol), int(max_sweeps))
+        self.n_sweeps = None
+
+    def __call__(self, theta):
+        if self._prob.device_gram:
+            ctx = self._prob.ctx(1)
+            ctx.set_ep(*self.ep_settings)
+            logz, _, _, _, _, st, nsw = ctx.ep(np.atleast_1d(theta)[None])
+            logz, st, nsw = float(logz[0]), int(st[0]), int(nsw[0])
+        else:
+            self.kernel_func(self._K, self.X, theta)
+            logz, nsw, st = _native.ep(self._K, self.y, False, *self.ep_settings)[5:]
+        raise_for_ep_status(st, self.ep_settings[2])
+        self.n_sweeps = nsw
+        self.n_cubic_ops += 2 * nsw
+        return logz
 
 
 class LogMarginalLikelihoodApproxPosteriorISEstimator(_EstimatorBase):

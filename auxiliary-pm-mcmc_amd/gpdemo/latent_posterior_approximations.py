@@ -12,11 +12,16 @@ import numpy as np
 
 from . import _native
 
-__all__ = ['MaximumIterationsExceededError', 'laplace_approximation']
+__all__ = ['MaximumIterationsExceededError', 'InvalidCavityError', 'laplace_approximation',
+           'ep_approximation']
 
 
 class MaximumIterationsExceededError(Exception):
     """Raised when Newton's method fails to converge by the iteration limit."""
+
+
+class InvalidCavityError(Exception):
+    """Raised when an expectation-propagation cavity precision is not positive and finite."""
 
 
 def laplace_approximation(K, y, calc_cov=True, calc_lml=False, diff_f_tol=1e-4, max_iters=1000,
@@ -42,3 +47,37 @@ def laplace_approximation(K, y, calc_cov=True, calc_lml=False, diff_f_tol=1e-4, 
 
 # the estimators run this approximation fused on the device when they are handed this function
 laplace_approximation.apm_fused = True
+
+
+def ep_approximation(K, y, calc_cov=True, calc_lml=False, damping=0.8, diff_tol=1e-8,
+                     max_sweeps=100, return_sites=False):
+    """Expectation-propagation approximation of the latent posterior for the probit likelihood
+    (Rasmussen & Williams §3.6; parallel EP with damped site updates), computed on
+    the GPU. No reference counterpart. The return shape is ``laplace_approximation``'s:
+    ``(mu, C, lml, n_ops)``, ``(mu, lml, n_ops)``, ``(mu, C, n_ops)`` or ``(mu, n_ops)`` with
+    ``mu`` the posterior mean, ``C`` the posterior covariance, ``lml = log Z_EP`` and ``n_ops``
+    the project's own count of O(N^3) operations, two per sweep (one factorisation and one matrix
+    triangular solve) plus one for ``C``. With ``return_sites=True`` a dict with the site
+    parameters ``tau`` and ``nu``, the marginal variances ``var`` and ``n_sweeps`` is appended.
+    Raises ``MaximumIterationsExceededError`` (no convergence in ``max_sweeps``),
+    ``numpy.linalg.LinAlgError`` (a factorisation failed) or ``InvalidCavityError``."""
+    mu, var, tau, nu, C, logz, n_sweeps, status = _native.ep(K, y, calc_cov, damping, diff_tol,
+                                                             max_sweeps)
+    raise_for_ep_status(status, max_sweeps)
+    n_ops = 2 * n_sweeps + (1 if calc_cov else 0)
+    out = (mu,) + ((C,) if calc_cov else ()) + ((logz,) if calc_lml else ()) + (n_ops,)
+    if return_sites:
+        out += (dict(tau=tau, nu=nu, var=var, n_sweeps=n_sweeps),)
+    return out
+
+
+def raise_for_ep_status(status, max_sweeps):
+    """The exception of an EP chain's status (include/apm.h), nothing for APM_STATUS_OK."""
+    if status == _native.STATUS_OK:
+        return
+    if status == _native.STATUS_MAXITER:
+        raise MaximumIterationsExceededError(
+            'Failed to converge in {0} sweeps'.format(max_sweeps))
+    if status == _native.STATUS_EP_CAVITY:
+        raise InvalidCavityError('a cavity precision was not positive and finite')
+    raise np.linalg.LinAlgError('Cholesky factorisation of B failed (not positive definite)')

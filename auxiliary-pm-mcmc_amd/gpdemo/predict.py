@@ -22,8 +22,9 @@ from scipy.special import log_ndtr
 
 from . import _native
 from .estimators import _kernel_spec, _raise_for_status
+from .latent_posterior_approximations import raise_for_ep_status
 
-__all__ = ['LaplacePredictor', 'posterior_average', 'log_predictive_density']
+__all__ = ['LaplacePredictor', 'EPPredictor', 'posterior_average', 'log_predictive_density']
 
 
 def _keep(a, burn, thin):
@@ -130,3 +131,36 @@ class LaplacePredictor(object):
 
     def close(self):
         self._ctx.close()
+
+
+class EPPredictor(LaplacePredictor):
+    """The same predictive quantities from the expectation-propagation fit
+    instead of the Laplace fit: ``mu* = k*^T a``, ``var* = k** - |L^-1 (S^1/2 . k*)|^2`` with the
+    EP sites' ``S = diag(tau~)``, ``a`` and ``L = chol(I + S^1/2 K S^1/2)``, ``pi* = Phi(mu* /
+    sqrt(1 + var*))`` (Rasmussen & Williams Alg. 3.6). Probit only: ``likelihood='logit'`` raises
+    ``NotImplementedError``. ``damping``, ``diff_tol`` and ``max_sweeps`` are the EP settings;
+    the methods are :class:`LaplacePredictor`'s, ``self.n_iter`` holding the sweep counts."""
+
+    def __init__(self, X, y, kernel_func, X_test, damping=0.8, diff_tol=1e-8, max_sweeps=100,
+                 max_batch=8, device=None, likelihood='probit'):
+        if _native.likelihood_code(likelihood) != _native.LIK_PROBIT:
+            raise NotImplementedError('expectation propagation is implemented for the probit '
+                                      'likelihood only')
+        super(EPPredictor, self).__init__(X, y, kernel_func, X_test, max_batch=max_batch,
+                                          device=device, likelihood=likelihood)
+        self.max_sweeps = int(max_sweeps)
+        self._ctx.set_ep(damping, diff_tol, max_sweeps)
+
+    def __call__(self, thetas, on_error='raise'):
+        """``(mean, var, prob)``, each (T, M); a theta whose EP fit fails raises
+        ``MaximumIterationsExceededError``, ``LinAlgError`` or ``InvalidCavityError``, or gives
+        NaN rows with ``on_error='nan'``."""
+        if on_error not in ('raise', 'nan'):
+            raise ValueError("on_error must be 'raise' or 'nan'")
+        th = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
+        mean, var, prob, st, nsw = self._ctx.ep_predict(th, self.X_test)
+        self.n_iter, self.status = nsw, st
+        if on_error == 'raise':
+            for s in st:
+                raise_for_ep_status(int(s), self.max_sweeps)
+        return mean, var, prob

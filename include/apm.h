@@ -12,6 +12,9 @@
  *                         inputs from the Newton quantities of laplace_approximation (:81-112)
  *   apm_laplace_grad   <- no reference counterpart: the gradient of the Laplace log marginal
  *                         likelihood (:103-106) with respect to theta
+ *   apm_ep_eval        <- no reference counterpart: expectation propagation for the probit (the
+ *   apm_ep_predict        fit, log Z_EP, the marginals and the predictive distribution; R&W §3.6)
+ *   apm_ep                with the sweeps' factorisations and solves on the device
  *   apm_laplace        <- gpdemo/latent_posterior_approximations.py:22-124  laplace_approximation(K, y, ...)
  *   apm_theta_eval     <- gpdemo/estimators.py:201-217 (+ :221-241)  ApproxPosteriorIS.__call__(ns, theta)
  *                         gpdemo/estimators.py:317-325               PriorMC.__call__(ns, theta)
@@ -53,6 +56,9 @@ extern "C" {
 #define APM_STATUS_GUARD 5    /* a device-side invariant of the theta-call failed (apm_guard_read;
                                  DESIGN.md §11): the value is withheld -> DeviceInvariantError
                                  (no reference counterpart: the reference has no device) */
+#define APM_STATUS_EP_CAVITY 6 /* an EP cavity precision 1/sigma_i^2 - tau~_i was <= 0 or not finite
+                                  -> InvalidCavityError (no reference counterpart: the reference has
+                                  no EP) */
 
 /* covariance kernels */
 #define APM_KERNEL_ISO 0         /* kernels.pyx:12-49, theta = (log sigma, log tau) */
@@ -182,6 +188,47 @@ int apm_predict(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ldt,
  * context's work matrix like every theta-call; cache slots and U buffers are not touched. */
 int apm_laplace_grad(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ldt, double *lml,
                      double *grad, int64_t ldg, int *status, int64_t *n_iter);
+/* ---- expectation propagation (no reference counterpart) ----------------------
+ * Parallel EP for the probit likelihood, labels y in {-1, +1}. From tau~ = nu~ = 0, sweep t = 1,
+ * 2, ...:
+ *   1. S^1/2 = sqrt(tau~), L = chol(I + S^1/2 K S^1/2) (failure: APM_STATUS_CHOL_B),
+ *      a = nu~ - S^1/2 B^-1 S^1/2 K nu~, mu = K a, V = L^-1 (S^1/2 K), sigma2_i = K_ii - sum_r V_ri^2;
+ *   2. tau_- = 1/sigma2 - tau~, nu_- = mu/sigma2 - nu~, mu_- = nu_-/tau_-, s_- = 1/tau_-; a tau_-
+ *      that is <= 0 or not finite fails the chain with APM_STATUS_EP_CAVITY;
+ *      z = y mu_- / sqrt(1 + s_-);
+ *   3. for t >= 2: mean_i (mu_i - mu_i of sweep t - 1)^2 < diff_tol stops the chain with no site
+ *      update, so sites, L, a, mu and sigma2 returned are those of one sweep, n_sweeps = t; a
+ *      chain not stopped after sweep max_sweeps fails with APM_STATUS_MAXITER;
+ *   4. r = phi(z)/Phi(z), mu^ = mu_- + y s_- r / sqrt(1 + s_-), s^ = s_- - s_-^2 r (z + r)/(1 + s_-);
+ *   5. tau~_new = max(1/s^ - tau_-, 0), nu~_new = mu^/s^ - nu_-, tau~ <- (1 - damping) tau~ +
+ *      damping tau~_new and nu~ likewise (the clamp removes rounding only: tau~_new >= 0 holds
+ *      exactly for the probit).
+ *   log Z_EP = sum log Phi(z_i) + 1/2 sum log(1 + tau~_i/tau_-i) - sum log L_ii + 1/2 nu~^T mu
+ *              - 1/2 sum nu~_i^2 sigma2_i + 1/2 sum mu_-i tau_-i (tau~_i mu_-i - 2 nu~_i) sigma2_i
+ * (R&W eqs. 3.65, 3.73-3.74), every sum over the n data rows in a fixed order. Everything is
+ * fp64. The logit is out of scope (its tilted moments have no closed form and need quadrature):
+ * every EP entry point returns APM_E_INVALID on a context whose likelihood is APM_LIK_LOGIT.
+ * apm_version() is unchanged: a caller detects EP by the presence of these symbols. */
+/* damping in (0, 1], diff_tol >= 0, max_sweeps >= 1 (APM_E_INVALID otherwise); defaults 0.8,
+ * 1e-8, 100 (DESIGN.md §16 has the study they come from) */
+int apm_set_ep(apm_ctx *ctx, double damping, double diff_tol, int64_t max_sweeps);
+/* The EP fit for `count` thetas (count <= max_batch): Gram -> sweeps (apm_set_ep settings) ->
+ * logz[i] and rows i of mu, var (sigma2), tau (tau~), nu (nu~), each count x n with row stride
+ * ldo; any of the five may be NULL. status[i]: APM_STATUS_* of chain i (the outputs of a failed
+ * chain are NaN); n_sweeps[i] (may be NULL). Needs an ISO or ARD context of any family, not a
+ * PRECOMPUTED one. A chain's outputs do not depend on its position in the batch nor on the other
+ * chains. Uses the context's work matrix like every theta-call; cache slots and U buffers are
+ * not touched. */
+int apm_ep_eval(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ldt, double *logz,
+                double *mu, double *var, double *tau, double *nu, int64_t ldo, int *status,
+                int64_t *n_sweeps);
+/* The EP fit, then apm_predict's pass on the final S^1/2, a and L at the m test inputs Xs (m x d,
+ * ldxs), in blocks of at most apm_padded_n rows: mean = k*^T a, var = s - |L^-1 (S^1/2 . k*)|^2
+ * with s = exp(theta_0), prob = Phi(mean / sqrt(1 + var)); each count x m with row stride ldo,
+ * any of the three may be NULL, NaN rows for a failed chain. Nothing is clamped. */
+int apm_ep_predict(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ldt,
+                   const double *Xs, int64_t m, int64_t ldxs, double *mean, double *var,
+                   double *prob, int64_t ldo, int *status, int64_t *n_sweeps);
 /* cached u-call: reuse slots[i]'s per-theta state with draws ubufs[i] */
 int apm_u_eval(apm_ctx *ctx, int64_t count, const int64_t *slots, const int64_t *ubufs,
                double *out_logf, int *status);
@@ -218,6 +265,16 @@ int apm_laplace_lik(int device, int lik, const double *K, int64_t n, int64_t ldk
                     double *f_out, double *C_out, int64_t ldc, double *lml_out,
                     int64_t *n_iter_out, int *status);
 
+/* EP's stand-alone twin of apm_laplace (no reference counterpart): the caller supplies K (n x n,
+ * ldk) and the settings; mu_out, var_out, tau_out, nu_out (n each), logz_out and n_sweeps_out
+ * may be NULL; calc_cov: C_out (n x n, ldc) = K - V^T V, the posterior covariance, formed as
+ * apm_laplace's. Probit only. On a failed fit (*status != 0) the outputs are NaN and C_out is
+ * left alone. */
+int apm_ep(int device, const double *K, int64_t n, int64_t ldk, const double *y, int calc_cov,
+           double damping, double diff_tol, int64_t max_sweeps, double *mu_out, double *var_out,
+           double *tau_out, double *nu_out, double *C_out, int64_t ldc, double *logz_out,
+           int64_t *n_sweeps_out, int *status);
+
 /* ---- device-time accounting of the hot kernels (HIP events on the context stream) ------------ */
 #define APM_PROF_GRAM 0
 #define APM_PROF_CHOL_UPDATE 1
@@ -243,7 +300,9 @@ int apm_laplace_lik(int device, int lik, const double *K, int64_t n, int64_t ldk
 #define APM_PROF_GUARD 12 /* not a kernel: launches = chains failed by the guard (APM_STATUS_GUARD) */
 #define APM_PROF_GRAD_REDUCE 13 /* k_grad_reduce of apm_laplace_grad; work = bytes (the lower
                                    triangles of R and K it reads) */
-#define APM_PROF_NKINDS 14
+#define APM_PROF_EP_SITES 14 /* k_ep_sites of the EP sweeps; work = bytes (the solved rows of V^T
+                                it reads) */
+#define APM_PROF_NKINDS 15
 /* on = 0 off; 1 the roofline kinds (GRAM, UGEMM and the two *_OUTER kinds: one event pair per
  * launch of those kernels only, so that the timing adds little to a timed region); 2 every kind
  * (CHOL_UPDATE / CHOL_UPDATE32 add an event pair around every in-panel update launch) */

@@ -1,0 +1,350 @@
+"""Expectation propagation on the device (apm_ep_eval / apm_ep_predict / apm_ep; ep.hip,
+host_ep.cpp) against the numpy restatement (tests/ep_restatement.py), plus the
+properties that need no oracle: batch neutrality, that an EP call leaves every other path's
+results alone, failure mapping and the Python layer."""
+import math
+
+import numpy as np
+import pytest
+
+import apm_oracle as orc
+import ep_restatement as ep
+import matern_restatement as mr
+from test_gpu_predict import I_EQ, SHAPES, _make_case
+
+pytestmark = pytest.mark.gpu
+
+EPS = 1e-8
+# device-to-restatement tolerance (x max(1, max|ref|)): fp64 against fp64 through the same
+# algebra, the project's yardstick. The measured maxima are in DESIGN.md §16.
+TOL = 1e-9
+DIFF_TOL = 1e-8  # the default stop tolerance
+KEYS = ('logz', 'mu', 'var', 'tau', 'nu')
+EDGE_N = (65, 512, 513, 577)
+
+
+def assert_stop_margin(fit, diff_tol=DIFF_TOL):
+    """A condition on the restatement alone: the stop measure of the last sweep is below 0.99
+    diff_tol and the one before it above 1.01 diff_tol, so rounding cannot flip the sweep count."""
+    m = fit['m_hist']
+    print('stop measure / diff_tol: last {0:.3f}, before {1}'.format(
+        m[-1] / diff_tol, 'none' if len(m) < 2 else '{0:.3f}'.format(m[-2] / diff_tol)))
+    assert m[-1] < 0.99 * diff_tol
+    assert len(m) < 2 or m[-2] > 1.01 * diff_tol
+
+
+def parity(dev, t, ref):
+    """max over the five outputs of |device - restatement| / max(1, max|restatement|)."""
+    worst = 0.0
+    for k, key in enumerate(KEYS):
+        scale = max(1.0, float(np.max(np.abs(ref[key]))))
+        err = float(np.max(np.abs(dev[k][t] - ref[key]))) / scale
+        print('  {0}: {1:.3e}'.format(key, err))
+        worst = max(worst, err)
+    return worst
+
+
+def oracle_K(c, th):
+    K = np.empty((c['n'], c['n']))
+    orc.c_gram(c['kind'], K, c['X'], th, EPS)
+    return K
+
+
+def kind_code(nat, kind):
+    return nat.KERNEL_ISO if kind == 'iso' else nat.KERNEL_ARD
+
+
+@pytest.fixture(scope='module')
+def nat(gpu_available):
+    from gpdemo import _native
+    _native.load_library()
+    return _native
+
+
+@pytest.fixture(scope='module')
+def cases():
+    """Data and restatement fits per shape of test_gpu_predict, computed once, left unchanged."""
+    out = []
+    for i, (n, d, m, kind) in enumerate(SHAPES):
+        c = _make_case(n, d, m, kind, 100 + i)
+        c['fit'] = [ep.ep_fit(oracle_K(c, th), c['y']) for th in c['thetas']]
+        out.append(c)
+    return out
+
+
+@pytest.fixture(scope='module')
+def device(nat, cases):
+    """apm_ep_eval per shape: one call, three thetas."""
+    out = []
+    for c in cases:
+        ctx = nat.Context(c['X'], c['y'], kind_code(nat, c['kind']), EPS, 1, max_batch=3,
+                          n_slots=1, n_ubufs=1)
+        out.append(ctx.ep(c['thetas']))
+        ctx.close()
+    return out
+
+
+@pytest.mark.parametrize('ci', range(len(SHAPES)))
+def test_ep_eval_vs_restatement(cases, device, ci):
+    c, dev = cases[ci], device[ci]
+    worst = 0.0
+    for t, fit in enumerate(c['fit']):
+        assert_stop_margin(fit)
+        assert dev[5][t] == 0
+        print('shape {0} theta_0 {1}: sweeps {2}'.format(SHAPES[ci], c['thetas'][t][0],
+                                                        fit['n_sweeps']))
+        assert int(dev[6][t]) == fit['n_sweeps']
+        worst = max(worst, parity(dev, t, fit))
+    print('EP parity shape {0}: worst {1:.3e} (tol {2:.0e})'.format(SHAPES[ci], worst, TOL))
+    assert worst <= TOL
+
+
+@pytest.mark.parametrize('n', EDGE_N)
+def test_panel_edges(nat, n):
+    """d = 4, ARD, theta_0 = 0.3 at the tile and outer-panel boundaries (nb = 2, 8, 9, 10)."""
+    c = _make_case(n, 4, 3, 'ard', 300 + n)
+    th = c['thetas'][0]
+    fit = ep.ep_fit(oracle_K(c, th), c['y'])
+    assert_stop_margin(fit)
+    ctx = nat.Context(c['X'], c['y'], nat.KERNEL_ARD, EPS, 1, max_batch=1, n_slots=1, n_ubufs=1)
+    dev = ctx.ep(th)
+    ctx.close()
+    assert dev[5][0] == 0 and int(dev[6][0]) == fit['n_sweeps']
+    worst = parity(dev, 0, fit)
+    print('EP parity N = {0}: worst {1:.3e}'.format(n, worst))
+    assert worst <= TOL
+
+
+def test_panel_edge_matern52(nat):
+    c = _make_case(513, 4, 3, 'ard', 300 + 513)
+    th = c['thetas'][0]
+    fit = ep.ep_fit(mr.gram('52', 'ard', c['X'], th, EPS), c['y'])
+    assert_stop_margin(fit)
+    ctx = nat.Context(c['X'], c['y'], nat.KERNEL_M52_ARD, EPS, 1, max_batch=1, n_slots=1,
+                      n_ubufs=1)
+    dev = ctx.ep(th)
+    ctx.close()
+    assert dev[5][0] == 0 and int(dev[6][0]) == fit['n_sweeps']
+    worst = parity(dev, 0, fit)
+    print('EP parity Matern 5/2 N = 513: worst {0:.3e}'.format(worst))
+    assert worst <= TOL
+
+
+@pytest.mark.parametrize('theta0', (6.0, 10.0))
+def test_wide_prior_variance(nat, cases, theta0):
+    """sigma = e^6, e^10 at (200, 3, iso): K_ii - |V_i|^2 cancels up to five digits, so log Z is
+    held to the estimator tolerance of DESIGN.md §3.3 (5e-4 nats), not to the 1e-9 yardstick."""
+    c = cases[2]
+    th = c['thetas'][0].copy()
+    th[0] = theta0
+    fit = ep.ep_fit(oracle_K(c, th), c['y'])
+    assert_stop_margin(fit)
+    ctx = nat.Context(c['X'], c['y'], nat.KERNEL_ISO, EPS, 1, max_batch=1, n_slots=1, n_ubufs=1)
+    logz, mu, var, tau, nu, st, nsw = ctx.ep(th)
+    ctx.close()
+    assert st[0] == 0 and int(nsw[0]) == fit['n_sweeps']
+    print('theta_0 {0}: sweeps {1}, dlogZ {2:.3e}, min var / sigma {3:.3e}'.format(
+        theta0, fit['n_sweeps'], abs(logz[0] - fit['logz']), var[0].min() / math.exp(theta0)))
+    assert abs(logz[0] - fit['logz']) <= 5e-4
+    assert np.all(var[0] > 0.0) and np.all(var[0] <= math.exp(theta0) + EPS)
+
+
+def test_standalone_ep_equals_ep_eval(nat, cases, device):
+    c, dev = cases[0], device[0]
+    th = c['thetas'][0]
+    K = oracle_K(c, th)
+    mu, var, tau, nu, C, logz, nsw, st = nat.ep(K, c['y'], True, 0.8, DIFF_TOL, 100)
+    assert st == 0 and nsw == int(dev[6][0])
+    for got, k in ((logz, 0), (mu, 1), (var, 2), (tau, 3), (nu, 4)):
+        scale = max(1.0, float(np.max(np.abs(dev[k][0]))))
+        assert np.max(np.abs(got - dev[k][0])) <= TOL * scale
+    assert np.array_equal(C, C.T)
+    rel = np.max(np.abs(np.diag(C) - var) / var)
+    print('apm_ep: max |diag(C) - var| / var = {0:.3e}'.format(rel))
+    assert rel <= 1e-12
+    import gpdemo.latent_posterior_approximations as lpa
+    out = lpa.ep_approximation(K, c['y'], calc_cov=True, calc_lml=True, return_sites=True)
+    assert len(out) == 5 and out[3] == 2 * nsw + 1
+    assert np.array_equal(out[0], mu) and np.array_equal(out[1], C) and out[2] == logz
+    assert np.array_equal(out[4]['tau'], tau) and np.array_equal(out[4]['var'], var)
+    assert len(lpa.ep_approximation(K, c['y'], calc_cov=False)) == 2
+
+
+@pytest.mark.parametrize('ci', (0, 4))
+def test_ep_predict_vs_restatement(nat, cases, ci):
+    """(130, 5, m = 70) and (600, 4, m = 70): test row 0 coincides with training row I_EQ, the
+    last one is 50 units away in every coordinate (k* = 0 exactly)."""
+    c = cases[ci]
+    assert c['m'] == 70
+    ctx = nat.Context(c['X'], c['y'], nat.KERNEL_ARD, EPS, 1, max_batch=3, n_slots=1, n_ubufs=1)
+    mean, var, prob, st, nsw = ctx.ep_predict(c['thetas'], c['Xs'])
+    ctx.close()
+    worst = 0.0
+    for t, (th, fit) in enumerate(zip(c['thetas'], c['fit'])):
+        assert st[t] == 0 and int(nsw[t]) == fit['n_sweeps']
+        G = np.empty((c['n'] + 70, c['n'] + 70))
+        orc.c_gram(c['kind'], G, np.concatenate([c['X'], c['Xs']]), th, EPS)
+        Ks = G[c['n']:, :c['n']]
+        sigma = math.exp(th[0])
+        ref = ep.at_test_inputs(Ks, sigma, fit)
+        for key, got in (('mean', mean), ('var', var), ('prob', prob)):
+            scale = 1.0 if key == 'prob' else max(1.0, float(np.abs(ref[key]).max()))
+            worst = max(worst, float(np.abs(got[t] - ref[key]).max()) / scale)
+        assert (mean[t, -1], var[t, -1], prob[t, -1]) == (0.0, sigma, 0.5)
+        # the coinciding row: k* = K[I_EQ, :] - epsilon e_i, so mu* = mu_i - epsilon a_i
+        assert abs(mean[t, 0] - fit['mu'][I_EQ]) <= 10 * EPS * np.abs(fit['a']).max()
+    print('EP predict parity shape {0}: worst {1:.3e}'.format(SHAPES[ci], worst))
+    assert worst <= TOL
+
+
+def test_batch_neutrality(nat, cases):
+    """Three thetas with different sweep counts in one call (max_batch = 4), then one by one:
+    every output bitwise equal."""
+    c = cases[0]
+    assert len(set(f['n_sweeps'] for f in c['fit'])) == 3
+    ctx = nat.Context(c['X'], c['y'], nat.KERNEL_ARD, EPS, 1, max_batch=4, n_slots=1, n_ubufs=1)
+    full = ctx.ep(c['thetas'])
+    pfull = ctx.ep_predict(c['thetas'], c['Xs'])
+    assert len(set(full[6].tolist())) == 3
+    for t in range(3):
+        one = ctx.ep(c['thetas'][t])
+        for a, b in zip(full, one):
+            assert np.array_equal(a[t], b[0])
+        pone = ctx.ep_predict(c['thetas'][t], c['Xs'])
+        for a, b in zip(pfull, pone):
+            assert np.array_equal(a[t], b[0])
+    ctx.close()
+
+
+def _other_paths(nat, ctx, c):
+    """Everything the other paths return on one context, as a flat list of arrays."""
+    th = c['thetas'][:2]
+    out = list(ctx.theta_eval(nat.EST_LAPLACE, th))
+    out += list(ctx.predict(th, c['Xs']))
+    out += list(ctx.laplace_grad(th))
+    ctx.u_normal([0, 1], [5, 5], [0, 1])
+    out += list(ctx.theta_eval(nat.EST_IS, th, [0, 1], [0, 1]))
+    out += list(ctx.u_eval([0, 1], [1, 0]))
+    for slot in (0, 1):
+        L, f, g, cst = ctx.slot_read(slot)
+        out += [L, f, g, np.array(cst)]
+    return out
+
+
+def test_ep_leaves_the_other_paths_alone(nat):
+    """N = 577: the Laplace theta-call, predict, laplace_grad and an IS theta-call, u-call and
+    slot read-back, before and after an EP fit and an EP predict on the same context, and on a
+    fresh context: all bitwise the same."""
+    c = _make_case(577, 4, 3, 'ard', 300 + 577)
+
+    def make():
+        return nat.Context(c['X'], c['y'], nat.KERNEL_ARD, EPS, 8, max_batch=2, n_slots=2,
+                           n_ubufs=2)
+    ctx = make()
+    before = _other_paths(nat, ctx, c)
+    assert not np.any(before[1]) and not np.any(before[13])  # (Laplace and IS statuses)
+    st = ctx.ep(c['thetas'][:2])[5]
+    pst = ctx.ep_predict(c['thetas'][:2], c['Xs'])[3]
+    assert not st.any() and not pst.any()
+    after = _other_paths(nat, ctx, c)
+    ctx.close()
+    ctx = make()
+    fresh = _other_paths(nat, ctx, c)
+    ctx.close()
+    assert len(before) == len(after) == len(fresh)
+    for i, (a, b, f) in enumerate(zip(before, after, fresh)):
+        assert np.array_equal(a, b, equal_nan=True), i
+        assert np.array_equal(a, f, equal_nan=True), i
+
+
+def test_failure_mapping(nat, cases):
+    import gpdemo.estimators as est
+    import gpdemo.kernels as krn
+    import gpdemo.predict as prd
+    from gpdemo.latent_posterior_approximations import MaximumIterationsExceededError
+    c = cases[0]
+    easy = c['thetas'][0].copy()
+    easy[0] = -16.0  # mu ~ n e^-16: the second sweep already moves it by less than the tolerance
+    assert ep.ep_fit(oracle_K(c, easy), c['y'])['n_sweeps'] == 2
+    thetas = np.array([easy, c['thetas'][0]])
+    ctx = nat.Context(c['X'], c['y'], nat.KERNEL_ARD, EPS, 1, max_batch=2, n_slots=1, n_ubufs=1)
+    ctx.set_ep(0.8, DIFF_TOL, 2)
+    bad = ctx.ep(thetas)
+    assert list(bad[5]) == [nat.STATUS_OK, nat.STATUS_MAXITER] and list(bad[6]) == [2, 2]
+    for k in range(5):
+        assert np.all(np.isnan(bad[k][1])) and np.all(np.isfinite(bad[k][0]))
+    ctx.set_ep()  # the defaults
+    good = ctx.ep(thetas)
+    assert list(good[5]) == [0, 0]
+    for k in range(5):
+        assert np.array_equal(good[k][0], bad[k][0])
+    ctx.close()
+    kf = krn.make_kernel_func('ard', EPS)
+    e = est.LogMarginalLikelihoodEPEstimator(c['X'], c['y'], kf, max_sweeps=2)
+    with pytest.raises(MaximumIterationsExceededError):
+        e(c['thetas'][0])
+    p = prd.EPPredictor(c['X'], c['y'], kf, c['Xs'], max_sweeps=2)
+    with pytest.raises(MaximumIterationsExceededError):
+        p(thetas)
+    got = p(thetas, on_error='nan')
+    assert list(p.status) == [nat.STATUS_OK, nat.STATUS_MAXITER]
+    assert np.all(np.isnan(got[0][1])) and np.all(np.isfinite(got[0][0]))
+    p.close()
+    # the logit: refused by the library and by the Python classes
+    lg = nat.Context(c['X'], c['y'], nat.KERNEL_ARD, EPS, 1, max_batch=2, n_slots=1, n_ubufs=1,
+                     likelihood='logit')
+    with pytest.raises(nat.NativeError):
+        lg.ep(thetas)
+    with pytest.raises(nat.NativeError):
+        lg.ep_predict(thetas, c['Xs'])
+    st = np.zeros(2, dtype=np.int32)
+    th = np.ascontiguousarray(thetas)
+    assert lg.lib.apm_ep_eval(lg._h, 2, th.ctypes.data, th.shape[1], None, None, None, None, None,
+                              c['n'], st.ctypes.data, None) == nat.APM_E_INVALID
+    assert lg.lib.apm_set_ep(lg._h, 0.8, 1e-8, 100) == nat.APM_E_INVALID
+    lg.close()
+    with pytest.raises(NotImplementedError):
+        est.LogMarginalLikelihoodEPEstimator(c['X'], c['y'], kf, likelihood='logit')
+    with pytest.raises(NotImplementedError):
+        prd.EPPredictor(c['X'], c['y'], kf, c['Xs'], likelihood='logit')
+
+
+def test_python_layer(nat, cases, device):
+    import gpdemo.estimators as est
+    import gpdemo.kernels as krn
+    import gpdemo.predict as prd
+    c, dev = cases[0], device[0]
+    kf = krn.make_kernel_func('ard', EPS)
+    e = est.LogMarginalLikelihoodEPEstimator(c['X'], c['y'], kf)
+    total = 0
+    for t, th in enumerate(c['thetas']):
+        assert e(th) == dev[0][t]
+        total += 2 * int(dev[6][t])
+        assert e.n_cubic_ops == total
+    p = prd.EPPredictor(c['X'], c['y'], kf, c['Xs'])
+    prob = p(c['thetas'])[2]
+    assert np.array_equal(p.n_iter, dev[6])
+    assert np.array_equal(p.posterior_average(c['thetas']), prob.mean(0))
+    p.close()
+
+
+def test_ep_estimator_drives_pm_mh(nat, cases):
+    """The EP estimator as PM-MH's deterministic target (n = 64, 12 steps): the chain equals the
+    one driven by the restatement's log Z_EP with the same random numbers. An accept decision
+    compares exp(d log Z) with a uniform draw; the two targets differ by ~1e-13 nats."""
+    import auxpm.samplers as smp
+    import gpdemo.estimators as est
+    import gpdemo.kernels as krn
+    c = cases[3]
+    e = est.LogMarginalLikelihoodEPEstimator(c['X'], c['y'], krn.make_kernel_func('ard', EPS))
+
+    def run(target):
+        prng = np.random.RandomState(11)
+        s = smp.PMMHSampler(target, None, lambda x, sc: x + sc * prng.normal(size=x.shape),
+                            np.full(c['thetas'].shape[1], 0.05), prng)
+        return s.get_samples(c['thetas'][0], 12)
+    dev, rej_dev = run(e)
+    ref, rej_ref = run(lambda th: ep.ep_fit(oracle_K(c, th), c['y'])['logz'])
+    assert rej_dev == rej_ref and 0 < rej_dev < 11
+    assert np.array_equal(dev, ref)
+    assert e.n_cubic_ops > 0 and e.n_cubic_ops % 2 == 0
