@@ -173,11 +173,11 @@ struct __attribute__((visibility("hidden"))) apm_ctx {
     bool h3_now = false;  // some chain of the current theta-call may use fp16x3 updates
     bool h3_all = false;  // ... and every chain may (the quad-tile far updates need that)
     bool h3post_all = false;  // every chain takes fp16x3 operands in the posterior bottom block
-    int* h3ok = nullptr;  // per chain: fp16x3 allowed (range check on theta_0, chol32.hip)
+    int* h3ok = nullptr;  // per chain: fp16x3 allowed (range check on theta_0, chol32_update.hip)
     int* h3post = nullptr;  // the same for the posterior factor's fp32 bottom block (h3ok + B)
     // per chain: explicit-inverse Newton panels allowed (h3ok + 2B): their fp16x3 operands are
     // Schur-complement entries of B, bounded by max B_ii <= 1 + K_ii (not by sqrt(B_ii) as the
-    // walk's solved entries are), so the range check is on 1 + K_ii itself (chol32.hip)
+    // walk's solved entries are), so the range check is on 1 + K_ii itself (chol32_panel.hip)
     int* invok = nullptr;
     bool inv_any = false, inv_all = false;
     double* icm_thr = nullptr;  // per chain: SlotSet::icm_thr
@@ -191,7 +191,7 @@ struct __attribute__((visibility("hidden"))) apm_ctx {
     // lookahead's far update reads panel K's while the dataflow launch of K + 1 writes its own)
     unsigned short* planes = nullptr;
     int64_t plane_cs = 0;  // halves per chain and buffer
-    // explicit-inverse panels (chol32.hip k_zinv_* / k_panel_inv_gemm32): the dataflow launch
+    // explicit-inverse panels (chol32_panel.hip k_zinv_* / k_panel_inv_gemm32): the dataflow launch
     // walks the diagonal block and the right-hand-side row only; Z = inv(L_D) per chain (fp32
     // scratch zt: Z, Z^T, T^T; fp16x3 planes zplanes) and one GEMM per row tile below
     float* zt = nullptr;

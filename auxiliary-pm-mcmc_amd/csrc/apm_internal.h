@@ -5,6 +5,7 @@
 #include <string>
 
 #include "apm_common.h"
+#include "tile_lists.h"  // the update lists the launchers below run over (plain C++)
 
 // A batched fp64 matrix: chain b's element (r, c) lives at base[b*cstride + r*ld + c].
 struct MatB {
@@ -13,7 +14,7 @@ struct MatB {
     int64_t cstride;
 };
 
-// The same for fp32 (mixed-precision Newton factorisation, chol32.hip).
+// The same for fp32 (the fp32 factorisations: chol32_panel.hip, chol32_update.hip).
 struct MatF {
     float* base;
     int64_t ld;
@@ -49,7 +50,7 @@ struct FusedDiag {
     int64_t lstride;
     int fail_code;
 };
-// tiles: device list of packed (i << 16) | j built by build_update_tiles (super-tile order)
+// tiles: device list built by build_update_tiles (tile_lists.cpp)
 // plus = true adds instead of subtracting (SYRK of the UL factorisation, postcov.hip)
 void launch_chol_update(MatB A, int k0, int kc, const unsigned* tiles, int ntiles, bool plus,
                         Live live, int nchains, hipStream_t s,
@@ -63,8 +64,9 @@ void launch_chol_update_t128(MatB A, int k0, int kc, const unsigned* tiles, int 
                              FusedDiag<double> fd = FusedDiag<double>{0, nullptr, 0, nullptr, 0, 0},
                              MatB S = MatB{nullptr, 0, 0});
 long update_tile_count(int i0, int R, int j0, int jend);
-#include <vector>
-std::vector<unsigned> build_update_tiles(int i0, int R, int j0, int jend, int glo = 0, int ghi = 0);
+// launch_chol_diag on an fp32 matrix: the first diagonal tile of an fp32 factorisation
+void launch_chol_diag32(MatF A, int k, float* Dinv, int64_t dstride, double* ldet,
+                        int64_t lstride, Live live, int fail_code, int nchains, hipStream_t s);
 // one step (block J) of the backward solve L^T z = r, r stored in row `rrow` of A (in place),
 // z written to z[b*zstride + ...]
 void launch_trsv_lt_step(MatB A, int J, int64_t rrow, const double* Dinv, int64_t dstride,
@@ -75,9 +77,7 @@ void launch_marker(int id, hipStream_t s);
 void launch_tile_nt_test(const double* A, const double* B, double* C, hipStream_t s);
 void launch_philox_test(const uint32_t* in, uint32_t* out, int64_t n, hipStream_t s);
 
-// ---- chol32.hip: mixed-precision Newton solve (fp32 factor of B + fp64 refinement) -----------
-void launch_chol_diag32(MatF A, int k, float* Dinv, int64_t dstride, double* ldet,
-                        int64_t lstride, Live live, int fail_code, int nchains, hipStream_t s);
+// ---- the fp32 factorisations and the mixed-precision Newton solve: shared types -------------
 // Bounded in-launch hand-overs of the Newton solve (k_chol_panel_df32, k_trsv32_mw). HIP promises
 // no dispatch order, so a workgroup's logical index is the ticket it draws from a monotonic
 // arrival counter when it starts (a ticket exists only for a workgroup that is running): a
@@ -91,7 +91,7 @@ struct SpinCtl {
     unsigned long long* timeouts;  // bounded-spin exits (APM_PROF_DF / _TRSV_TIMEOUTS)
     int limit;                     // polls before a wait gives up
 };
-// fp16x3 operand planes of one outer panel of the Newton matrix (chol32.hip): for each 32-column
+// fp16x3 operand planes of one outer panel of the Newton matrix (tile32.h): for each 32-column
 // slice s of the panel and row r < rows, hi = fp16(x) and lo = fp16(x - hi) of the row's 32
 // entries (64 bytes each), hi at base + b * cstride + (s * rows + r) * 32 and lo at + lo (fp16
 // bit patterns). Written by the dataflow panel kernel for the rows below the panel's diagonal
@@ -103,8 +103,10 @@ struct Planes16 {
     int64_t lo;
     int rows;
 };
+
+// ---- chol32_panel.hip: in-panel steps of the fp32 factorisations ----------------------------
 // tile columns [K, K+ncols) of an outer panel (diagonal tile (K, K) already factored) in one
-// dataflow launch (chol32.hip: per-(chain, row) progress words prog[b * pstride + row], monotonic
+// dataflow launch (per-(chain, row) progress words prog[b * pstride + row], monotonic
 // base per factorisation and panel); returns the launch's workgroup count (its tickets), 0 when
 // nothing was launched, -1 for a panel wider than the progress word allows. pl.base != nullptr:
 // the rows below the diagonal block (row tiles < pl.rows / 64) also write the panel's planes.
@@ -115,7 +117,7 @@ long launch_chol_panel_df32(MatF A, int K, int ncols, int R, FusedDiag<float> fd
                             int64_t pstride, unsigned long long base, SpinCtl sc, hipStream_t s,
                             Planes16 pl = Planes16{nullptr, 0, 0, 0}, int rhs_as = -1,
                             const int* inv_skip = nullptr);
-// explicit-inverse panel of the Newton factorisation (chol32.hip), after a dataflow launch over
+// explicit-inverse panel of the Newton factorisation, after a dataflow launch over
 // the diagonal block [K, K+8) and the right-hand-side row (rhs_as): Z = inv(L_D) of the 512x512
 // diagonal block as fp16x3 planes (zpl, 512 rows), by recursive doubling over fp32 scratch (zt:
 // 3 x 512 x 512 per chain, zstride floats apart); then every row tile i in [K+8, nb) becomes
@@ -132,32 +134,43 @@ void launch_chol_panel_bulk32(MatF A, int K, int ncols, int row0, int R, int zro
                               FusedDiag<float> fd, Live live, int nchains, int hlim,
                               const int* h3ok, hipStream_t s,
                               Planes16 pl = Planes16{nullptr, 0, 0, 0});
+
+// ---- chol32_update.hip: trailing updates of the fp32 factorisations -------------------------
 void launch_chol_update32(MatF A, int k0, int kc, const unsigned* tiles, int ntiles, Live live,
                           int nchains, hipStream_t s,
                           FusedDiag<float> fd = FusedDiag<float>{0, nullptr, 0, nullptr, 0, 0},
                           int hlim = 0, const int* h3ok = nullptr);
 // the same update with one 128x128 super-tile per workgroup (tiles from build_update_supertiles);
-// hlim > 0: fp16x3 operands (chol32.hip) for super-tiles whose rows lie below row tile hlim, in
-// the chains b with h3ok[b] != 0 (h3ok == nullptr: every chain); the others take fp32 operands.
+// hlim > 0: fp16x3 operands for super-tiles whose rows lie below row tile hlim, in the chains b
+// with h3ok[b] != 0 (h3ok == nullptr: every chain); the others take fp32 operands.
 // rhs >= 0: row tile rhs is the appended right-hand side whose first row alone is data (its
 // super-tiles must hold it alone: build_update_supertiles(..., solo = rhs)); it is updated as a
-// row-vector product (fp64 accumulation) instead of a 64-row tile product
+// row-vector product (fp64 accumulation) instead of a 64-row tile product.
+// role: which launch population this is (the kernel's ROLE: each has its own instantiation and so
+// its own profiler figures). The caller states it; pl (k0's panel's planes) goes with
+// UPD32_NEWTON_PLANES and with no other role, else the launcher throws.
+enum {
+    UPD32_NEWTON = 0,         // the Newton factorisation, fp16x3 operands split while staged
+    UPD32_POST = 1,           // the posterior factor's bottom block (same code)
+    UPD32_NEWTON_PLANES = 2,  // the Newton factorisation, fp16x3 operands from the planes
+};
 void launch_chol_update32_t128(MatF A, int k0, int kc, const unsigned* tiles, int ntiles,
                                Live live, int nchains, hipStream_t s,
                                FusedDiag<float> fd = FusedDiag<float>{0, nullptr, 0, nullptr, 0, 0},
                                int hlim = 0, const int* h3ok = nullptr, int rhs = -1,
-                               int role = 0,  // 1: the posterior bottom block, 3: the rhs row
-                                              // alone (names only)
-                               Planes16 pl = Planes16{nullptr, 0, 0, 0});  // k0's panel's planes
-// the far trailing updates of the Newton factorisation on 256x256 quad tiles (chol32.hip): fp16x3
-// operands from the planes only, rows below the appended right-hand side, chains with h3ok set
+                               int role = UPD32_NEWTON, Planes16 pl = Planes16{nullptr, 0, 0, 0});
+// the far trailing updates of the fp32 factorisations on 256x256 quad tiles: fp16x3 operands
+// from the planes only, rows below the appended right-hand side, chains with h3ok set
+// (role: UPD32_NEWTON or UPD32_POST)
 void launch_chol_update32_q256(MatF A, int k0, int kc, const unsigned* quads, int nq, Live live,
                                int nchains, hipStream_t s, const int* h3ok, Planes16 pl,
-                               int role = 0);
-std::vector<unsigned> build_update_quads(int i0, int R, int j0, int jend);
-// solo >= 0: row tile solo gets super-tile rows of its own (never paired with another row tile)
-std::vector<unsigned> build_update_supertiles(int i0, int R, int j0, int jend, int glo, int ghi,
-                                              int solo = -1);
+                               int role = UPD32_NEWTON);
+// the appended right-hand-side row beside the quad tiles, whose lists stop above it: tiles = the
+// super-tiles of row tile rhs alone (build_update_supertiles(rhs, rhs + 1, ..., solo = rhs))
+void launch_rhs_row_update32(MatF A, int k0, int kc, const unsigned* tiles, int ntiles, Live live,
+                             int nchains, hipStream_t s);
+
+// ---- newton_solve.hip: K b, TRSV and fp64 refinement of the mixed-precision Newton solve ----
 // y = K x from K's lower tiles (part: nb*nb*64 doubles per chain of partials); Bf.base != null
 // also forms the fp32 Newton matrix I + W^1/2 K W^1/2 and its right-hand-side block (x = b)
 void launch_symv(MatB K, const double* x, int64_t xstride, double* y, int64_t ystride,

@@ -253,7 +253,7 @@ int apm_theta_eval(apm_ctx* c, int est, int64_t count, const double* thetas, int
     try {
         HIPC(hipSetDevice(c->device));
         const double* th = upload_thetas(c, count, thetas, ldt);
-        // fp16x3 Newton updates need |L_ij| <= sqrt(1 + K_ii) < 65504 (chol32.hip): per chain;
+        // fp16x3 Newton updates need |L_ij| <= sqrt(1 + K_ii) < 65504 (chol32_update.hip): per chain;
         // the posterior bottom block's operands |L'_ij| <= sqrt(1 + n K_ii) (postcov.hip)
         for (int64_t b = 0; b < count; ++b) {
             pin_h3(c)[b] = c->h3 && th[b * c->P] < 19.0;
@@ -282,7 +282,7 @@ int apm_theta_eval_K(apm_ctx* c, int est, const double* K, int64_t ldk, int64_t 
         HIPC(hipSetDevice(c->device));
         std::vector<double> Kp;  // (alive until theta_eval_impl's syncs)
         const double kmax = upload_padded_K(c, K, ldk, Kp);
-        pin_h3(c)[0] = c->h3 && kmax < 1.8e8;  // sqrt(1 + K_ii) < 1.4e4 (chol32.hip)
+        pin_h3(c)[0] = c->h3 && kmax < 1.8e8;  // sqrt(1 + K_ii) < 1.4e4 (chol32_update.hip)
         pin_inv(c)[0] = 1.0 + kmax < 32768.0;
         pin_h3post(c)[0] = c->h3 && 1.0 + c->n * kmax < 4e8;
         pin_icm(c)[0] = c->n * kmax / std::max(c->icm_q, 1.0);

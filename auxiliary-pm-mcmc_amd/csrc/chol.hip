@@ -360,7 +360,7 @@ void launch_chol_update(MatB A, int k0, int kc, const unsigned* tiles, int ntile
 }
 
 // ------------------------------------------------------------------------- 128x128 trailing update
-// The fp64 twin of chol32.hip's k_chol_update32_t128 (super-tile entries and validity rules of
+// The fp64 twin of chol32_update.hip's k_chol_update32_t128 (super-tile entries and validity rules of
 // build_update_supertiles): one 128x128 super-tile per workgroup, each wave a 64x64 tile as 4x4
 // v_mfma_f64_16x16x4_f64 accumulators (128 VGPRs). Per byte staged it feeds twice the MFMAs of the
 // 64x64 kernel, whose operand-load rate co-limits it. Operands move global -> LDS with 16-byte
@@ -564,21 +564,6 @@ void launch_chol_update_t128(MatB A, int k0, int kc, const unsigned* tiles, int 
     const long total = (long)ntiles * nchains;
     APM_LAUNCH(k_chol_update_t128, dim3((unsigned)total), dim3(256), 0, s, A, k0, kc,
                        tiles, ntiles, nchains, plus, live, fd, S);
-}
-
-// Host: tiles (i, j), i in [i0, R), j0 <= j <= min(i, jend-1), in super-tile order (SxS tiles,
-// super-rows top-down, super-columns left-right, row-major inside), packed (i << 16) | j.
-std::vector<unsigned> build_update_tiles(int i0, int R, int j0, int jend, int glo, int ghi) {
-    std::vector<unsigned> v;
-    const int S = 8;
-    for (int I = i0; I < R; I += S)
-        for (int J = j0; J < jend; J += S)
-            for (int i = I; i < std::min(I + S, R); ++i) {
-                if (i >= glo && i < ghi) continue;
-                for (int j = J; j < std::min(J + S, jend); ++j)
-                    if (j <= i) v.push_back(((unsigned)i << 16) | (unsigned)j);
-            }
-    return v;
 }
 
 // ------------------------------------------------------------------------------- L^T z = r

@@ -1,6 +1,6 @@
 // Factorisation of one 64x64 diagonal tile (Cholesky + inverse of the factor), shared by the
 // stand-alone diag kernel (chol.hip) and the trailing-update kernels that fuse it into the
-// workgroup that produces the tile (chol.hip, chol32.hip).
+// workgroup that produces the tile (chol.hip, chol32_update.hip, chol32_panel.hip).
 //
 // One wave, no barriers, blocked by 16: per 16-column block the 16x16 diagonal block is factored
 // with lane r holding row r in registers (pivot by v_readlane, column broadcast through LDS,

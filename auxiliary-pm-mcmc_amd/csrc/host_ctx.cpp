@@ -75,7 +75,7 @@ void upload_idx(apm_ctx* c, int count, const int64_t* slots, const int64_t* ubuf
 
 // per-chain range flags of a theta-call (staged by the entry point in pin_h3 / pin_h3post /
 // pin_inv, the layout of the device block h3ok .. h3ok + 3B, uploaded with one copy, and the icm
-// thresholds in pin_icm) -> device. fp16x3 operands (chol32.hip): the walk's and
+// thresholds in pin_icm) -> device. fp16x3 operands (chol32_update.hip): the walk's and
 // the trailing updates' operands are solved entries of L, |L_ij| <= sqrt(B_ii) <= sqrt(1 + K_ii)
 // (probit W < 1, logit W <= 1/4); the explicit-inverse panel also splits Schur-complement
 // entries of B itself, |A_ij| <= max B_ii <= 1 + K_ii, so its flag asks 1 + K_ii < 2^15 (fp16

@@ -1,5 +1,5 @@
 // The Newton loop of laplace_approximation: the fp32 factorisation of the Newton matrix
-// (chol32.hip) in the memory of the work matrix with its one-panel lookahead, the solve with
+// (chol32_panel.hip, chol32_update.hip) in the memory of the work matrix with its one-panel lookahead, the solve with
 // fp64 iterative refinement, the loop itself and the IS estimator's fp64 rerun.
 #include "apm_host.h"
 
@@ -48,8 +48,9 @@ void tracked_update32(apm_ctx* c, MatF M, int k0, int kc, int i0, int R, int j0,
         fd = FusedDiag<float>{1, dinv32_of(c), 2 * c->dstride, c->ldet, c->lstride, fail_code};
     const bool outer = kc >= 2 && jend - j0 >= 2 && (fuse_k < 0 || (i0 == fuse_k && j0 == fuse_k));
     // the Newton matrix's appended right-hand-side row tile (nb, rows < R) is updated as a row
-    // vector (rhs_row_update32); with the quad tiles that row is a launch of its own (role 3,
-    // outside the profiled scope: the roofline's launches are the quad and 128-row GEMMs)
+    // vector (rhs_row_update32); with the quad tiles that row is a launch of its own
+    // (k_rhs_row_update32, outside the profiled scope: the roofline's launches are the quad and
+    // 128-row GEMMs)
     const int rhs = R > c->nb || jext > 0 ? c->nb : -1;
     const bool quad =
         outer && pl.base && fuse_k < 0 && c->h3_all && i0 < c->nb && jext <= 0;
@@ -67,7 +68,8 @@ void tracked_update32(apm_ctx* c, MatF M, int k0, int kc, int i0, int R, int j0,
             const auto sl = jext > jend ? super_list_ext(c, i0, R, j0, jend, rhs, jext)
                                                     : super_list(c, i0, R, j0, jend, Gap{0, 0}, rhs);
             launch_chol_update32_t128(M, k0, kc, sl.first, sl.second, live_of(c), count, st, fd,
-                                      c->h3_now ? c->nb : 0, c->h3ok, rhs, 0, pl);
+                                      c->h3_now ? c->nb : 0, c->h3ok, rhs,
+                                      pl.base ? UPD32_NEWTON_PLANES : UPD32_NEWTON, pl);
         } else {
             launch_chol_update32(M, k0, kc, tl.first, tl.second, live_of(c), count, st, fd,
                                  c->h3_now ? c->nb : 0, c->h3ok);
@@ -75,8 +77,7 @@ void tracked_update32(apm_ctx* c, MatF M, int k0, int kc, int i0, int R, int j0,
     }
     if (quad && R > c->nb) {
         const auto sl = super_list(c, c->nb, R, j0, jend, Gap{0, 0}, rhs);
-        launch_chol_update32_t128(M, k0, kc, sl.first, sl.second, live_of(c), count, st, fd,
-                                  c->nb, c->h3ok, rhs, 3, pl);
+        launch_rhs_row_update32(M, k0, kc, sl.first, sl.second, live_of(c), count, st);
     }
 }
 
@@ -148,7 +149,7 @@ void chol_range32(apm_ctx* c, MatF M, int k0, int k1, int R, int Cb, int fail_co
 }
 
 // B x = W^1/2 K b with the fp32 factor (its forward solve is the appended row np) and n_refine
-// steps of fp64 iterative refinement; x -> v.z (chol32.hip)
+// steps of fp64 iterative refinement; x -> v.z (newton_solve.hip)
 void newton_solve32(apm_ctx* c, int count) {
     const Live lv = live_of(c);
     hipStream_t s = c->stream;

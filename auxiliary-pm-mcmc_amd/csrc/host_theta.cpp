@@ -150,12 +150,12 @@ void post_bottom32_steps(apm_ctx* c, int count, int K, int Kend, hipStream_t s) 
     if (pl.base) {  // 256x256 quad tiles from the planes (bitwise the split-while-staged kernel)
         const auto ql = quad_list(c, row0, 2 * nb, Kend, nb);
         launch_chol_update32_q256(S, K, Kend - K, ql.first, ql.second, lv, count, s, c->h3post,
-                                  pl, /*role: the posterior bottom block*/ 1);
+                                  pl, UPD32_POST);
     } else {
         const auto sl = super_list(c, row0, 2 * nb, Kend, nb, Gap{0, 0});
         launch_chol_update32_t128(S, K, Kend - K, sl.first, sl.second, lv, count, s,
                                   FusedDiag<float>{0, nullptr, 0, nullptr, 0, 0}, hlim, c->h3post,
-                                  -1, /*role: the posterior bottom block*/ 1);
+                                  -1, UPD32_POST);
     }
 }
 

@@ -177,7 +177,7 @@ def test_invalid_covariance_check_off_is_pushthrough(nat, monkeypatch, name):
 
 def test_forced_spin_timeouts_never_return_wrong_values(nat, monkeypatch):
     """The Newton solve's in-launch hand-overs (the dataflow panel k_chol_panel_df32, the
-    multi-workgroup TRSV k_trsv32_mw) wait with bounded spins (chol32.hip SpinCtl). With the
+    multi-workgroup TRSV k_trsv32_mw) wait with bounded spins (SpinCtl, apm_internal.h). With the
     bound forced to one poll (APM_SPIN_LIMIT=1, read at context creation) the waits time out:
     every exit must be counted and must fail its chain, which the Newton loop reruns in fp64 -
     so each chain comes back with status 0 and the value of an undisturbed context (within the

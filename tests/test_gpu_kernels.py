@@ -333,8 +333,8 @@ def _run_is(nat, X, y, thetas, ns, monkeypatch, **env):
 
 
 def test_mixed_newton_matches_fp64(nat, monkeypatch):
-    """The fp32 factorisation of B + fp64 refinement (chol32.hip) reproduces the fp64 Newton mode
-    within the f_post tolerance, 1e-8 of its maximum (~1e-12 with the dataflow
+    """The fp32 factorisation of B + fp64 refinement (newton_solve.hip) reproduces the fp64 Newton
+    mode within the f_post tolerance, 1e-8 of its maximum (~1e-12 with the dataflow
     walk, ~1e-9 with the explicit-inverse panels, whose fp16x3 product with inv(L_D) leaves a
     less accurate factor for the refinement to correct), and hence the estimate, for
     sigma = e^0..e^4."""
@@ -349,8 +349,8 @@ def test_mixed_newton_matches_fp64(nat, monkeypatch):
 
 
 def test_fp16x3_updates_match_fp32_operands(nat, monkeypatch):
-    """fp16x3 trailing updates of the Newton factor (chol32.hip, default) against fp32 operands
-    (APM_H3=0, which also walks every panel: the explicit-inverse panels need the planes): same
+    """fp16x3 trailing updates of the Newton factor (chol32_update.hip, default) against fp32
+    operands (APM_H3=0, which also walks every panel: the explicit-inverse panels need the planes): same
     iteration counts, modes within the f_post tolerance (1e-8 of the maximum), estimates to 1e-6.
     The range
     guard is per chain: a chain at theta_0 >= 19 takes fp32 operands (bit-identical to APM_H3=0)
@@ -397,7 +397,7 @@ def _run_is_stats(nat, X, y, thetas, ns, monkeypatch, **env):
 
 @pytest.mark.parametrize('n', [2048, 1700, 700])
 def test_panel_forms_are_batch_independent(nat, monkeypatch, n):
-    """The Newton factorisation takes, per chain, the explicit-inverse panel (chol32.hip
+    """The Newton factorisation takes, per chain, the explicit-inverse panel (chol32_panel.hip
     k_zinv_level32 + k_panel_inv_gemm32, chains with 1 + K_ii < 2^15), the dataflow walk with
     fp16x3 operands (1 + K_ii >= 2^15, theta_0 < 19) or the walk with fp32 operands
     (theta_0 >= 19); a batch whose chains all take the first runs compact dataflow launches and

@@ -1,7 +1,7 @@
 """Can the Newton loop skip the fp64 refinement of its early solves?
 
 The IS theta-call's Newton iterations (latent_posterior_approximations.py:85-99) solve
-B x = W^1/2 K b with an fp32 factor of B and refine x in fp64 (chol32.hip). An early iterate's
+B x = W^1/2 K b with an fp32 factor of B and refine x in fp64 (newton_solve.hip). An early iterate's
 solve error is damped by the Newton map's contraction (its derivative vanishes at the mode), so an
 unrefined solve there may leave f_post and n_iter unchanged. This study runs the iteration in
 float64 with the solves of the iterations the rule marks as unrefined replaced by an fp32 solve

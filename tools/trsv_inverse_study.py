@@ -1,6 +1,6 @@
 """Can the Newton solves use explicit inverses of 512-wide diagonal blocks?
 
-The device solves B x = r with the fp32 factor L of B (chol32.hip) by substitution over 64-wide
+The device solves B x = r with the fp32 factor L of B (newton_solve.hip) by substitution over 64-wide
 blocks (inverses of the 64x64 diagonal tiles, fp64 vectors), then refines once in fp64. A solve
 over 512-wide blocks against fp32 explicit inverses of the 512x512 diagonal blocks would have 8
 instead of 64 dependent steps. This study (numpy; the bench's data, Newton matrices of the

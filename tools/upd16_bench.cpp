@@ -1,10 +1,10 @@
 // Microbenchmark of the Newton factor's trailing update (k_chol_update32_t128: fp32 operands and
 // fp16x3 split while staging) on random data, Newton-matrix shape at N=4096, 64 chains
-// (development tool). Ablations:
-// -DH3_ABL=1 every slice reads slice 0 (operands cache-resident), =2 no MFMA.
+// (development tool).
 // hipcc --offload-arch=gfx950 -O3 -x hip tools/upd16_bench.cpp -o tools/upd16.bin
 #define APM_TOOL_NO_SKEW
-#include "../auxiliary-pm-mcmc_amd/csrc/chol32.hip"
+#include "../auxiliary-pm-mcmc_amd/csrc/chol32_update.hip"
+#include "../auxiliary-pm-mcmc_amd/csrc/tile_lists.cpp"
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -65,8 +65,8 @@ int main(int argc, char** argv) {
             float ms;
             hipEventElapsedTime(&ms, e0, e1);
             const double fl = flops_of(c.i0, R, c.i0, Cb, c.kc) * chains * reps;
-            printf("ABL=%d %s %-20s supertiles %5zu x %d: %8.3f ms/launch %7.2f TFLOP/s (fp32-eq)\n",
-                   H3_ABL, h3 ? "fp16x3" : "fp32  ", c.name, t.size(), chains, ms / reps,
+            printf("%s %-20s supertiles %5zu x %d: %8.3f ms/launch %7.2f TFLOP/s (fp32-eq)\n",
+                   h3 ? "fp16x3" : "fp32  ", c.name, t.size(), chains, ms / reps,
                    fl / (ms * 1e-3) / 1e12);
         }
         hipFree(dt);

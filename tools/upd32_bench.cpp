@@ -6,7 +6,8 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -x hip tools/upd32_bench.cpp -o tools/upd32.bin
 //   tools/upd32.bin [chains=64] [K=0] [reps=10]
 #define APM_TOOL_NO_SKEW
-#include "../auxiliary-pm-mcmc_amd/csrc/chol32.hip"
+#include "../auxiliary-pm-mcmc_amd/csrc/chol32_update.hip"
+#include "../auxiliary-pm-mcmc_amd/csrc/tile_lists.cpp"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,11 +22,7 @@ __global__ void k_fill_planes(const float* A, int64_t ld, int64_t cs, int np, in
     const int b = blockIdx.y;
     if (e >= n) return;
     const int r = (int)(e / (64 * kc)), col = (int)(e % (64 * kc));
-    const float v = A[b * cs + (int64_t)r * ld + k0 * 64 + col];
-    const _Float16 h = (_Float16)v, l = (_Float16)(v - (float)h);
-    const int64_t o = b * pl.cstride + ((int64_t)(col >> 5) * pl.rows + r) * 32 + (col & 31);
-    pl.base[o] = __builtin_bit_cast(unsigned short, h);
-    pl.base[o + pl.lo] = __builtin_bit_cast(unsigned short, l);
+    plane_put(pl.base + b * pl.cstride, pl, r, col, A[b * cs + (int64_t)r * ld + k0 * 64 + col]);
 }
 
 static double upd_flops(int i0, int R, int j0, int jend, int kc) {
@@ -93,7 +90,7 @@ int main(int argc, char** argv) {
                            dim3(256), 0, 0, A0, ld, cs, np, k0, kc, pl);
     };
     // UPD_Q256=1 (with UPD_PLANES=1): 256x256 quad tiles for the rows above the right-hand side,
-    // the 128-row kernel for that row alone
+    // k_rhs_row_update32 for that row
     const char* qe = getenv("UPD_Q256");
     const bool q256 = qe && atoi(qe) && pl.base;
     std::vector<unsigned> ql = build_update_quads(Kend, nb, Kend, nb);
@@ -106,11 +103,10 @@ int main(int argc, char** argv) {
     auto launch = [&]() {
         if (q256) {
             launch_chol_update32_q256(M, k0, kc, dql, (int)ql.size(), lv, chains, nullptr, h3, pl);
-            launch_chol_update32_t128(M, k0, kc, drl, (int)rl.size(), lv, chains, nullptr, fd, nb,
-                                      h3, rhs, 0, pl);
+            launch_rhs_row_update32(M, k0, kc, drl, (int)rl.size(), lv, chains, nullptr);
         } else {
             launch_chol_update32_t128(M, k0, kc, dsl, (int)sl.size(), lv, chains, nullptr, fd, nb,
-                                      h3, rhs, 0, pl);
+                                      h3, rhs, pl.base ? UPD32_NEWTON_PLANES : UPD32_NEWTON, pl);
         }
     };
     // checksum of one launch from the pristine matrix

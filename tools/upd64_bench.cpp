@@ -1,9 +1,9 @@
 // Microbenchmark of the fp64 128x128 trailing update (k_chol_update_t128) on random data at the
 // chol(K) shape of N=4096 (development tool). Ablations: -DT64_ABL=1 no MFMA, =2 no operand loads.
-// hipcc --offload-arch=gfx950 -O3 -std=c++17 -x hip tools/upd64_bench.cpp \
-//     auxiliary-pm-mcmc_amd/build/chol32.hip.o -o tools/upd64.bin
+// hipcc --offload-arch=gfx950 -O3 -std=c++17 -x hip tools/upd64_bench.cpp -o tools/upd64.bin
 #define APM_TOOL_NO_SKEW
 #include "../auxiliary-pm-mcmc_amd/csrc/chol.hip"
+#include "../auxiliary-pm-mcmc_amd/csrc/tile_lists.cpp"
 #include <cstdio>
 #include <cstdlib>
 #include <vector>

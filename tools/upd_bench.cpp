@@ -2,6 +2,7 @@
 // hipcc --offload-arch=gfx950 -O3 -DUPD_KS=16 -x hip tools/upd_bench.cpp -o tools/upd_ks16.bin
 #define APM_TOOL_NO_SKEW
 #include "../auxiliary-pm-mcmc_amd/csrc/chol.hip"
+#include "../auxiliary-pm-mcmc_amd/csrc/tile_lists.cpp"
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
