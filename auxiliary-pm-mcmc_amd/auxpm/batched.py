@@ -54,7 +54,8 @@ __all__ = ['BatchedAPMEllSSPlusRandDirSliceSampler', 'BatchedAPMEllSSPlusMHSampl
            'BatchedAPMMetIndPlusMHSampler', 'BatchedAPMMetIndPlusSeqSliceSampler',
            'BatchedAPMEllSSPlusEllSSSampler', 'chain_streams']
 
-_EST = {'is': _native.EST_IS, 'priormc': _native.EST_PRIORMC, 'laplace': _native.EST_LAPLACE}
+_EST = {'is': _native.EST_IS, 'priormc': _native.EST_PRIORMC, 'laplace': _native.EST_LAPLACE,
+        'is_ep': _native.EST_IS_EP}
 
 
 def chain_streams(seed, n_chains, first_chain=0):
@@ -83,7 +84,7 @@ class _BatchedChains(object):
 
     def __init__(self, X, y, n_chains, n_imp, prior, kernel='ard', epsilon=1e-8,
                  max_slice_iters=1000, seed=0, estimator='is', device=None, first_chain=0,
-                 likelihood='probit'):
+                 likelihood='probit', ep_settings=None):
         _native.likelihood_code(likelihood)  # ('probit' | 'logit'; ValueError otherwise)
         self.likelihood = likelihood
         self.n_chains = int(n_chains)
@@ -96,6 +97,10 @@ class _BatchedChains(object):
         C = self.n_chains
         self.ctx = _native.Context(X, y, kind, epsilon, n_imp, max_batch=C, n_slots=2 * C,
                                    n_ubufs=3 * C, device=device, likelihood=likelihood)
+        # the EP fit of 'is_ep' theta-calls: dict of damping / diff_tol / max_sweeps (probit only)
+        self.ep_settings = None if ep_settings is None else dict(ep_settings)
+        if self.ep_settings is not None:
+            self.ctx.set_ep(**self.ep_settings)
         self.P = self.ctx.theta_len
         self.slot_cur = np.arange(C, dtype=np.int64)
         self.slot_prop = np.arange(C, 2 * C, dtype=np.int64)
@@ -376,10 +381,10 @@ class BatchedAPMEllSSPlusRandDirSliceSampler(_BatchedChains):
 
     def __init__(self, X, y, n_chains, n_imp, prior, kernel='ard', epsilon=1e-8, w=1.,
                  max_steps_out=0, max_slice_iters=1000, seed=0, estimator='is', device=None,
-                 first_chain=0, likelihood='probit'):
+                 first_chain=0, likelihood='probit', ep_settings=None):
         super(BatchedAPMEllSSPlusRandDirSliceSampler, self).__init__(
             X, y, n_chains, n_imp, prior, kernel, epsilon, max_slice_iters, seed, estimator,
-            device, first_chain, likelihood=likelihood)
+            device, first_chain, likelihood=likelihood, ep_settings=ep_settings)
         self.w = float(w)
         self.max_steps_out = int(max_steps_out)
         C = self.n_chains
@@ -748,10 +753,10 @@ class BatchedAPMEllSSPlusMHSampler(_BatchedMHMixin, _BatchedChains):
 
     def __init__(self, X, y, n_chains, n_imp, prior, prop_scales, kernel='ard', epsilon=1e-8,
                  metropolis=False, max_slice_iters=1000, seed=0, estimator='is', device=None,
-                 first_chain=0, likelihood='probit'):
+                 first_chain=0, likelihood='probit', ep_settings=None):
         super(BatchedAPMEllSSPlusMHSampler, self).__init__(
             X, y, n_chains, n_imp, prior, kernel, epsilon, max_slice_iters, seed, estimator,
-            device, first_chain, likelihood=likelihood)
+            device, first_chain, likelihood=likelihood, ep_settings=ep_settings)
         self._init_mh(prop_scales, metropolis)
 
     def _mh_theta(self):
@@ -784,10 +789,10 @@ class BatchedPMMHSampler(_BatchedMHMixin, _BatchedChains):
 
     def __init__(self, X, y, n_chains, n_imp, prior, prop_scales, kernel='iso', epsilon=1e-8,
                  metropolis=False, seed=0, estimator='is', device=None, first_chain=0,
-                 likelihood='probit'):
+                 likelihood='probit', ep_settings=None):
         super(BatchedPMMHSampler, self).__init__(
             X, y, n_chains, n_imp, prior, kernel, epsilon, 1000, seed, estimator, device,
-            first_chain, likelihood=likelihood)
+            first_chain, likelihood=likelihood, ep_settings=ep_settings)
         self._init_mh(prop_scales, metropolis)
 
     def set_estimator(self, estimator):
@@ -853,10 +858,10 @@ class BatchedAPMMetIndPlusSeqSliceSampler(BatchedAPMEllSSPlusRandDirSliceSampler
 
     def __init__(self, X, y, n_chains, n_imp, prior, ws, kernel='ard', epsilon=1e-8,
                  max_steps_out=0, max_slice_iters=1000, seed=0, estimator='is', device=None,
-                 first_chain=0, likelihood='probit'):
+                 first_chain=0, likelihood='probit', ep_settings=None):
         super(BatchedAPMMetIndPlusSeqSliceSampler, self).__init__(
             X, y, n_chains, n_imp, prior, kernel, epsilon, 1., max_steps_out, max_slice_iters,
-            seed, estimator, device, first_chain, likelihood=likelihood)
+            seed, estimator, device, first_chain, likelihood=likelihood, ep_settings=ep_settings)
         self.ws = np.array(np.broadcast_to(np.asarray(ws, dtype=np.float64), (self.P,)))
 
     def _u_update(self, chains=None):
@@ -893,10 +898,10 @@ class BatchedAPMEllSSPlusEllSSSampler(BatchedAPMEllSSPlusRandDirSliceSampler):
 
     def __init__(self, X, y, n_chains, n_imp, theta_prior_std, kernel='ard', epsilon=1e-8,
                  max_slice_iters=1000, seed=0, estimator='is', device=None, first_chain=0,
-                 likelihood='probit'):
+                 likelihood='probit', ep_settings=None):
         super(BatchedAPMEllSSPlusEllSSSampler, self).__init__(
             X, y, n_chains, n_imp, {}, kernel, epsilon, 1., 0, max_slice_iters, seed, estimator,
-            device, first_chain, likelihood=likelihood)
+            device, first_chain, likelihood=likelihood, ep_settings=ep_settings)
         self.theta_prior_std = np.array(np.broadcast_to(
             np.asarray(theta_prior_std, dtype=np.float64), (self.P,)))
         C = self.n_chains

@@ -377,6 +377,9 @@ void launch_ep_sites(MatB A, MatB K, int n, int nb, NewtonVecs v, const double* 
 void launch_ep_chain(EpVecs e, NewtonVecs v, int n, int np, const double* ldet, int64_t lstride,
                      int nb, double diff_tol, int fail_code, int* active, int* status,
                      int* n_iter, int nchains, hipStream_t s);
+// per live chain after the stop sweep, for the IS theta-call's posterior factor and slot writer:
+// v.f <- v.fnew (mu) and exact zeros in rows [n, np) of v.f, v.W, v.Ws and v.a
+void launch_ep_handoff(NewtonVecs v, int n, int np, Live live, int nchains, hipStream_t s);
 
 // cache slot: fp32 factor with an extra TB-row block (row np holds g^T for apm_slot_read; the
 // estimate does not use it), plus fp64 vectors of the self-consistent epilogue (ugemm.hip)

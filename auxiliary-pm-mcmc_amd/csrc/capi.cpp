@@ -241,8 +241,11 @@ int apm_theta_eval(apm_ctx* c, int est, int64_t count, const double* thetas, int
                    const int64_t* ubufs, const int64_t* slots, double* out_logf, int* status,
                    int64_t* nops) {
     if (!c || count <= 0 || count > c->max_batch || !thetas || !out_logf || !status ||
-        est < 0 || est > 2 || c->kind == APM_KERNEL_PRECOMPUTED || ldt < c->P)
+        est < 0 || est > APM_EST_IS_EP || c->kind == APM_KERNEL_PRECOMPUTED || ldt < c->P)
         return fail(c, APM_E_INVALID, "apm_theta_eval: bad arguments");
+    if (est == APM_EST_IS_EP && c->lik != APM_LIK_PROBIT)
+        return fail(c, APM_E_INVALID, "apm_theta_eval: APM_EST_IS_EP is probit only (the logit's "
+                                      "tilted moments need quadrature)");
     if (est != APM_EST_LAPLACE) {
         if (!ubufs || !slots) return fail(c, APM_E_INVALID, "apm_theta_eval: ubufs/slots required");
         if (!check_idx(c, count, slots, c->n_slots, "slot") ||
@@ -272,8 +275,11 @@ int apm_theta_eval(apm_ctx* c, int est, int64_t count, const double* thetas, int
 
 int apm_theta_eval_K(apm_ctx* c, int est, const double* K, int64_t ldk, int64_t ubuf,
                      int64_t slot, double* out_logf, int* status, int64_t* nops) {
-    if (!c || !K || ldk < c->n || !out_logf || !status || est < 0 || est > 2)
+    if (!c || !K || ldk < c->n || !out_logf || !status || est < 0 || est > APM_EST_IS_EP)
         return fail(c, APM_E_INVALID, "apm_theta_eval_K: bad arguments");
+    if (est == APM_EST_IS_EP && c->lik != APM_LIK_PROBIT)
+        return fail(c, APM_E_INVALID, "apm_theta_eval_K: APM_EST_IS_EP is probit only (the "
+                                      "logit's tilted moments need quadrature)");
     if (est != APM_EST_LAPLACE &&
         (slot < 0 || slot >= c->n_slots || ubuf < 0 || ubuf >= c->n_ubufs))
         return fail(c, APM_E_INVALID, "apm_theta_eval_K: slot/ubuf out of range");

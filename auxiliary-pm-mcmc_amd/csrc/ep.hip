@@ -144,3 +144,41 @@ void launch_ep_chain(EpVecs e, NewtonVecs v, int n, int np, const double* ldet, 
     APM_LAUNCH(k_ep_chain, dim3(nchains), dim3(256), 0, s, e, v, n, np, ldet, lstride, nb,
                diff_tol, fail_code, active, status, n_iter);
 }
+
+// The hand-over of a converged fit to the posterior-factor and slot code of the IS theta-call
+// (host_theta.cpp), once per call after the stop sweep, live chains only. That
+// code reads the Newton vectors: f_post from v.f (post_cov_lk's right-hand side, the slot, the
+// guard's row residuals), W from v.W (the slot's z = a + W f_post = nu~), W^1/2 from v.Ws
+// (k_form_y2_rev, icm_check) and a from v.a. The stop sweep left tau~, S^1/2 and its a there, which
+// stay; mu of that sweep (v.fnew = K a) is written into v.f, so the state handed over does not rest
+// on k_ep_chain's mu_prev <- mu, and rows >= n of the four vectors are set to exact zeros, as the
+// factor's right-hand side row and the padded rows of Y2 = S^1/2 L_K expect them. Two rows per
+// thread, one 16-byte access per vector (vstride and np are multiples of 64).
+__global__ __launch_bounds__(256) void k_ep_handoff(NewtonVecs v, int n, int np, Live live) {
+    const int b = blockIdx.y;
+    if (!live_e(live, b)) return;
+    const int i = 2 * (blockIdx.x * 256 + threadIdx.x);
+    if (i >= np) return;
+    const int64_t o = b * v.vstride + i;
+    if (i + 1 < n) {
+        *reinterpret_cast<d2_t*>(v.f + o) = *reinterpret_cast<const d2_t*>(v.fnew + o);
+        return;
+    }
+    const d2_t zero = d2_t{0.0, 0.0};
+    if (i >= n) {
+        *reinterpret_cast<d2_t*>(v.f + o) = zero;
+        *reinterpret_cast<d2_t*>(v.W + o) = zero;
+        *reinterpret_cast<d2_t*>(v.Ws + o) = zero;
+        *reinterpret_cast<d2_t*>(v.a + o) = zero;
+        return;
+    }
+    // i = n - 1 (n odd): row i is the last training row, row i + 1 the first padded one
+    *reinterpret_cast<d2_t*>(v.f + o) = d2_t{v.fnew[o], 0.0};
+    *reinterpret_cast<d2_t*>(v.W + o) = d2_t{v.W[o], 0.0};
+    *reinterpret_cast<d2_t*>(v.Ws + o) = d2_t{v.Ws[o], 0.0};
+    *reinterpret_cast<d2_t*>(v.a + o) = d2_t{v.a[o], 0.0};
+}
+
+void launch_ep_handoff(NewtonVecs v, int n, int np, Live live, int nchains, hipStream_t s) {
+    APM_LAUNCH(k_ep_handoff, dim3((np / 2 + 255) / 256, nchains), dim3(256), 0, s, v, n, np, live);
+}

@@ -334,6 +334,21 @@ void theta_eval_impl(apm_ctx* c, int est, int count, bool gram, double* out_logf
         launch_slot_write(c->A, c->v, c->ldet, c->lstride, c->nb, c->Sl, c->d_slots, 1, c->n,
                           c->np, lv, count, c->stream);
         u_eval_device(c, count, true);
+    } else if (est == APM_EST_IS_EP) {
+        // the IS estimator around the EP fit: f_post = mu, W = tau~, z = nu~.
+        // No concurrent chol(K): the sweeps keep the rows of V^T in BL, where it would factor, so
+        // K is factored after the fit on the main stream (post_cov_lk without L_K). Chains whose
+        // fit failed carry their status and drop out of everything below through Live.
+        ep_fit(c, count, st_h);
+        launch_ep_handoff(c->v, c->n, c->np, lv, count, c->stream);
+        // the guard's 1/2 log|B| of the stop sweep's factor (fp64 here)
+        launch_guard_save(c->ldet, c->lstride, 0, c->nb, c->guard, c->max_batch, 0, lv, count,
+                          c->stream);
+        post_cov_lk(c, count, false);
+        launch_slot_write(c->A, c->v, c->ldet, c->lstride, c->nb, c->Sl, c->d_slots, 3, c->n,
+                          c->np, lv, count, c->stream, s32_of(c), c->guard_rows);
+        guard_check(c, lv, count);
+        u_eval_device(c, count, true);
     } else {
         if (ov) {
             // edge gram_k (main -> s2): K and BL's first outer panel written by the Gram, the
@@ -391,14 +406,16 @@ void theta_eval_impl(apm_ctx* c, int est, int count, bool gram, double* out_logf
                       RB{c->n_iter, (int)sizeof(int) * count, it_h.data()},
                       RB{c->Sl.chain_wide, (int)sizeof(int) * count, wide_h.data()}});
         const int64_t* hs = pin_slots(c);  // the call's slots
+        // (the follow-ups of the Laplace proposal's estimator apply to the EP proposal's alike)
+        const bool is_like = est == APM_EST_IS || est == APM_EST_IS_EP;
         std::vector<int> chk;  // bit 3: the reference's route to chol(C) is checked (icm_check)
         for (int b = 0; b < count; ++b)
-            if (st_h[b] == 0 && (wide_h[b] & 8) && est == APM_EST_IS) chk.push_back(b);
+            if (st_h[b] == 0 && (wide_h[b] & 8) && is_like) chk.push_back(b);
         std::vector<int> redo, rewrite;  // fp32 bottom blocks above the trace bound (bit 1);
         bool attached = false;           // wide slots whose fp64 factor was not written (bit 2)
         for (int b = 0; b < count; ++b) {  // (a guard-failed chain's slot was written too)
             if (st_h[b] != 0 && st_h[b] != APM_STATUS_GUARD) continue;
-            const bool rd = (wide_h[b] & 2) && est == APM_EST_IS && st_h[b] == 0;
+            const bool rd = (wide_h[b] & 2) && is_like && st_h[b] == 0;
             if (rd) redo.push_back(b);
             if ((wide_h[b] & 4) && !c->l64_h[hs[b]]) {
                 attach_l64(c, hs[b]);
@@ -448,6 +465,7 @@ void theta_eval_impl(apm_ctx* c, int est, int count, bool gram, double* out_logf
         if (nops) {
             if (est == APM_EST_PRIORMC) nops[b] = 1;                   // estimators.py:322
             else if (est == APM_EST_LAPLACE) nops[b] = it_h[b];        // lpa.py:441-443 (i)
+            else if (est == APM_EST_IS_EP) nops[b] = 2 * (int64_t)it_h[b] + 1 + 2;  // §16 + IS
             else nops[b] = (int64_t)it_h[b] + 1 + 2;                   // estimators.py:217
         }
     }

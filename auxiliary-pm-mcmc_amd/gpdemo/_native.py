@@ -19,6 +19,7 @@ KERNEL_M32_ISO, KERNEL_M32_ARD, KERNEL_M52_ISO, KERNEL_M52_ARD = 3, 4, 5, 6
 # the kinds with one length scale (theta has 2 entries; the others' has d + 1)
 _ISO_KINDS = (KERNEL_ISO, KERNEL_M32_ISO, KERNEL_M52_ISO)
 EST_IS, EST_PRIORMC, EST_LAPLACE = 0, 1, 2
+EST_IS_EP = 3  # EST_IS with the EP fit's posterior as the importance distribution (probit)
 LIK_PROBIT, LIK_LOGIT = 0, 1
 _LIKELIHOODS = {'probit': LIK_PROBIT, 'logit': LIK_LOGIT}
 APM_SUCCESS, APM_E_INVALID, APM_E_HIP, APM_E_NOMEM = 0, -1, -2, -3

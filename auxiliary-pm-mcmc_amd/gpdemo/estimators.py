@@ -219,19 +219,38 @@ class LogMarginalLikelihoodEPEstimator(_EstimatorBase):
 
 class LogMarginalLikelihoodApproxPosteriorISEstimator(_EstimatorBase):
     """Unbiased importance-sampling estimate of p(y | theta, X) with the Laplace posterior as
-    proposal (reference estimators.py:90-241). ``ns``: (n_data, n_imp_sample) N(0,1) draws."""
+    proposal (reference estimators.py:90-241). ``ns``: (n_data, n_imp_sample) N(0,1) draws.
 
-    def __init__(self, X, y, kernel_func, post_approx_func, likelihood='probit'):
-        _native.likelihood_code(likelihood)
+    With ``post_approx_func=ep_approximation`` the proposal is the posterior of the converged
+    expectation-propagation fit instead (``EST_IS_EP`` theta-calls; probit only:
+    ``likelihood='logit'`` raises ``NotImplementedError``). ``damping``, ``diff_tol`` and
+    ``max_sweeps`` are that fit's settings; ``n_cubic_ops`` then grows by two per sweep plus the
+    estimator's own three."""
+
+    def __init__(self, X, y, kernel_func, post_approx_func, likelihood='probit', damping=0.8,
+                 diff_tol=1e-8, max_sweeps=100):
+        lik = _native.likelihood_code(likelihood)
+        name = getattr(post_approx_func, '__name__', '')
         if not (getattr(post_approx_func, 'apm_fused', False) or
-                getattr(post_approx_func, '__name__', '') == 'laplace_approximation'):
+                name == 'laplace_approximation'):
             raise NotImplementedError(
-                'the device estimator fuses the Laplace approximation '
-                '(gpdemo.latent_posterior_approximations.laplace_approximation); got {0!r}'
-                .format(post_approx_func))
+                'the device estimator fuses the Laplace approximation or the EP approximation '
+                '(gpdemo.latent_posterior_approximations.laplace_approximation / '
+                'ep_approximation); got {0!r}'.format(post_approx_func))
+        self._est = _native.EST_IS_EP if name == 'ep_approximation' else _native.EST_IS
+        if self._est == _native.EST_IS_EP and lik != _native.LIK_PROBIT:
+            raise NotImplementedError('expectation propagation is implemented for the probit '
+                                      'likelihood only')
         super(LogMarginalLikelihoodApproxPosteriorISEstimator, self).__init__(
             X, y, kernel_func, likelihood)
         self.post_approx_func = post_approx_func
+        self.ep_settings = (float(damping), float(diff_tol), int(max_sweeps))
+
+    def _raise(self, status, ctx):
+        if self._est == _native.EST_IS_EP and status in (
+                _native.STATUS_CHOL_B, _native.STATUS_EP_CAVITY, _native.STATUS_MAXITER):
+            raise_for_ep_status(status, self.ep_settings[2])
+        _raise_for_status(status, ctx)
 
     def __call__(self, ns, theta=None, cached_results=None):
         if theta is None and cached_results is None:
@@ -239,11 +258,13 @@ class LogMarginalLikelihoodApproxPosteriorISEstimator(_EstimatorBase):
         ns = np.asarray(ns, dtype=np.float64)
         if cached_results is None:
             ctx = self._prob.ctx(ns.shape[1])
+            if self._est == _native.EST_IS_EP:
+                ctx.set_ep(*self.ep_settings)
             ctx.u_upload(_UBUF, ns)
             slot = ctx.slots.acquire()
-            cache = DeviceCache(ctx, slot, _native.EST_IS, self, theta)
-            out, st, nops = self._theta_call(_native.EST_IS, ctx, theta, _UBUF, slot)
-            _raise_for_status(int(st[0]), ctx)
+            cache = DeviceCache(ctx, slot, self._est, self, theta)
+            out, st, nops = self._theta_call(self._est, ctx, theta, _UBUF, slot)
+            self._raise(int(st[0]), ctx)
             self.n_cubic_ops += int(nops[0])
             return float(out[0]), cache
         ctx = cached_results._ctx

@@ -71,6 +71,11 @@ def ep_approximation(K, y, calc_cov=True, calc_lml=False, damping=0.8, diff_tol=
     return out
 
 
+# the IS estimator runs this approximation fused on the device (EST_IS_EP theta-calls) when it
+# is handed this function
+ep_approximation.apm_fused = True
+
+
 def raise_for_ep_status(status, max_sweeps):
     """The exception of an EP chain's status (include/apm.h), nothing for APM_STATUS_OK."""
     if status == _native.STATUS_OK:

@@ -82,6 +82,16 @@ extern "C" {
 #define APM_EST_IS 0       /* LogMarginalLikelihoodApproxPosteriorISEstimator */
 #define APM_EST_PRIORMC 1  /* LogMarginalLikelihoodPriorMCEstimator */
 #define APM_EST_LAPLACE 2  /* LogMarginalLikelihoodLaplaceEstimator */
+/* APM_EST_IS with the importance distribution N(mu, (K^-1 + diag tau~)^-1) of the converged
+ * expectation-propagation fit (apm_set_ep settings) in place of the Laplace
+ * posterior. Probit only: APM_E_INVALID on an APM_LIK_LOGIT context. The cache slot holds the
+ * same state as an APM_EST_IS slot (f_post = mu, W = tau~, z = nu~, cst = 1/2 mu^T nu~ -
+ * 1/2 log|B|), so apm_u_eval, apm_slot_read, apm_guard_read and the apm_cache_* calls serve it
+ * unchanged. status[i]: APM_STATUS_CHOL_B, APM_STATUS_EP_CAVITY or APM_STATUS_MAXITER of the fit,
+ * APM_STATUS_CHOL_K, APM_STATUS_CHOL_C or APM_STATUS_GUARD as for APM_EST_IS; a failed chain is
+ * treated as a failed APM_EST_IS chain. n_cubic_ops[i] = 2 n_sweeps + 1 + 2 (two per sweep,
+ * DESIGN.md §16, plus APM_EST_IS's own). apm_version() is unchanged: detect it by this macro. */
+#define APM_EST_IS_EP 3
 
 /* likelihoods p(y | f) of a label y in {-1, +1} (R&W §3.4; the reference has the probit only):
  *   PROBIT  Phi(y f)     the default of every context and of apm_laplace
