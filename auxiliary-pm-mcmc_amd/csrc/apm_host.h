@@ -414,6 +414,8 @@ void predict_buffers(apm_ctx* c);
 void predict_block(apm_ctx* c, int count, const double* xs, int ms);
 void grad_buffers(apm_ctx* c);
 void grad_block(apm_ctx* c, int count);
+// grad_block's second pass for the chains left live by ep_fit: d log Z_EP / d theta into c->gout
+void ep_grad_block(apm_ctx* c, int count);
 
 // ---- host_ep.cpp ----------------------------------------------------------------------------
 void ep_buffers(apm_ctx* c);

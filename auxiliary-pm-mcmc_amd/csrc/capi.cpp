@@ -719,6 +719,52 @@ int apm_ep_predict(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt,
     return APM_SUCCESS;
 }
 
+int apm_ep_grad(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, double* logz,
+                double* grad, int64_t ldg, int* status, int64_t* n_sweeps) {
+    if (!c) return fail(nullptr, APM_E_INVALID, "apm_ep_grad: null context");
+    if (c->lik != APM_LIK_PROBIT)
+        return fail(c, APM_E_INVALID, "apm_ep_grad: probit only (the logit's tilted moments need "
+                                      "quadrature)");
+    if (c->kind == APM_KERNEL_PRECOMPUTED)
+        return fail(c, APM_E_INVALID, "apm_ep_grad: needs an ISO or ARD context (dK/dtheta is "
+                                      "built on the device)");
+    if (count <= 0 || count > c->max_batch)
+        return fail(c, APM_E_INVALID, "apm_ep_grad: count outside [1, max_batch]");
+    if (ldt < c->P) return fail(c, APM_E_INVALID, "apm_ep_grad: ldt < theta length");
+    if (ldg < c->P) return fail(c, APM_E_INVALID, "apm_ep_grad: ldg < theta length");
+    if (!thetas || !grad || !status) return fail(c, APM_E_INVALID, "apm_ep_grad: bad arguments");
+    const SkewScope skew(c);
+    try {
+        HIPC(hipSetDevice(c->device));
+        std::vector<int> st_h;
+        const int ok = ep_gram_fit(c, count, thetas, ldt, st_h);
+        std::vector<int> it_h((size_t)count);
+        std::vector<double> lz((size_t)count), gh((size_t)count * c->P);
+        HIPC(hipMemcpyAsync(it_h.data(), c->n_iter, sizeof(int) * count, hipMemcpyDeviceToHost,
+                            c->stream));
+        HIPC(hipMemcpyAsync(lz.data(), c->ep.logz, sizeof(double) * count, hipMemcpyDeviceToHost,
+                            c->stream));
+        if (ok) {  // S^1/2 (v.Ws), a and the factor of each chain's last sweep are in place
+            grad_buffers(c);
+            ep_grad_block(c, (int)count);
+            HIPC(hipMemcpyAsync(gh.data(), c->gout, sizeof(double) * count * c->P,
+                                hipMemcpyDeviceToHost, c->stream));
+        }
+        sync(c);
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        for (int64_t b = 0; b < count; ++b) {
+            status[b] = st_h[b];
+            if (n_sweeps) n_sweeps[b] = it_h[b];
+            const bool good = st_h[b] == APM_STATUS_OK;
+            if (logz) logz[b] = good ? lz[b] : nan;
+            for (int p = 0; p < c->P; ++p) grad[b * ldg + p] = good ? gh[b * c->P + p] : nan;
+        }
+    } catch (const HipError& e) {
+        return fail(c, APM_E_HIP, e.msg);
+    }
+    return APM_SUCCESS;
+}
+
 int apm_ep(int device, const double* K, int64_t n, int64_t ldk, const double* y, int calc_cov,
            double damping, double diff_tol, int64_t max_sweeps, double* mu_out, double* var_out,
            double* tau_out, double* nu_out, double* C_out, int64_t ldc, double* logz_out,

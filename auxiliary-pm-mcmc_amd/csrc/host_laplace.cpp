@@ -1,6 +1,7 @@
 // What follows a Laplace fit on its last fp64 Newton factor: apm_laplace's covariance, the
 // predictive distribution at test inputs and the gradient of the log marginal likelihood, each
-// a pass of chol_solve_rows over free rows of the work matrix.
+// a pass of chol_solve_rows over free rows of the work matrix; and the gradient of log Z_EP on an
+// EP fit's last factor, which is the Laplace gradient's second pass.
 #include "apm_host.h"
 
 namespace apm_host {
@@ -75,24 +76,28 @@ void grad_buffers(apm_ctx* c) {
     c->gout = dalloc<double>(c, B * c->P);
 }
 
-void grad_block(apm_ctx* c, int count) {
+// The second pass and the contraction, shared by the Laplace and the EP gradient: diag(W^1/2)
+// (S^1/2 for EP) from v.Ws against the factor in A / Dinv -> -R in the bottom-right's lower tiles,
+// then M = 1/2 a a^T - 1/2 R + 1/2 (q g^T + g q^T) against dK/dtheta_j into gout. With t (the
+// Laplace gradient's K s2) q = s2 - R t is formed between the two; without it (EP, whose M has no
+// implicit term) q and g are zeroed, and k_grad_reduce's 1/2 (fma(a_i, a_k, -R_ik) + fma(0, g_k,
+// 0 q_k)) is 1/2 a_i a_k - 1/2 R_ik exactly.
+static void grad_contract(apm_ctx* c, int count, const double* t) {
     const Live lv = live_of(c);
     const int nb = c->nb, ns = (nb + 1) / 2, nst = ns * (ns + 1) / 2;
     const int64_t np = c->np, B = c->max_batch;
-    double *dS = c->gvec, *g = dS + B * np, *s2 = g + B * np, *t = s2 + B * np, *u = t + B * np,
-           *q = u + B * np;
-    launch_form_aug(c->K, c->A, c->v, c->np, lv, count, c->stream, /*lower_only=*/!c->k_full);
-    chol_solve_rows(c, c->A, nb, /*row_start=*/nb, /*R=*/2 * nb, /*Cb=*/nb, count);
-    launch_grad_rows(c->lik, c->A, c->K, c->n, nb, c->v.f, c->y, c->v.vstride, dS, g, s2, np, lv,
-                     count, c->stream);
-    launch_symv(c->K, s2, np, t, np, c->sympart, c->sstride, c->np, MatF{}, nullptr, 0, lv, count,
-                c->stream, c->symv_tpw);
+    double *g = c->gvec + B * np, *s2 = g + B * np, *u = c->gvec + 4 * B * np, *q = u + B * np;
     launch_grad_fill(c->A, c->v.Ws, c->v.vstride, nb, lv, count, c->stream);
     chol_solve_rows(c, c->A, nb, /*row_start=*/nb, /*R=*/2 * nb, /*Cb=*/2 * nb, count);
     const MatB Rn{c->A.base + np * c->A.ld + np, c->A.ld, c->A.cstride};  // -R, lower tiles
-    launch_symv(Rn, t, np, u, np, c->sympart, c->sstride, c->np, MatF{}, nullptr, 0, lv, count,
-                c->stream, c->symv_tpw);
-    launch_grad_q(s2, u, q, np, c->n, c->np, lv, count, c->stream);
+    if (t) {
+        launch_symv(Rn, t, np, u, np, c->sympart, c->sstride, c->np, MatF{}, nullptr, 0, lv, count,
+                    c->stream, c->symv_tpw);
+        launch_grad_q(s2, u, q, np, c->n, c->np, lv, count, c->stream);
+    } else {
+        HIPC(hipMemsetAsync(g, 0, sizeof(double) * count * np, c->stream));
+        HIPC(hipMemsetAsync(q, 0, sizeof(double) * count * np, c->stream));
+    }
     {   // bytes: the lower triangles of R and K (the inputs and vectors are small beside them)
         ProfScope ps(c, APM_PROF_GRAD_REDUCE, 8.0 * (double)c->n * (c->n + 1) * c->live_n);
         launch_grad_reduce(c->K, Rn, c->X, c->d, c->n, c->d, nb, c->theta, c->P, c->kind, c->v.a,
@@ -101,5 +106,24 @@ void grad_block(apm_ctx* c, int count) {
     }
     launch_grad_sum(c->gpart, (int64_t)nst * c->P, nst, c->P, c->gout, lv, count, c->stream);
 }
+
+void grad_block(apm_ctx* c, int count) {
+    const Live lv = live_of(c);
+    const int nb = c->nb;
+    const int64_t np = c->np, B = c->max_batch;
+    double *dS = c->gvec, *g = dS + B * np, *s2 = g + B * np, *t = s2 + B * np;
+    launch_form_aug(c->K, c->A, c->v, c->np, lv, count, c->stream, /*lower_only=*/!c->k_full);
+    chol_solve_rows(c, c->A, nb, /*row_start=*/nb, /*R=*/2 * nb, /*Cb=*/nb, count);
+    launch_grad_rows(c->lik, c->A, c->K, c->n, nb, c->v.f, c->y, c->v.vstride, dS, g, s2, np, lv,
+                     count, c->stream);
+    launch_symv(c->K, s2, np, t, np, c->sympart, c->sstride, c->np, MatF{}, nullptr, 0, lv, count,
+                c->stream, c->symv_tpw);
+    grad_contract(c, count, t);
+}
+
+// Gradient of log Z_EP w.r.t. theta for the chains left live by ep_fit: the stop
+// sweep's factor, S^1/2 (v.Ws) and a are in place and rows [np, 2np) of A (that sweep's V^T) are
+// free, so this is grad_block's second pass alone. grad_buffers() first.
+void ep_grad_block(apm_ctx* c, int count) { grad_contract(c, count, nullptr); }
 
 }  // namespace apm_host

@@ -77,6 +77,7 @@ _SIGS = {
     'apm_set_ep': (_i, [_p, _d, _d, _i64]),
     'apm_ep_eval': (_i, [_p, _i64, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _p]),
     'apm_ep_predict': (_i, [_p, _i64, _p, _i64, _p, _i64, _i64, _p, _p, _p, _i64, _p, _p]),
+    'apm_ep_grad': (_i, [_p, _i64, _p, _i64, _p, _p, _i64, _p, _p]),
     'apm_ep': (_i, [_i, _p, _i64, _i64, _p, _i, _d, _d, _i64, _p, _p, _p, _p, _p, _i64, _p, _p,
                     _p]),
     'apm_laplace': (_i, [_i, _p, _i64, _i64, _p, _i, _i, _d, _i64, _p, _p, _i64, _p, _p, _p]),
@@ -486,6 +487,25 @@ class Context(object):
                 mean[t0:].ctypes.data, var[t0:].ctypes.data, prob[t0:].ctypes.data, m,
                 st[t0:].ctypes.data, nsw[t0:].ctypes.data), self._h)
         return mean, var, prob, st, nsw
+
+    def ep_grad(self, thetas):
+        """log Z_EP and its gradient with respect to theta for every row of thetas, `max_batch`
+        at a time: ``(logz (T,), grad (T, P), status, n_sweeps)`` with NaN where status != 0
+        (include/apm.h apm_ep_grad)."""
+        th = np.atleast_2d(_f64(thetas))
+        if th.shape[1] < self.theta_len:
+            raise IndexError('Out of bounds on buffer access (axis 0)')
+        T, P = th.shape[0], self.theta_len
+        logz = np.full(T, np.nan)
+        grad = np.full((T, P), np.nan)
+        st = np.zeros(T, dtype=np.int32)
+        nsw = np.zeros(T, dtype=np.int64)
+        for t0 in range(0, T, self.max_batch):
+            cnt = min(self.max_batch, T - t0)
+            _check(self.lib.apm_ep_grad(
+                self._h, cnt, th[t0:].ctypes.data, th.shape[1], logz[t0:].ctypes.data,
+                grad[t0:].ctypes.data, P, st[t0:].ctypes.data, nsw[t0:].ctypes.data), self._h)
+        return logz, grad, st, nsw
 
     def u_eval(self, slots, ubufs):
         sl = np.ascontiguousarray(slots, dtype=np.int64)

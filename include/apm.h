@@ -15,6 +15,7 @@
  *   apm_ep_eval        <- no reference counterpart: expectation propagation for the probit (the
  *   apm_ep_predict        fit, log Z_EP, the marginals and the predictive distribution; R&W §3.6)
  *   apm_ep                with the sweeps' factorisations and solves on the device
+ *   apm_ep_grad        <- no reference counterpart: the gradient of log Z_EP with respect to theta
  *   apm_laplace        <- gpdemo/latent_posterior_approximations.py:22-124  laplace_approximation(K, y, ...)
  *   apm_theta_eval     <- gpdemo/estimators.py:201-217 (+ :221-241)  ApproxPosteriorIS.__call__(ns, theta)
  *                         gpdemo/estimators.py:317-325               PriorMC.__call__(ns, theta)
@@ -239,6 +240,26 @@ int apm_ep_eval(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ldt, 
 int apm_ep_predict(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ldt,
                    const double *Xs, int64_t m, int64_t ldxs, double *mean, double *var,
                    double *prob, int64_t ldo, int *status, int64_t *n_sweeps);
+/* The EP fit (Gram -> sweeps with the apm_set_ep settings), then the gradient of log Z_EP with
+ * respect to theta into row i of grad (count x P, row stride ldg >= P = apm_theta_len). With
+ * S^1/2, L and a of the sweep the fit stopped at (R&W eq. 5.27 / Alg. 5.2; a is their b):
+ *   Z = L^-1 diag(S^1/2), R = Z^T Z = S^1/2 B^-1 S^1/2, M = 1/2 a a^T - 1/2 R,
+ *   grad_j = sum_ik M_ik (dK/dtheta_j)_ik,
+ * dK/dtheta_j exactly apm_laplace_grad's (dK/dtheta_0 = S WITHOUT epsilon, the G-weighted
+ * squared scaled differences for the length scales): apm_laplace_grad's M without its implicit
+ * term, because at the EP fixed point the derivative through the sites vanishes. The gradient is
+ * therefore only as exact as the fit is converged: at the default diff_tol = 1e-8 it is off by
+ * up to a few 1e-4 of max(1, max|grad|), at 1e-16 by a few 1e-8 (DESIGN.md §18 has the table);
+ * set a tight diff_tol (and max_sweeps to match) before fitting theta with it.
+ * logz[i] (may be NULL) is bitwise the value apm_ep_eval returns for the same theta and
+ * settings; status[i] is the fit's (APM_STATUS_CHOL_B, _EP_CAVITY, _MAXITER; a failed chain has
+ * NaN logz and a NaN row); n_sweeps[i] (may be NULL). Probit only, ISO or ARD context of any
+ * family, count <= max_batch (APM_E_INVALID otherwise). A chain's outputs do not depend on its
+ * position in the batch nor on the other chains. Uses the context's work matrix like every
+ * theta-call; cache slots and U buffers are not touched. apm_version() is unchanged: a caller
+ * detects this entry point by its symbol. */
+int apm_ep_grad(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ldt, double *logz,
+                double *grad, int64_t ldg, int *status, int64_t *n_sweeps);
 /* cached u-call: reuse slots[i]'s per-theta state with draws ubufs[i] */
 int apm_u_eval(apm_ctx *ctx, int64_t count, const int64_t *slots, const int64_t *ubufs,
                double *out_logf, int *status);
@@ -308,8 +329,8 @@ int apm_ep(int device, const double *K, int64_t n, int64_t ldk, const double *y,
 #define APM_PROF_ICM_CHECKS 11 /* not a kernel: launches = chains whose chol(C) was also formed the
                                  reference's way (the InvalidCovarianceMatrixError check) */
 #define APM_PROF_GUARD 12 /* not a kernel: launches = chains failed by the guard (APM_STATUS_GUARD) */
-#define APM_PROF_GRAD_REDUCE 13 /* k_grad_reduce of apm_laplace_grad; work = bytes (the lower
-                                   triangles of R and K it reads) */
+#define APM_PROF_GRAD_REDUCE 13 /* k_grad_reduce of apm_laplace_grad and apm_ep_grad; work = bytes
+                                   (the lower triangles of R and K it reads) */
 #define APM_PROF_EP_SITES 14 /* k_ep_sites of the EP sweeps; work = bytes (the solved rows of V^T
                                 it reads) */
 #define APM_PROF_NKINDS 15
