@@ -183,6 +183,31 @@ class _BatchedChains(object):
         self.log_f, self.lp_cur = self._theta_eval(idx, self.theta, self.slot_cur[idx])
         return self.theta.copy()
 
+    def predict(self, X_test):
+        """Importance-sampling predictive of every live chain's current state ``(theta, u)`` at
+        ``X_test`` (m, D): ``(prob, ess)``, (n_chains, m) and (n_chains,), NaN for failed chains
+        (``apm_is_predict``). Averaged over a run's transitions, ``prob`` estimates
+        the exact posterior predictive. For ``estimator='is'`` and ``'is_ep'`` only.
+
+        The call evaluates each chain's theta into its CURRENT slot with its current U buffer. It
+        relies on batch independence: a slot's contents are a function of theta alone (the
+        U buffer enters the estimate only), and a theta-call writes the same bits whatever batch
+        it runs in, so the slot is rewritten with what it already holds and the chains'
+        trajectories do not change. No sampler state (theta, log f, streams, counters) is
+        touched."""
+        if self.est not in (_native.EST_IS, _native.EST_IS_EP):
+            raise ValueError("predict() needs estimator='is' or 'is_ep': the other estimators "
+                             'carry no importance samples of f')
+        Xs = np.ascontiguousarray(X_test, dtype=np.float64)
+        prob = np.full((self.n_chains, Xs.shape[0]), np.nan)
+        ess = np.full(self.n_chains, np.nan)
+        live = np.flatnonzero(~self.failed)
+        if live.size:
+            _, p, _, _, e, st, _ = self.ctx.is_predict(self.est, self.theta[live],
+                                                       self.ub_u[live], self.slot_cur[live], Xs)
+            prob[live], ess[live] = p, e
+        return prob, ess
+
     # ------------------------------------------------------------------ checkpoint / resume
     def checkpoint(self, store_u=None):
         """Chain state at a transition boundary as a dict of numpy arrays (``numpy.savez``-able,

@@ -8,6 +8,7 @@
 //   host_theta.cpp    the theta-call: concurrent chol(K), posterior factor, guard, ICM check
 //   host_laplace.cpp  apm_laplace's covariance, the predictive and gradient paths
 //   host_ep.cpp       the sweep loop of parallel expectation propagation (ep.hip)
+//   host_is_predict.cpp  the importance-sampling predictive's tail after an IS theta-call
 // Everything shared has hidden visibility: the library exports the apm_* functions only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -243,6 +244,12 @@ struct __attribute__((visibility("hidden"))) apm_ctx {
     double ep_damping = 0.8, ep_tol = 1e-8;
     int64_t ep_max_sweeps = 100;
     EpVecs ep{};
+    // the importance-sampling predictive (apm_is_predict), allocated at its first call: the
+    // reversed transpose of each chain's U buffer (max_batch x sp x np), the weights (max_batch x
+    // sp) and ess (max_batch), v* and c per test row (max_batch x np each), a vector of ones
+    // (max_batch x np: k_gram_cross's Ws) and the sample-tile partials (max_batch x 3 x np x sp/64)
+    double *is_ut = nullptr, *is_w = nullptr, *is_ess = nullptr, *is_vstar = nullptr;
+    double *is_c = nullptr, *is_ones = nullptr, *is_part = nullptr;
 };
 
 namespace apm_host __attribute__((visibility("hidden"))) {
@@ -416,6 +423,16 @@ void grad_buffers(apm_ctx* c);
 void grad_block(apm_ctx* c, int count);
 // grad_block's second pass for the chains left live by ep_fit: d log Z_EP / d theta into c->gout
 void ep_grad_block(apm_ctx* c, int count);
+
+// ---- host_is_predict.cpp --------------------------------------------------------------------
+// The predictive tail after an APM_EST_IS / APM_EST_IS_EP theta-call on the same context (its
+// thetas, slots and ubufs still on the device; st_h the call's statuses) at the m test inputs:
+// prob / mean / var (count x m, row stride ldo) and ess (count), any of them null. Rows of a
+// chain that is not OK are left untouched. A factorisation that fails in the tail (none can for
+// a chain whose theta-call succeeded in exact arithmetic) is reported in st_h.
+void is_predict_tail(apm_ctx* c, int count, const double* thetas, int64_t ldt, int* st_h,
+                     const double* Xs, int64_t m, int64_t ldxs, double* prob, double* mean,
+                     double* var, int64_t ldo, double* ess);
 
 // ---- host_ep.cpp ----------------------------------------------------------------------------
 void ep_buffers(apm_ctx* c);

@@ -483,6 +483,35 @@ void launch_lme(const double* partial, int64_t pstride, int nb, int S, int sp, S
                 const int64_t* slots, double* out, const int* status, int nchains,
                 hipStream_t s);
 
+// ---- is_predict.hip: importance-sampling predictive at test inputs ----------
+// wbar[b * sp + s] = the self-normalised weight of sample s < S from the per-sample sums the
+// theta-call's k_ugemm left in `partial` (k_lme's log w_s), exact zeros for s in [S, sp);
+// ess[b] = 1 / sum_s wbar_s^2
+void launch_is_weights(const double* partial, int64_t pstride, int nb, int S, int sp,
+                       const double* cst, const int64_t* slots, double* wbar, double* ess,
+                       Live live, int nchains, hipStream_t s);
+// Ut[b][s][k] = U[ubufs[b]][np - 1 - k][s] (sp x np per chain); the U buffers are only read
+void launch_is_ut(UPool P, const int64_t* ubufs, int np, double* Ut, Live live, int nchains,
+                  hipStream_t s);
+// per chain and row r < 64 mb of the solved rows p_r^T in A's rows [row0, ..) x columns
+// [0, 64 nb): vstar = sig[b] - |p_r|^2, cvec = sum_tj part[tj][r] in order (0 for r >= ms), each at
+// out[b * ostride + r], and p_r^T J into columns [64 nb, 128 nb) of the same row
+void launch_is_rows(MatB A, int64_t row0, int ms, int mb, int nb, const double* sig,
+                    const double* part, int64_t pstride, double* vstar, double* cvec,
+                    int64_t ostride, Live live, int nchains, hipStream_t s);
+// per (chain, row tile < mb, sample tile < sp / 64): the h-rows (A's rows [row0, ..), columns
+// [col0, col0 + np)) times Ut on the f64 MFMA, m = cvec + acc, the link (lik: APM_LIK_*) and the
+// weighted sums over the tile's samples into pp[((b 3 + q) npr + row) (sp / 64) + tile], q = 0: wbar
+// link, 1: wbar m, 2: wbar m^2
+void launch_is_pred_gemm(int lik, MatB A, int64_t row0, int64_t col0, int np, int mb,
+                         const double* Ut, int sp, const double* wbar, const double* vstar,
+                         const double* cvec, int64_t ostride, double* pp, int64_t npr, Live live,
+                         int nchains, hipStream_t s);
+// the sample-tile partials in order -> prob, mean, var = vstar + sum wbar m^2 - mean^2 (r < ms)
+void launch_is_finish(const double* pp, int64_t npr, int nst, int ms, const double* vstar,
+                      double* mean, double* var, double* prob, int64_t ostride, Live live,
+                      int nchains, hipStream_t s);
+
 // chol(K) retry of the chains with fail[b] == code, unblocked in LAPACK's dpotf2 order (chol.hip,
 // DESIGN.md §3.4): K's lower triangle into A, L in place, per-tile log-diagonal sums into ldet;
 // success clears fail[b]. Returns false (nothing launched) for np > 512.

@@ -497,6 +497,46 @@ int apm_predict(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, co
     return APM_SUCCESS;
 }
 
+int apm_is_predict(apm_ctx* c, int est, int64_t count, const double* thetas, int64_t ldt,
+                   const int64_t* ubufs, const int64_t* slots, const double* Xs, int64_t m,
+                   int64_t ldxs, double* out_logf, double* prob, double* mean, double* var,
+                   int64_t ldo, double* ess, int* status, int64_t* nops) {
+    if (!c) return fail(nullptr, APM_E_INVALID, "apm_is_predict: null context");
+    if (est != APM_EST_IS && est != APM_EST_IS_EP)
+        return fail(c, APM_E_INVALID, "apm_is_predict: APM_EST_IS or APM_EST_IS_EP only");
+    if (c->kind == APM_KERNEL_PRECOMPUTED)
+        return fail(c, APM_E_INVALID, "apm_is_predict: needs a context whose covariance is built "
+                                      "on the device (the cross-covariance is)");
+    if (m <= 0 || ldo < m || !Xs || ldxs < c->d)
+        return fail(c, APM_E_INVALID, "apm_is_predict: bad test inputs or ldo < m");
+    // the theta-call itself: apm_theta_eval's checks (count, the logit's IS_EP refusal, indices),
+    // staging and values
+    const int rc = apm_theta_eval(c, est, count, thetas, ldt, ubufs, slots, out_logf, status, nops);
+    if (rc != APM_SUCCESS) return rc;
+    const SkewScope skew(c);
+    try {
+        int ok = 0;
+        for (int64_t b = 0; b < count; ++b) ok += status[b] == APM_STATUS_OK;
+        if (ok)
+            is_predict_tail(c, (int)count, thetas, ldt, status, Xs, m, ldxs, prob, mean, var, ldo,
+                            ess);
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        for (int64_t b = 0; b < count; ++b) {
+            if (status[b] != APM_STATUS_OK) {
+                for (double* o : {mean, var, prob})
+                    if (o) std::fill(o + b * ldo, o + b * ldo + m, nan);
+                if (ess) ess[b] = nan;
+            } else if (nops) {
+                nops[b] += 2;  // the tail's chol(K) and chol(J M J); the row solves count as
+                               // apm_predict's do: not at all
+            }
+        }
+    } catch (const HipError& e) {
+        return fail(c, APM_E_HIP, e.msg);
+    }
+    return APM_SUCCESS;
+}
+
 int apm_laplace_grad(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, double* lml,
                      double* grad, int64_t ldg, int* status, int64_t* n_iter) {
     if (!c) return fail(nullptr, APM_E_INVALID, "apm_laplace_grad: null context");

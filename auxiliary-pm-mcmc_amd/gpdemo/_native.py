@@ -73,6 +73,8 @@ _SIGS = {
     'apm_gram': (_i, [_i, _i, _p, _i64, _i64, _i64, _p, _i64, _d, _p, _i64]),
     'apm_gram_cross': (_i, [_i, _i, _p, _i64, _p, _i64, _i64, _i64, _p, _i64, _p, _i64]),
     'apm_predict': (_i, [_p, _i64, _p, _i64, _p, _i64, _i64, _p, _p, _p, _i64, _p, _p]),
+    'apm_is_predict': (_i, [_p, _i, _i64, _p, _i64, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _i64,
+                            _p, _p, _p]),
     'apm_laplace_grad': (_i, [_p, _i64, _p, _i64, _p, _p, _i64, _p, _p]),
     'apm_set_ep': (_i, [_p, _d, _d, _i64]),
     'apm_ep_eval': (_i, [_p, _i64, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _p]),
@@ -422,6 +424,36 @@ class Context(object):
                 mean[t0:].ctypes.data, var[t0:].ctypes.data, prob[t0:].ctypes.data, m,
                 st[t0:].ctypes.data, nit[t0:].ctypes.data), self._h)
         return mean, var, prob, st, nit
+
+    def is_predict(self, est, thetas, ubufs, slots, X_test):
+        """Importance-sampling predictive at X_test (m, d) for up to `max_batch` chains: the
+        theta-call of :meth:`theta_eval` (`est` EST_IS or EST_IS_EP; the slots are written, log f
+        is that call's bitwise) and then the self-normalised average over the importance samples
+        of the chains' U buffers: ``(logf, prob, mean, var, ess, status, n_cubic_ops)``, prob /
+        mean / var (count, m) and ess (count,) NaN where status != 0 (include/apm.h
+        apm_is_predict)."""
+        th = np.atleast_2d(_f64(thetas))
+        count = th.shape[0]
+        if th.shape[1] < self.theta_len:
+            raise IndexError('Out of bounds on buffer access (axis 0)')
+        Xs = _f64(X_test)
+        if Xs.ndim != 2 or Xs.shape[1] != self.d:
+            raise ValueError('X_test has shape {0}, expected (m, {1})'.format(Xs.shape, self.d))
+        m = Xs.shape[0]
+        ub = np.ascontiguousarray(ubufs, dtype=np.int64)
+        sl = np.ascontiguousarray(slots, dtype=np.int64)
+        if ub.shape != (count,) or sl.shape != (count,):
+            raise ValueError('one U buffer and one slot per theta')
+        out = np.full(count, np.nan)
+        prob, mean, var = (np.full((count, m), np.nan) for _ in range(3))
+        ess = np.full(count, np.nan)
+        st = np.zeros(count, dtype=np.int32)
+        nops = np.zeros(count, dtype=np.int64)
+        _check(self.lib.apm_is_predict(
+            self._h, est, count, _ptr(th), th.shape[1], _ptr(ub), _ptr(sl), _ptr(Xs), m, self.d,
+            _ptr(out), _ptr(prob), _ptr(mean), _ptr(var), m, _ptr(ess), _ptr(st), _ptr(nops)),
+            self._h)
+        return out, prob, mean, var, ess, st, nops
 
     def laplace_grad(self, thetas):
         """Laplace log marginal likelihood and its gradient with respect to theta for every row

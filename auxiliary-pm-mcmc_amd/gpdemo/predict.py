@@ -24,7 +24,8 @@ from . import _native
 from .estimators import _kernel_spec, _raise_for_status
 from .latent_posterior_approximations import raise_for_ep_status
 
-__all__ = ['LaplacePredictor', 'EPPredictor', 'posterior_average', 'log_predictive_density']
+__all__ = ['LaplacePredictor', 'EPPredictor', 'ISPredictor', 'posterior_average',
+           'log_predictive_density']
 
 
 def _keep(a, burn, thin):
@@ -56,16 +57,24 @@ def log_predictive_density(mean, var, y_test, burn=0, thin=1, likelihood='probit
     if likelihood == 'logit':
         if prob is None:
             raise ValueError("likelihood='logit' needs the device's prob")
-        p = _keep(prob, burn, thin)
-        if y.shape != (p.shape[1],):
-            raise ValueError('y_test has shape {0}, expected ({1},)'.format(y.shape, p.shape[1]))
-        with np.errstate(divide='ignore'):
-            lp = np.where(y[None, :] > 0, np.log(p), np.log1p(-p))
+        lp = _log_prob_of_labels(_keep(prob, burn, thin), y)
     else:
         z = _keep(mean, burn, thin) / np.sqrt(1.0 + _keep(var, burn, thin))
         if y.shape != (z.shape[1],):
             raise ValueError('y_test has shape {0}, expected ({1},)'.format(y.shape, z.shape[1]))
         lp = log_ndtr(y[None, :] * z)
+    return _log_mean_exp_density(lp)
+
+
+def _log_prob_of_labels(p, y):
+    """log p (y* = +1) or log1p(-p) (y* = -1) per sample and test point, p (T, M)."""
+    if y.shape != (p.shape[1],):
+        raise ValueError('y_test has shape {0}, expected ({1},)'.format(y.shape, p.shape[1]))
+    with np.errstate(divide='ignore'):
+        return np.where(y[None, :] > 0, np.log(p), np.log1p(-p))
+
+
+def _log_mean_exp_density(lp):
     top = lp.max(0)
     return float(np.mean(top + np.log(np.mean(np.exp(lp - top[None, :]), axis=0))))
 
@@ -164,3 +173,147 @@ class EPPredictor(LaplacePredictor):
             for s in st:
                 raise_for_ep_status(int(s), self.max_sweeps)
         return mean, var, prob
+
+
+class ISPredictor(object):
+    """Importance-sampling predictive distribution at ``X_test`` (M, D): for each pair
+    ``(theta, u)`` the self-normalised average over the importance samples ``f_s = f_post +
+    C_chol u_s`` of ``p(y* = 1 | f_s, theta)`` (``prob``), of the conditional latent mean (``mean``)
+    and the matching total variance (``var``), with the weights of the IS estimate of
+    ``p(y | theta)`` (``apm_is_predict``). Averaged over the states ``(theta, u)``
+    of a pseudo-marginal chain, ``prob`` estimates the exact posterior predictive at any fixed
+    ``n_imp``: no Gaussian approximation of ``p(f | theta, y)`` is left in it, unlike
+    :class:`LaplacePredictor` and :class:`EPPredictor`.
+
+    ``proposal`` is the importance distribution, ``'laplace'`` or ``'ep'`` (probit only:
+    ``likelihood='logit'`` raises ``NotImplementedError``); ``diff_f_tol`` / ``max_iters`` are the
+    Newton settings, ``damping`` / ``diff_tol`` / ``max_sweeps`` the EP fit's. ``kernel_func`` must
+    be a device kernel (``gpdemo.kernels.make_kernel_func``). The arguments are checked first and
+    the device context is created at the first call."""
+
+    def __init__(self, X, y, kernel_func, X_test, n_imp, proposal='laplace', likelihood='probit',
+                 max_batch=8, diff_f_tol=1e-4, max_iters=1000, damping=0.8, diff_tol=1e-8,
+                 max_sweeps=100, device=None):
+        lik = _native.likelihood_code(likelihood)
+        if proposal not in ('laplace', 'ep'):
+            raise ValueError("proposal must be 'laplace' or 'ep', got {0!r}".format(proposal))
+        if proposal == 'ep' and lik != _native.LIK_PROBIT:
+            raise NotImplementedError('expectation propagation is implemented for the probit '
+                                      'likelihood only')
+        self.likelihood, self.proposal = likelihood, proposal
+        self._est = _native.EST_IS_EP if proposal == 'ep' else _native.EST_IS
+        self._kind, self._eps = _kernel_spec(kernel_func)
+        if self._kind == _native.KERNEL_PRECOMPUTED:
+            raise NotImplementedError(
+                'the device predictor builds the cross-covariance itself and needs one of '
+                'gpdemo.kernels.make_kernel_func(...); got {0!r}'.format(kernel_func))
+        self.X = np.asarray(X, dtype=np.float64)
+        self.y = np.asarray(y, dtype=np.float64)
+        self.X_test = np.ascontiguousarray(X_test, dtype=np.float64)
+        if self.X_test.ndim != 2 or self.X_test.shape[1] != self.X.shape[1]:
+            raise ValueError('X_test has shape {0}, expected (M, {1})'
+                             .format(self.X_test.shape, self.X.shape[1]))
+        self.n_imp, self.max_batch = int(n_imp), int(max_batch)
+        if self.n_imp < 1 or self.max_batch < 1:
+            raise ValueError('n_imp and max_batch must be positive')
+        self.kernel_func = kernel_func
+        self.max_iters, self.max_sweeps = int(max_iters), int(max_sweeps)
+        self._newton = (float(diff_f_tol), int(max_iters))
+        self._ep = (float(damping), float(diff_tol), int(max_sweeps))
+        self._device = device
+        self._ctx = None
+        self.status = self.n_cubic_ops = None
+
+    def _context(self):
+        if self._ctx is None:
+            B = self.max_batch
+            ctx = _native.Context(self.X, self.y, self._kind, self._eps, self.n_imp, max_batch=B,
+                                  n_slots=B, n_ubufs=B, device=self._device,
+                                  likelihood=self.likelihood)
+            ctx.set_newton(*self._newton)
+            if self._est == _native.EST_IS_EP:
+                ctx.set_ep(*self._ep)
+            self._ctx = ctx
+        return self._ctx
+
+    def _raise(self, status, ctx):
+        if self._est == _native.EST_IS_EP and status in (
+                _native.STATUS_CHOL_B, _native.STATUS_EP_CAVITY, _native.STATUS_MAXITER):
+            raise_for_ep_status(status, self.max_sweeps)
+        _raise_for_status(status, ctx, self.max_iters)
+
+    def __call__(self, thetas, us=None, seeds=None, on_error='raise'):
+        """``(prob, mean, var, ess, logf)`` for thetas (T, P) or (P,): prob / mean / var (T, M),
+        ess and logf (T,). The draws are either ``us``, host arrays (n, n_imp) per theta, or
+        ``seeds``, one Philox seed per theta for the device's own normals (``apm_u_normal``,
+        counter 0) - exactly one of the two. A theta whose fit fails raises the estimators'
+        exception, or gives NaN rows with ``on_error='nan'``; ``self.status`` keeps the codes."""
+        if on_error not in ('raise', 'nan'):
+            raise ValueError("on_error must be 'raise' or 'nan'")
+        if (us is None) == (seeds is None):
+            raise ValueError('give exactly one of us (host draws) and seeds (device draws)')
+        th = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
+        T, M = th.shape[0], self.X_test.shape[0]
+        if us is not None:
+            us = np.asarray(us, dtype=np.float64)
+            if us.ndim == 2:
+                us = us[None]
+            if us.shape != (T, self.X.shape[0], self.n_imp):
+                raise ValueError('us has shape {0}, expected {1}'
+                                 .format(us.shape, (T, self.X.shape[0], self.n_imp)))
+        else:
+            seeds = np.atleast_1d(np.asarray(seeds, dtype=np.uint64))
+            if seeds.shape != (T,):
+                raise ValueError('one seed per theta')
+        ctx = self._context()
+        prob, mean, var = (np.full((T, M), np.nan) for _ in range(3))
+        ess, logf = np.full(T, np.nan), np.full(T, np.nan)
+        st = np.zeros(T, dtype=np.int32)
+        nops = np.zeros(T, dtype=np.int64)
+        for t0 in range(0, T, self.max_batch):
+            cnt = min(self.max_batch, T - t0)
+            idx = np.arange(cnt, dtype=np.int64)
+            if us is not None:
+                for i in range(cnt):
+                    ctx.u_upload(i, us[t0 + i])
+            else:
+                ctx.u_normal(idx, seeds[t0:t0 + cnt], np.zeros(cnt, dtype=np.uint64))
+            sl = slice(t0, t0 + cnt)
+            logf[sl], prob[sl], mean[sl], var[sl], ess[sl], st[sl], nops[sl] = ctx.is_predict(
+                self._est, th[sl], idx, idx, self.X_test)
+        self.status, self.n_cubic_ops = st, nops
+        if on_error == 'raise':
+            for s in st:
+                self._raise(int(s), ctx)
+        return prob, mean, var, ess, logf
+
+    def posterior_average(self, thetas, us=None, seeds=None, burn=0, thin=1, on_error='raise'):
+        """Class probabilities (M,) averaged over the kept ``(theta, u)`` states."""
+        th, us, seeds = self._kept(thetas, us, seeds, burn, thin)
+        return posterior_average(self(th, us, seeds, on_error)[0])
+
+    def log_predictive_density(self, thetas, y_test, us=None, seeds=None, burn=0, thin=1,
+                               on_error='raise'):
+        """Mean test log predictive density of labels ``y_test`` (M,) in {-1, +1}, from ``prob``
+        (``log prob`` for y* = +1, ``log1p(-prob)`` for y* = -1, a log-mean-exp over the states):
+        ``mean`` and ``var`` describe the latent value and are not read."""
+        th, us, seeds = self._kept(thetas, us, seeds, burn, thin)
+        prob = _keep(self(th, us, seeds, on_error)[0], 0, 1)
+        return _log_mean_exp_density(
+            _log_prob_of_labels(prob, np.asarray(y_test, dtype=np.float64)))
+
+    @staticmethod
+    def _kept(thetas, us, seeds, burn, thin):
+        k = slice(int(burn), None, int(thin))
+        th = np.atleast_2d(np.asarray(thetas, dtype=np.float64))[k]
+        if us is not None:
+            us = np.asarray(us, dtype=np.float64)
+            us = (us[None] if us.ndim == 2 else us)[k]
+        if seeds is not None:
+            seeds = np.atleast_1d(np.asarray(seeds, dtype=np.uint64))[k]
+        return th, us, seeds
+
+    def close(self):
+        if self._ctx is not None:
+            self._ctx.close()
+            self._ctx = None

@@ -174,6 +174,34 @@ int apm_theta_eval_K(apm_ctx *ctx, int estimator, const double *K, int64_t ldk, 
 int apm_predict(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ldt,
                 const double *Xs, int64_t m, int64_t ldxs, double *mean, double *var,
                 double *prob, int64_t ldo, int *status, int64_t *n_iter);
+/* Importance-sampling predictive at m test inputs Xs (m x d, ldxs) for `count` chains (count <=
+ * max_batch), estimator APM_EST_IS or APM_EST_IS_EP. The call first IS apm_theta_eval(estimator,
+ * ...) on the same thetas, ubufs and slots: the slots are written, out_logf[i], status[i] and the
+ * failure handling are that call's, out_logf[i] bitwise. Then, for the chains that are OK, with
+ * the importance samples f_s = f_post + C_chol u_s of U buffer ubufs[i] and their self-normalised
+ * weights wbar_s (the summands of the estimate, exp(log w_s - max) / sum over the S real samples;
+ * padded sample columns weigh exactly 0):
+ *   p_j = L_K^-1 k*_j (k* = k(X, x*_j), no epsilon), v*_j = s - |p_j|^2, s = exp(theta_0),
+ *   h_j = U_M^-1 p_j (M = I + L_K^T W L_K = U_M U_M^T), c_j = k*_j^T a, a = K^-1 f_post,
+ *   m_sj = E[f*_j | f_s] = c_j + h_j^T u_s,
+ *   prob_j = sum_s wbar_s Phi(m_sj / sqrt(1 + v*_j))      (APM_LIK_PROBIT)
+ *          = sum_s wbar_s GH(m_sj, v*_j)                   (APM_LIK_LOGIT: apm_predict's rule)
+ *   mean_j = sum_s wbar_s m_sj,  var_j = v*_j + sum_s wbar_s m_sj^2 - mean_j^2,
+ *   ess = 1 / sum_s wbar_s^2,
+ * prob / mean / var count x m with row stride ldo >= m, ess count; any of the four may be NULL.
+ * Averaged over the iterations of a pseudo-marginal chain whose state is (theta, u), prob is a
+ * consistent estimate of the exact posterior predictive at any fixed number of samples. Nothing
+ * is clamped; the tail is fp64 throughout and never applies K^-1 to a computed f_s (DESIGN.md
+ * §19). The outputs of a chain that is not OK are NaN. n_cubic_ops[i] (may be NULL) is the
+ * theta-call's own plus 2 for an OK chain: the tail factors K and J M J again in fp64; the two n x m
+ * row solves are not counted, as apm_predict does not count its own. APM_E_INVALID for any other
+ * estimator, a PRECOMPUTED context, APM_EST_IS_EP under APM_LIK_LOGIT and count > max_batch. A
+ * chain's outputs do not depend on its position in the batch nor on the other chains; the U
+ * buffers are not modified. apm_version() is unchanged: detect the entry point by its symbol. */
+int apm_is_predict(apm_ctx *ctx, int estimator, int64_t count, const double *thetas, int64_t ldt,
+                   const int64_t *ubufs, const int64_t *slots, const double *Xs, int64_t m,
+                   int64_t ldxs, double *out_logf, double *prob, double *mean, double *var,
+                   int64_t ldo, double *ess, int *status, int64_t *n_cubic_ops);
 /* Gradient of the Laplace log marginal likelihood with respect to theta for `count` thetas
  * (count <= max_batch): Gram -> fp64 Newton (apm_set_newton settings) -> lml[i] (may be NULL) and
  * grad row i (count x P, row stride ldg >= P = apm_theta_len). status[i]: APM_STATUS_* of chain i
