@@ -109,6 +109,11 @@ class _BatchedChains(object):
         self.ub_prop = np.arange(2 * C, 3 * C, dtype=np.int64)
         self.prngs, self.dev_seeds = chain_streams(seed, C, first_chain)
         self.dev_ctr = np.zeros(C, dtype=np.uint64)
+        # estimate_spread's own Philox streams (keys apart from dev_seeds, counters of their own)
+        self.spread_seeds = np.array(
+            [np.random.SeedSequence(seed, spawn_key=(first_chain + c, 1))
+             .generate_state(2, np.uint64)[0] for c in range(C)], dtype=np.uint64)
+        self.spread_ctr = np.zeros(C, dtype=np.uint64)
         self.theta = np.zeros((C, self.P))
         self.log_f = np.full(C, -np.inf)
         self.lp_cur = np.zeros(C)  # log prior of the current theta (constant during the u-update)
@@ -207,6 +212,46 @@ class _BatchedChains(object):
                                                        self.ub_u[live], self.slot_cur[live], Xs)
             prob[live], ess[live] = p, e
         return prob, ess
+
+    def estimate_spread(self, n_rep=16, block=None):
+        """How noisy the log-estimate is at every live chain's current theta (DESIGN.md §20,
+        ``apm_is_spread``): `n_rep` independent redraws of u against the chain's current cache
+        slot, each cut into blocks of `block` samples (None: n_imp). Returns a dict with
+        ``log_estimates``, ``ess`` and ``wmax`` (n_chains, n_rep, n_imp // block) and ``sd``
+        (n_chains,), the standard deviation (ddof = 1) of a chain's block estimates; NaN for
+        failed chains. For ``estimator='is'``, ``'is_ep'`` and ``'priormc'``.
+
+        The draws come from a stream of their own: chain c's key is the first 64-bit word of
+        ``SeedSequence(seed, spawn_key=(first_chain + c, 1))`` - a child of the chain's own
+        sequence, which keys u and nu - with a counter that starts at 0 and advances by `n_rep`
+        per call, so repeated calls are independent. They are drawn into the chain's proposal
+        buffer ``ub_prop``, which holds no live state at a transition boundary (every u-update
+        overwrites it before reading it); the slots are only read and neither ``dev_ctr`` nor the
+        host streams move, so the trajectories are bitwise what they are without the call. The
+        spread stream's counter is not part of ``checkpoint()``."""
+        if self.est not in (_native.EST_IS, _native.EST_IS_EP, _native.EST_PRIORMC):
+            raise ValueError("estimate_spread() needs estimator='is', 'is_ep' or 'priormc': the "
+                             'Laplace estimate has no draws')
+        n_rep = int(n_rep)
+        block = self.n_imp if block is None else int(block)
+        if n_rep < 1 or not 1 <= block <= self.n_imp:
+            raise ValueError('n_rep >= 1 and 1 <= block <= n_imp = {0} are required'
+                             .format(self.n_imp))
+        nblk = self.n_imp // block
+        C = self.n_chains
+        out = {k: np.full((C, n_rep, nblk), np.nan) for k in ('log_estimates', 'ess', 'wmax')}
+        out['sd'] = np.full(C, np.nan)
+        out['block'] = block
+        live = np.flatnonzero(~self.failed)
+        if live.size:
+            lf, es, wm, st = self.ctx.is_spread(self.slot_cur[live], self.ub_prop[live],
+                                                self.spread_seeds[live], self.spread_ctr[live],
+                                                n_rep, block)
+            self.spread_ctr[live] += np.uint64(n_rep)
+            out['log_estimates'][live], out['ess'][live], out['wmax'][live] = lf, es, wm
+            if n_rep * nblk > 1:
+                out['sd'][live] = np.std(lf.reshape(live.size, -1), axis=1, ddof=1)
+        return out
 
     # ------------------------------------------------------------------ checkpoint / resume
     def checkpoint(self, store_u=None):

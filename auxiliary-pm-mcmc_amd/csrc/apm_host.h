@@ -9,6 +9,7 @@
 //   host_laplace.cpp  apm_laplace's covariance, the predictive and gradient paths
 //   host_ep.cpp       the sweep loop of parallel expectation propagation (ep.hip)
 //   host_is_predict.cpp  the importance-sampling predictive's tail after an IS theta-call
+//   host_is_diag.cpp  block estimates and weight diagnostics of the IS estimate over replicates
 // Everything shared has hidden visibility: the library exports the apm_* functions only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -110,6 +111,9 @@ struct __attribute__((visibility("hidden"))) apm_ctx {
     static constexpr int symv_tpw = 2;  // K x: lower tiles per workgroup (launch_symv)
     std::vector<int> slot_refs;  // owners of each cache slot (apm_cache_*; 0 = free)
     std::vector<int> slot_wide;  // host mirror of Sl.wide (read back with each theta-call)
+    // the last theta-call into the slot failed (its status != 0): the slot was not written, or its
+    // value is withheld - apm_u_eval_diag / apm_is_spread report NaN for it
+    std::vector<int> slot_failed;
     // fp64 factors of the wide slots: one np x np buffer attached per wide slot (Sl.L64 is the
     // device copy of l64_h), returned to l64_free when its slot is rewritten narrow
     std::vector<double*> l64_h, l64_free;
@@ -250,6 +254,11 @@ struct __attribute__((visibility("hidden"))) apm_ctx {
     // (max_batch x np: k_gram_cross's Ws) and the sample-tile partials (max_batch x 3 x np x sp/64)
     double *is_ut = nullptr, *is_w = nullptr, *is_ess = nullptr, *is_vstar = nullptr;
     double *is_c = nullptr, *is_ones = nullptr, *is_part = nullptr;
+    // the block diagnostics (apm_u_eval_diag / apm_is_spread), allocated at their first call: the
+    // staging array (3 x max_batch x APM_SPREAD_MAX_BLOCKS) and the replicates' Philox keys
+    // ([seeds: max_batch][counters: APM_SPREAD_MAX_BLOCKS x max_batch])
+    double* sd_out = nullptr;
+    uint64_t* sd_keys = nullptr;
 };
 
 namespace apm_host __attribute__((visibility("hidden"))) {
@@ -433,6 +442,16 @@ void ep_grad_block(apm_ctx* c, int count);
 void is_predict_tail(apm_ctx* c, int count, const double* thetas, int64_t ldt, int* st_h,
                      const double* Xs, int64_t m, int64_t ldxs, double* prob, double* mean,
                      double* var, int64_t ldo, double* ess);
+
+// ---- host_is_diag.cpp -----------------------------------------------------------------------
+// The u-path on the call's slots and U buffers and the block reduction (k_lme_blocks) of its
+// per-sample sums, n_rep times; before replicate r the U buffers are redrawn from (seeds[i],
+// counters[i] + r) when seeds is given (apm_is_spread), else n_rep = 1 and the buffers are read as
+// they are (apm_u_eval_diag). Arguments are checked by the caller; logf / ess / wmax (count x
+// n_rep nblk, row stride ldo) may be null, NaN for a chain whose slot's theta-call failed.
+void is_diag_run(apm_ctx* c, int count, const int64_t* slots, const int64_t* ubufs,
+                 const uint64_t* seeds, const uint64_t* counters, int64_t n_rep, int64_t block,
+                 double* logf, double* ess, double* wmax, int64_t ldo, int* status);
 
 // ---- host_ep.cpp ----------------------------------------------------------------------------
 void ep_buffers(apm_ctx* c);

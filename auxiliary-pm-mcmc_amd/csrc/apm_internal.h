@@ -483,6 +483,15 @@ void launch_lme(const double* partial, int64_t pstride, int nb, int S, int sp, S
                 const int64_t* slots, double* out, const int* status, int nchains,
                 hipStream_t s);
 
+// ---- is_diag.hip: block estimates and weight diagnostics of the IS estimate --
+// per chain b and block j < nblk of B samples of `partial` (k_ugemm's per-sample sums, log w_s as
+// k_lme forms it): logf, ess and wmax at out[q * qstride + b * ostride + off + j], q = 0, 1, 2;
+// chains with status != 0 are skipped
+void launch_lme_blocks(const double* partial, int64_t pstride, int nb, int B, int nblk, int sp,
+                       const double* cst, const int64_t* slots, double* out, int64_t qstride,
+                       int64_t ostride, int64_t off, const int* status, int nchains,
+                       hipStream_t s);
+
 // ---- is_predict.hip: importance-sampling predictive at test inputs ----------
 // wbar[b * sp + s] = the self-normalised weight of sample s < S from the per-sample sums the
 // theta-call's k_ugemm left in `partial` (k_lme's log w_s), exact zeros for s in [S, sp);

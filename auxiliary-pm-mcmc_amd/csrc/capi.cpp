@@ -324,6 +324,56 @@ int apm_u_eval(apm_ctx* c, int64_t count, const int64_t* slots, const int64_t* u
     return APM_SUCCESS;
 }
 
+// ---- block estimates and weight diagnostics of the IS estimate (host_is_diag.cpp) ------------
+namespace {
+
+// the checks apm_u_eval_diag and apm_is_spread share (draws: the latter's seeds / counters)
+int is_diag_call(apm_ctx* c, const char* who, int64_t count, const int64_t* slots,
+                 const int64_t* ubufs, bool draws, const uint64_t* seeds, const uint64_t* counters,
+                 int64_t n_rep, int64_t block, double* logf, double* ess, double* wmax,
+                 int64_t ldo, int* status) {
+    const std::string w(who);
+    if (!c) return fail(nullptr, APM_E_INVALID, w + ": null context");
+    if (count <= 0 || count > c->max_batch)
+        return fail(c, APM_E_INVALID, w + ": count outside [1, max_batch]");
+    if (!slots || !ubufs || !status || (draws && (!seeds || !counters)))
+        return fail(c, APM_E_INVALID, w + ": bad arguments");
+    if (block < 1 || block > c->S) return fail(c, APM_E_INVALID, w + ": block outside [1, n_imp]");
+    if (n_rep < 1) return fail(c, APM_E_INVALID, w + ": n_rep < 1");
+    const int64_t nblk = c->S / block;
+    if (n_rep > APM_SPREAD_MAX_BLOCKS || n_rep * nblk > APM_SPREAD_MAX_BLOCKS)
+        return fail(c, APM_E_INVALID, w + ": n_rep * nblk above APM_SPREAD_MAX_BLOCKS");
+    if (ldo < n_rep * nblk) return fail(c, APM_E_INVALID, w + ": ldo < n_rep * nblk");
+    if (!check_idx(c, count, slots, c->n_slots, "slot") ||
+        !check_idx(c, count, ubufs, c->n_ubufs, "ubuf"))
+        return APM_E_INVALID;
+    const SkewScope skew(c);
+    try {
+        HIPC(hipSetDevice(c->device));
+        is_diag_run(c, (int)count, slots, ubufs, draws ? seeds : nullptr, counters, n_rep, block,
+                    logf, ess, wmax, ldo, status);
+    } catch (const HipError& e) {
+        return fail(c, APM_E_HIP, e.msg);
+    }
+    return APM_SUCCESS;
+}
+
+}  // namespace
+
+int apm_u_eval_diag(apm_ctx* c, int64_t count, const int64_t* slots, const int64_t* ubufs,
+                    int64_t block, double* logf, double* ess, double* wmax, int64_t ldo,
+                    int* status) {
+    return is_diag_call(c, "apm_u_eval_diag", count, slots, ubufs, false, nullptr, nullptr, 1,
+                        block, logf, ess, wmax, ldo, status);
+}
+
+int apm_is_spread(apm_ctx* c, int64_t count, const int64_t* slots, const int64_t* ubufs,
+                  const uint64_t* seeds, const uint64_t* counters, int64_t n_rep, int64_t block,
+                  double* logf, double* ess, double* wmax, int64_t ldo, int* status) {
+    return is_diag_call(c, "apm_is_spread", count, slots, ubufs, true, seeds, counters, n_rep,
+                        block, logf, ess, wmax, ldo, status);
+}
+
 // ---- cache-slot lifetimes (samplers.py:563-584: an MH sampler holds the current state's cache
 // and the proposal's at once; on accept the proposal's becomes current and the old one is dropped).
 // Host bookkeeping only: a slot's contents are immutable between theta-calls into it, so a copy

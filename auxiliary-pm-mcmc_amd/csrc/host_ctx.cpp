@@ -295,6 +295,7 @@ void init_ctx(apm_ctx* c, int device, int kind, const double* X, int64_t n, int6
     HIPC(hipMemset(c->Sl.cst, 0, sizeof(double) * n_slots));
     HIPC(hipMemset(c->Sl.wide, 0, sizeof(int) * n_slots));
     c->slot_wide.assign((size_t)n_slots, 0);
+    c->slot_failed.assign((size_t)n_slots, 0);
     c->Up = UPool{dalloc<double>(c, n_ubufs * np * c->sp), np * c->sp, c->sp,
                   dalloc<float>(c, n_ubufs * np * c->sp)};
     HIPC(hipMemset(c->Up.base, 0, sizeof(double) * n_ubufs * np * c->sp));

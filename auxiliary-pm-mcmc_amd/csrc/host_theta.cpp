@@ -460,6 +460,8 @@ void theta_eval_impl(apm_ctx* c, int est, int count, bool gram, double* out_logf
         }
         if (detached) upload_l64(c);
     }
+    if (est != APM_EST_LAPLACE)  // (host bookkeeping for the block diagnostics, host_is_diag.cpp)
+        for (int b = 0; b < count; ++b) c->slot_failed[pin_slots(c)[b]] = st_h[b] != 0;
     for (int b = 0; b < count; ++b) {
         status[b] = st_h[b];
         if (nops) {

@@ -30,6 +30,7 @@ PROF_GRAM, PROF_CHOL_UPDATE, PROF_UGEMM, PROF_CHOL_UPDATE32, PROF_STATS = 0, 1, 
 PROF_CHOL_UPDATE32_OUTER, PROF_CHOL_UPDATE_OUTER, PROF_DF_TIMEOUTS = 5, 6, 7
 PROF_POST32_OUTER, PROF_POST64_RERUNS, PROF_TRSV_TIMEOUTS = 8, 9, 10
 PROF_ICM_CHECKS, PROF_GUARD, PROF_GRAD_REDUCE, PROF_EP_SITES, PROF_NKINDS = 11, 12, 13, 14, 15
+SPREAD_MAX_BLOCKS = 4096  # APM_SPREAD_MAX_BLOCKS: n_rep * nblk of one apm_is_spread call
 
 
 class NativeUnavailableError(RuntimeError):
@@ -65,6 +66,8 @@ _SIGS = {
     'apm_theta_eval': (_i, [_p, _i, _i64, _p, _i64, _p, _p, _p, _p, _p]),
     'apm_theta_eval_K': (_i, [_p, _i, _p, _i64, _i64, _i64, _p, _p, _p]),
     'apm_u_eval': (_i, [_p, _i64, _p, _p, _p, _p]),
+    'apm_u_eval_diag': (_i, [_p, _i64, _p, _p, _i64, _p, _p, _p, _i64, _p]),
+    'apm_is_spread': (_i, [_p, _i64, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _i64, _p]),
     'apm_slot_read': (_i, [_p, _i64, _p, _i64, _p, _p, _p]),
     'apm_cache_acquire': (_i, [_p, _p]),
     'apm_cache_copy': (_i, [_p, _i64]),
@@ -548,6 +551,61 @@ class Context(object):
         _check(self.lib.apm_u_eval(self._h, sl.shape[0], _ptr(sl), _ptr(ub), _ptr(out), _ptr(st)),
                self._h)
         return out, st
+
+    def _diag_args(self, slots, ubufs, n_rep, block):
+        """The checks of u_eval_diag / is_spread, made before the library is called:
+        ``(slots, ubufs, block, nblk)``."""
+        sl = np.ascontiguousarray(slots, dtype=np.int64)
+        ub = np.ascontiguousarray(ubufs, dtype=np.int64)
+        if sl.ndim != 1 or ub.shape != sl.shape or not 1 <= sl.shape[0] <= self.max_batch:
+            raise ValueError('one U buffer per slot, between 1 and max_batch = {0} chains'
+                             .format(self.max_batch))
+        block = self.n_imp if block is None else int(block)
+        if not 1 <= block <= self.n_imp:
+            raise ValueError('block = {0} outside [1, n_imp = {1}]'.format(block, self.n_imp))
+        n_rep = int(n_rep)
+        if n_rep < 1:
+            raise ValueError('n_rep = {0} < 1'.format(n_rep))
+        nblk = self.n_imp // block
+        if n_rep * nblk > SPREAD_MAX_BLOCKS:
+            raise ValueError('n_rep * nblk = {0} above {1} (APM_SPREAD_MAX_BLOCKS): split the '
+                             'replicates over several calls'.format(n_rep * nblk,
+                                                                    SPREAD_MAX_BLOCKS))
+        return sl, ub, block, nblk
+
+    def u_eval_diag(self, slots, ubufs, block=None):
+        """The cached u-call of :meth:`u_eval` cut into blocks of `block` samples (None: n_imp,
+        one block): ``(logf, ess, wmax, status)``, the first three (count, n_imp // block) - each
+        block's estimate, weight ESS and largest normalised weight (include/apm.h
+        apm_u_eval_diag). With one block, logf is u_eval's value bitwise."""
+        sl, ub, block, nblk = self._diag_args(slots, ubufs, 1, block)
+        count = sl.shape[0]
+        logf, ess, wmax = (np.full((count, nblk), np.nan) for _ in range(3))
+        st = np.zeros(count, dtype=np.int32)
+        _check(self.lib.apm_u_eval_diag(self._h, count, _ptr(sl), _ptr(ub), block, _ptr(logf),
+                                        _ptr(ess), _ptr(wmax), nblk, _ptr(st)), self._h)
+        return logf, ess, wmax, st
+
+    def is_spread(self, slots, ubufs, seeds, counters, n_rep, block=None):
+        """`n_rep` independent replicates of the estimate at the slots' fixed state: replicate r
+        redraws U buffer ubufs[i] from the Philox stream (seeds[i], counters[i] + r), as
+        :meth:`u_normal` draws it, and evaluates it in blocks of `block` samples (None: n_imp):
+        ``(logf, ess, wmax, status)``, the first three (count, n_rep, n_imp // block). The U
+        buffers are scratch (they end holding the last replicate's draws); the slots are only
+        read (include/apm.h apm_is_spread)."""
+        sl, ub, block, nblk = self._diag_args(slots, ubufs, n_rep, block)
+        n_rep = int(n_rep)
+        count = sl.shape[0]
+        sd = np.ascontiguousarray(seeds, dtype=np.uint64)
+        ct = np.ascontiguousarray(counters, dtype=np.uint64)
+        if sd.shape != (count,) or ct.shape != (count,):
+            raise ValueError('one seed and one counter per chain')
+        logf, ess, wmax = (np.full((count, n_rep, nblk), np.nan) for _ in range(3))
+        st = np.zeros(count, dtype=np.int32)
+        _check(self.lib.apm_is_spread(self._h, count, _ptr(sl), _ptr(ub), _ptr(sd), _ptr(ct),
+                                      n_rep, block, _ptr(logf), _ptr(ess), _ptr(wmax),
+                                      n_rep * nblk, _ptr(st)), self._h)
+        return logf, ess, wmax, st
 
     def slot_read(self, slot):
         L = np.zeros((self.n, self.n))

@@ -22,7 +22,8 @@ from .latent_posterior_approximations import (MaximumIterationsExceededError,
 __all__ = ['LogMarginalLikelihoodLaplaceEstimator', 'LogMarginalLikelihoodEPEstimator',
            'InvalidCovarianceMatrixError',
            'LogMarginalLikelihoodApproxPosteriorISEstimator',
-           'LogMarginalLikelihoodPriorMCEstimator', 'DeviceCache', 'DeviceInvariantError']
+           'LogMarginalLikelihoodPriorMCEstimator', 'DeviceCache', 'DeviceInvariantError',
+           'n_imp_curve', 'select_n_imp', 'tune_n_imp']
 
 _UBUF = 0  # single-chain estimators upload each call's draws into this device buffer
 
@@ -172,6 +173,118 @@ class _EstimatorBase(object):
         return ctx.theta_eval_K(est, self._K, ubuf, slot)
 
 
+def _spread_result(logf, ess, wmax, block, n_cubic_ops):
+    """One block length's replicates (each (n_rep, nblk)) as spread() returns them."""
+    return {'log_estimates': logf, 'sd': float(np.std(logf, ddof=1)) if logf.size > 1 else np.nan,
+            'ess': ess, 'wmax': wmax, 'block': int(block), 'n_cubic_ops': int(n_cubic_ops)}
+
+
+def _check_spread_args(n_imp, n_rep, blocks):
+    """ValueError for what apm_is_spread would refuse, before any device call."""
+    if n_imp is None or int(n_imp) < 1:
+        raise ValueError('n_imp is not known: pass n_imp=, or call the estimator once first')
+    if int(n_rep) < 1:
+        raise ValueError('n_rep = {0} < 1'.format(n_rep))
+    for b in blocks:
+        if not 1 <= int(b) <= int(n_imp):
+            raise ValueError('block = {0} outside [1, n_imp = {1}]'.format(b, n_imp))
+        if int(n_rep) * (int(n_imp) // int(b)) > _native.SPREAD_MAX_BLOCKS:
+            raise ValueError('n_rep * (n_imp // block) above {0}'.format(_native.SPREAD_MAX_BLOCKS))
+
+
+class _SpreadMixin(object):
+    """Replicate spread of the estimators that average over draws u."""
+
+    _spread_est = None  # the theta-call's APM_EST_*
+    _last_n_imp = None  # the number of draws of the last __call__ (spread's default n_imp)
+
+    def _spread_raise(self, status, ctx):
+        _raise_for_status(status, ctx)
+
+    def _spread_blocks(self, theta, n_rep, blocks, seed=0, n_imp=None):
+        """One theta-call, then apm_is_spread per block length on the same draws (the Philox
+        stream (seed, 0 .. n_rep - 1), in the context's one U buffer - scratch between calls)."""
+        n_imp = self._last_n_imp if n_imp is None else n_imp
+        blocks = [n_imp if b is None else b for b in blocks]
+        _check_spread_args(n_imp, n_rep, blocks)
+        ctx = self._prob.ctx(int(n_imp))
+        if self._spread_est == _native.EST_IS_EP:
+            ctx.set_ep(*self.ep_settings)
+        ctx.u_normal([_UBUF], [seed], [0])
+        slot = ctx.slots.acquire()
+        try:
+            _, st, nops = self._theta_call(self._spread_est, ctx, theta, _UBUF, slot)
+            self._spread_raise(int(st[0]), ctx)
+            self.n_cubic_ops += int(nops[0])
+            res = []
+            for b in blocks:
+                logf, ess, wmax, st = ctx.is_spread([slot], [_UBUF], [seed], [0], n_rep, b)
+                _raise_for_status(int(st[0]), ctx)
+                res.append(_spread_result(logf[0], ess[0], wmax[0], b, nops[0]))
+        finally:
+            ctx.slots.release(slot)
+        return res
+
+    def spread(self, theta, n_rep=32, block=None, seed=0, n_imp=None):
+        """How noisy the log-estimate is at `theta`: one theta-call, then `n_rep` independent
+        redraws of u on the device, each cut into blocks of `block` samples (None: n_imp, one
+        block per replicate). Returns a dict: ``log_estimates`` (n_rep, nblk), one estimate per
+        block; ``sd``, their standard deviation (ddof = 1 over all of them) - the spread of an
+        estimator that uses `block` samples; ``ess`` and ``wmax`` (n_rep, nblk), each block's
+        weight ESS (sum w)^2 / sum w^2 and largest normalised weight; ``block``; ``n_cubic_ops``
+        of the theta-call. `n_imp` defaults to that of the estimator's last call. The draws are
+        the Philox stream (seed, 0 .. n_rep - 1): the same for every block length."""
+        return self._spread_blocks(theta, n_rep, [block], seed, n_imp)[0]
+
+
+def n_imp_curve(estimator, theta, n_rep=32, seed=0, n_imp=None):
+    """``estimator.spread`` at `theta` for every block length 64 * 2^k <= n_imp, and n_imp
+    itself, on the same draws and one theta-call: ``{block: spread dict}``, ascending."""
+    n_imp = getattr(estimator, '_last_n_imp', None) if n_imp is None else n_imp
+    _check_spread_args(n_imp, n_rep, [])
+    blocks = []
+    b = 64
+    while b <= n_imp:
+        blocks.append(b)
+        b *= 2
+    if n_imp not in blocks:
+        blocks.append(int(n_imp))
+    res = estimator._spread_blocks(theta, n_rep, blocks, seed, n_imp)
+    return dict(zip(blocks, res))
+
+
+def select_n_imp(curves, target_sd=1.0):
+    """The smallest block length present in every curve (``n_imp_curve`` dicts) whose ``sd`` is
+    at most `target_sd` in every one of them, or None when no measured length is. A NaN sd does
+    not meet the target."""
+    if not curves:
+        return None
+    common = set(curves[0])
+    for c in curves[1:]:
+        common &= set(c)
+    for b in sorted(common):
+        if all(c[b]['sd'] <= target_sd for c in curves):
+            return b
+    return None
+
+
+def tune_n_imp(estimator, thetas, target_sd=1.0, n_rep=32, seed=0, n_imp=None):
+    """The number of importance samples that keeps the standard deviation of the log-estimate at
+    or below `target_sd` (the pseudo-marginal rule of thumb is about one) at every row of
+    `thetas`: ``(curves, block)`` with ``curves[t] = n_imp_curve(estimator, thetas[t], n_rep)``
+    and ``block`` the smallest measured block length that meets the target at every theta - or
+    None when even n_imp does not.
+
+    Nothing is extrapolated beyond n_imp. Where the target is missed the weights are degenerate
+    (a handful of effective samples), and there the spread falls much slower than 1 / sqrt(N):
+    with the Laplace proposal at a large signal variance (theta_0 = 3, n = 130) the sd at N = 64,
+    128, 256 was measured as 1.66, 1.44, 1.28 where 1 / sqrt(N) scaling from N = 64 predicts
+    1.17 and 0.83. An extrapolated N would be far too small exactly when it is needed; raise
+    n_imp (or change the proposal) and measure again."""
+    curves = [n_imp_curve(estimator, th, n_rep, seed, n_imp) for th in np.atleast_2d(thetas)]
+    return curves, select_n_imp(curves, target_sd)
+
+
 class LogMarginalLikelihoodLaplaceEstimator(_EstimatorBase):
     """Deterministic (biased) Laplace-approximation estimate of log p(y | theta, X)
     (reference estimators.py:19-82)."""
@@ -217,7 +330,7 @@ class LogMarginalLikelihoodEPEstimator(_EstimatorBase):
         return logz
 
 
-class LogMarginalLikelihoodApproxPosteriorISEstimator(_EstimatorBase):
+class LogMarginalLikelihoodApproxPosteriorISEstimator(_SpreadMixin, _EstimatorBase):
     """Unbiased importance-sampling estimate of p(y | theta, X) with the Laplace posterior as
     proposal (reference estimators.py:90-241). ``ns``: (n_data, n_imp_sample) N(0,1) draws.
 
@@ -245,6 +358,10 @@ class LogMarginalLikelihoodApproxPosteriorISEstimator(_EstimatorBase):
             X, y, kernel_func, likelihood)
         self.post_approx_func = post_approx_func
         self.ep_settings = (float(damping), float(diff_tol), int(max_sweeps))
+        self._spread_est = self._est
+
+    def _spread_raise(self, status, ctx):
+        self._raise(status, ctx)
 
     def _raise(self, status, ctx):
         if self._est == _native.EST_IS_EP and status in (
@@ -256,6 +373,7 @@ class LogMarginalLikelihoodApproxPosteriorISEstimator(_EstimatorBase):
         if theta is None and cached_results is None:
             raise ValueError('One of theta or cached_results must be provided')
         ns = np.asarray(ns, dtype=np.float64)
+        self._last_n_imp = ns.shape[1]
         if cached_results is None:
             ctx = self._prob.ctx(ns.shape[1])
             if self._est == _native.EST_IS_EP:
@@ -277,15 +395,18 @@ class LogMarginalLikelihoodApproxPosteriorISEstimator(_EstimatorBase):
         return float(out[0]), cached_results
 
 
-class LogMarginalLikelihoodPriorMCEstimator(_EstimatorBase):
+class LogMarginalLikelihoodPriorMCEstimator(_SpreadMixin, _EstimatorBase):
     """Unbiased simple Monte Carlo estimate of p(y | theta, X) with draws from the GP prior
     (reference estimators.py:244-325). Returns ``(log_estimate, K_chol)``; ``K_chol`` is a
     :class:`DeviceCache`."""
+
+    _spread_est = _native.EST_PRIORMC
 
     def __call__(self, ns, theta=None, K_chol=None):
         if theta is None and K_chol is None:
             raise ValueError('One of theta or K_chol must be provided')
         ns = np.asarray(ns, dtype=np.float64)
+        self._last_n_imp = ns.shape[1]
         if K_chol is None:
             ctx = self._prob.ctx(ns.shape[1])
             ctx.u_upload(_UBUF, ns)

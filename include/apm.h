@@ -16,6 +16,8 @@
  *   apm_ep_predict        fit, log Z_EP, the marginals and the predictive distribution; R&W §3.6)
  *   apm_ep                with the sweeps' factorisations and solves on the device
  *   apm_ep_grad        <- no reference counterpart: the gradient of log Z_EP with respect to theta
+ *   apm_u_eval_diag    <- no reference counterpart: the cached u-call cut into blocks of samples, with
+ *   apm_is_spread         each block's weight ESS, over independent redraws of u on the device
  *   apm_laplace        <- gpdemo/latent_posterior_approximations.py:22-124  laplace_approximation(K, y, ...)
  *   apm_theta_eval     <- gpdemo/estimators.py:201-217 (+ :221-241)  ApproxPosteriorIS.__call__(ns, theta)
  *                         gpdemo/estimators.py:317-325               PriorMC.__call__(ns, theta)
@@ -291,6 +293,37 @@ int apm_ep_grad(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ldt, 
 /* cached u-call: reuse slots[i]'s per-theta state with draws ubufs[i] */
 int apm_u_eval(apm_ctx *ctx, int64_t count, const int64_t *slots, const int64_t *ubufs,
                double *out_logf, int *status);
+/* ---- replicate spread and weight diagnostics of the IS estimate (no reference counterpart;
+ * DESIGN.md §20) -------------------------------------------------------------------------------
+ * For one chain, with slot state and a U buffer of S = n_imp real columns, log w_s is the summand
+ * of the estimate exactly as apm_u_eval forms it. For a block length 1 <= block <= n_imp the
+ * samples are cut into nblk = floor(n_imp / block) blocks, block j being samples [j block,
+ * (j + 1) block); leftover samples are ignored. Per block:
+ *   logf_j = logsumexp_{s in j} log w_s - log(block)     (an estimate from `block` samples)
+ *   ess_j  = (sum w)^2 / sum w^2,  wmax_j = max w / sum w (w = exp(log w_s - block maximum))
+ * and, where the block maximum is not finite, logf_j = max - log(block), ess_j = wmax_j = 0. With
+ * block = n_imp, logf_0 is bitwise apm_u_eval's value. A chain's outputs do not depend on its
+ * position in the batch nor on the other chains. APM_E_INVALID, with nothing written, for block < 1
+ * or > n_imp, n_rep < 1, n_rep nblk > APM_SPREAD_MAX_BLOCKS, ldo < n_rep nblk, count outside [1,
+ * max_batch], null slots / ubufs / status (apm_is_spread: seeds / counters) and indices out of
+ * range. Any of logf, ess, wmax may be NULL. A chain whose slot's last theta-call failed (status
+ * != 0 there: the slot was not written, or its value is withheld) gets apm_u_eval's status and NaN
+ * in all three outputs. Works for slots written by APM_EST_IS, APM_EST_IS_EP and APM_EST_PRIORMC
+ * under both likelihoods. apm_version() is unchanged: detect the entry points by their symbols. */
+#define APM_SPREAD_MAX_BLOCKS 4096
+/* apm_u_eval (the same checks, launches and status) followed by the block reduction: nblk values
+ * per chain into row i of logf / ess / wmax (row stride ldo). Slots and U buffers are only read. */
+int apm_u_eval_diag(apm_ctx *ctx, int64_t count, const int64_t *slots, const int64_t *ubufs,
+                    int64_t block, double *logf, double *ess, double *wmax, int64_t ldo,
+                    int *status);
+/* n_rep independent replicates of the estimate at fixed slot state: for r = 0 .. n_rep - 1 U
+ * buffer ubufs[i] is redrawn as apm_u_normal(seeds[i], counters[i] + r) draws it and the u-path
+ * and the block reduction run on it; replicate r's block j goes to [i ldo + r nblk + j]. All
+ * replicates are enqueued without a host synchronisation; one read-back ends the call. ubufs[i] is
+ * scratch: at return it holds the last replicate's draws. The slots are only read. */
+int apm_is_spread(apm_ctx *ctx, int64_t count, const int64_t *slots, const int64_t *ubufs,
+                  const uint64_t *seeds, const uint64_t *counters, int64_t n_rep, int64_t block,
+                  double *logf, double *ess, double *wmax, int64_t ldo, int *status);
 /* cache-slot lifetimes (samplers.py:563-584: an MH sampler keeps the current state's cache and the
  * proposal's alive at once). acquire: a free slot, one owner (APM_E_NOMEM when all are owned);
  * copy: one more owner of the same (immutable) state - the handle copy of the reference's tuple;
