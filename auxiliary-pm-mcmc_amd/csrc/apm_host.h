@@ -6,7 +6,7 @@
 //   host_chol64.cpp   update-list caches, the fp64 two-level Cholesky schedule (two forms)
 //   host_newton.cpp   fp32 Newton factorisation with its lookahead, the Newton loop, fp64 rerun
 //   host_theta.cpp    the theta-call: concurrent chol(K), posterior factor, guard, ICM check
-//   host_laplace.cpp  apm_laplace's covariance, the predictive and gradient paths
+//   host_laplace.cpp  apm_laplace's fit and covariance, the predictive and gradient paths
 //   host_ep.cpp       the sweep loop of parallel expectation propagation (ep.hip)
 //   host_is_predict.cpp  the importance-sampling predictive's tail after an IS theta-call
 //   host_is_diag.cpp  block estimates and weight diagnostics of the IS estimate over replicates
@@ -280,6 +280,9 @@ void init_ctx(apm_ctx* c, int device, int kind, const double* X, int64_t n, int6
               int64_t ldx, const double* y, double eps, int64_t S, int64_t max_batch,
               int64_t n_slots, int64_t n_ubufs);
 void free_ctx(apm_ctx* c);
+// the cached PRECOMPUTED context of a stand-alone call's shape (apm_laplace_lik, apm_ep), created
+// at the first call (c null) and given the call's labels
+void standalone_ctx(apm_ctx*& c, int device, int64_t n, const double* y);
 
 struct SkewState {  // APM_SKEW (tests only): the calling thread's skew_point setting
     int mode = 0;
@@ -422,12 +425,45 @@ void theta_eval_impl(apm_ctx* c, int est, int count, bool gram, double* out_logf
 
 // ---- host_laplace.cpp -----------------------------------------------------------------------
 void augmented(apm_ctx* c, int count);
+// C = K - V^T V of chain 0's last factor (augmented(): the bottom-right of A, lower) -> both
+// triangles of C_out (n x n, ldc)
+void covariance_out(apm_ctx* c, double* C_out, int64_t ldc);
+// apm_laplace's fit of a host K (n x n, ldk) on a stand-alone context whose settings are made:
+// the mode into f_out and, where asked for (non-null), the covariance and the LML; nothing but
+// status and n_iter_out for a fit that failed
+void laplace_on_K(apm_ctx* c, const double* K, int64_t ldk, double* f_out, double* C_out,
+                  int64_t ldc, double* lml_out, int64_t* n_iter_out, int* status);
 // a Laplace theta-call (Gram, fp64 Newton, LML into lml: count doubles) whose OK chains are then
 // made live again (they left the Newton loop with active = 0) for the passes that reuse the last
 // Newton factor; returns their number
 int laplace_then_live(apm_ctx* c, int count, double* lml, int* status, int64_t* n_iter);
 void predict_buffers(apm_ctx* c);
-void predict_block(apm_ctx* c, int count, const double* xs, int ms);
+void predict_block(apm_ctx* c, int count, int ms);
+// One call's test inputs Xs (m x d, row stride ldxs), a block of at most np rows at a time: the
+// constructor uploads the chains' s = exp(theta_0) to psig (predict_buffers() first), upload()
+// packs rows [r0, r0 + ms) and sends them to pxs (returns ms), rows_back() enqueues the copy of
+// the block's pmean / pvar / pprob rows to the caller's arrays (count x m, row stride ldo, any of
+// them null). The two users copy back differently on purpose: the Laplace / EP predictive every
+// row with one 2-D copy per output (only_ok null; rows of failed chains hold stale values, which
+// the C-ABI overwrites), the IS predictive the rows of the chains that are OK in only_ok, because
+// it leaves the caller's other rows untouched. The object stays alive until the sync after the
+// last block.
+struct TestInputs {
+    apm_ctx* c;
+    int count;
+    const double* Xs;
+    int64_t m, ldxs;
+    std::vector<double> xs, sig;
+    TestInputs(apm_ctx* c, int count, const double* thetas, int64_t ldt, const double* Xs,
+               int64_t m, int64_t ldxs);
+    int upload(int64_t r0);
+    void rows_back(int64_t r0, int ms, const int* only_ok, double* mean, double* var, double* prob,
+                   int64_t ldo);
+};
+// the predictive distribution of the live chains' state (S^1/2 or W^1/2 in v.Ws, a, the factor in
+// A) at the m test inputs, in blocks of the free rows of A; outputs count x m, row stride ldo
+void predict_all(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, const double* Xs,
+                 int64_t m, int64_t ldxs, double* mean, double* var, double* prob, int64_t ldo);
 void grad_buffers(apm_ctx* c);
 void grad_block(apm_ctx* c, int count);
 // grad_block's second pass for the chains left live by ep_fit: d log Z_EP / d theta into c->gout
@@ -461,5 +497,17 @@ void ep_buffers(apm_ctx* c);
 // the factor in A / Dinv / ldet); host status per chain in st_h, sweeps in c->n_iter. The OK
 // chains are live again on return (active = 1), as after laplace_then_live; returns their number
 int ep_fit(apm_ctx* c, int count, std::vector<int>& st_h);
+// ep_fit with the copy of the sweep counts enqueued behind it: f.sweeps holds them after the
+// caller's next synchronisation of the main stream, until which f stays alive
+struct EpFit {
+    std::vector<int> st, sweeps;
+    int ok = 0;  // chains left OK (and live)
+};
+void ep_fit_counted(apm_ctx* c, int count, EpFit& f);
+// the Gram of the call's thetas (K's lower tiles, as a Laplace theta-call), then ep_fit_counted
+void ep_gram_fit(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, EpFit& f);
+// count x n device vectors (row stride src_ld) -> host rows (row stride ldo), if asked for
+void ep_fetch(apm_ctx* c, double* dst, int64_t ldo, const double* src, int64_t src_ld,
+              int64_t count);
 
 }  // namespace apm_host

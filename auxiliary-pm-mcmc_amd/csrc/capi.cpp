@@ -1,9 +1,13 @@
-// The C-ABI (include/apm.h): argument checks, the per-call staging of the host's inputs and the
-// translation of a HipError into APM_E_HIP. The orchestration behind the entry points is in the
-// host_*.cpp units (apm_host.h).
+// The C-ABI (include/apm.h): argument checks, the per-call staging of the host's inputs, the
+// translation of a HipError into APM_E_HIP and the NaN rows of failed chains, each frame written
+// once (ctx_call, cached_call, check_theta_call, finish_rows). The orchestration behind the entry
+// points is in the host_*.cpp units (apm_host.h): a batched theta-call here names its fit and its
+// tail there and launches nothing itself. What still launches from this file is one kernel behind
+// a staged copy (the U-buffer calls, apm_gram, apm_gram_cross, the self-tests, the marker).
 #include <cmath>
 #include <limits>
 #include <mutex>
+#include <optional>
 
 #include "apm_host.h"
 
@@ -34,62 +38,112 @@ bool check_idx(apm_ctx* c, int64_t count, const int64_t* idx, int64_t lim, const
 std::mutex g_mu;
 std::map<std::tuple<int, int64_t, int64_t, int>, apm_ctx*> g_cache;
 
-// the predictive distribution of the live chains' state (S^1/2 or W^1/2 in v.Ws, a, the factor in
-// A) at the m test inputs, in blocks of the free rows of A; outputs count x m, row stride ldo
-void predict_all(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, const double* Xs,
-                 int64_t m, int64_t ldxs, double* mean, double* var, double* prob, int64_t ldo) {
-    predict_buffers(c);
-    std::vector<double> xs, sig((size_t)count);  // (alive until the blocks' syncs)
-    for (int64_t b = 0; b < count; ++b) sig[b] = std::exp(thetas[b * ldt]);
-    HIPC(hipMemcpyAsync(c->psig, sig.data(), sizeof(double) * count, hipMemcpyHostToDevice,
-                        c->stream));
-    for (int64_t r0 = 0; r0 < m; r0 += c->np) {
-        const int ms = (int)std::min<int64_t>(c->np, m - r0);
-        xs.resize((size_t)ms * c->d);
-        for (int i = 0; i < ms; ++i)
-            for (int k = 0; k < c->d; ++k) xs[(size_t)i * c->d + k] = Xs[(r0 + i) * ldxs + k];
-        predict_block(c, (int)count, xs.data(), ms);
-        const std::pair<double*, const double*> outs[3] = {
-            {mean, c->pmean}, {var, c->pvar}, {prob, c->pprob}};
-        for (const auto& o : outs)
-            if (o.first)
-                HIPC(hipMemcpy2DAsync(o.first + r0, sizeof(double) * ldo, o.second,
-                                      sizeof(double) * c->np, sizeof(double) * ms, count,
-                                      hipMemcpyDeviceToHost, c->stream));
-        sync(c);  // (xs is reused by the next block)
+// A context entry point: its launches belong to c (the SkewScope, where the entry point opens
+// one), on c's device, and a HipError of the body becomes APM_E_HIP. The body returns nothing; an
+// early `return` in it ends the call with APM_SUCCESS.
+enum Skew { NO_SKEW, SKEW };
+template <class Body>
+int ctx_call(apm_ctx* c, Skew skew, Body body) {
+    std::optional<SkewScope> scope;
+    if (skew == SKEW) scope.emplace(c);
+    try {
+        HIPC(hipSetDevice(c->device));
+        body();
+    } catch (const HipError& e) {
+        return fail(c, APM_E_HIP, e.msg);
     }
+    return APM_SUCCESS;
 }
 
-// the cached PRECOMPUTED context of a stand-alone call's shape (apm_laplace_lik, apm_ep), created
-// at the first call and given the call's labels
-void standalone_ctx(apm_ctx*& c, int device, int64_t n, const double* y) {
-    if (!c) {
-        c = new apm_ctx();
-        init_ctx(c, device, APM_KERNEL_PRECOMPUTED, nullptr, n, 0, 0, y, 1e-8, 1, 1, 1, 1);
-    } else {
-        HIPC(hipSetDevice(device));
-        std::vector<double> yp((size_t)c->np, 0.0);
-        for (int64_t i = 0; i < n; ++i) yp[i] = y[i];
-        HIPC(hipMemcpyAsync(c->y, yp.data(), sizeof(double) * c->np, hipMemcpyHostToDevice,
-                            c->stream));
-    }
-}
-
-// C = K - V^T V of chain 0's last factor (augmented(): the bottom-right of A, lower) -> both
-// triangles of C_out (n x n, ldc)
-void covariance_out(apm_ctx* c, double* C_out, int64_t ldc) {
-    const int np = c->np;
-    augmented(c, 1);
-    std::vector<double> Cb((size_t)np * np);
-    HIPC(hipMemcpy2DAsync(Cb.data(), sizeof(double) * np, c->A.base + (int64_t)np * c->A.ld + np,
-                          sizeof(double) * c->A.ld, sizeof(double) * np, np,
-                          hipMemcpyDeviceToHost, c->stream));
-    sync(c);
-    for (int64_t i = 0; i < c->n; ++i)
-        for (int64_t j = 0; j <= i; ++j) {
-            C_out[i * ldc + j] = Cb[(size_t)i * np + j];
-            C_out[j * ldc + i] = Cb[(size_t)i * np + j];
+// A stand-alone call on the cached context of its (device, n, d, kind) shape; the body creates or
+// refreshes it (c is null at the shape's first call). A HipError frees the context and forgets it.
+template <class Body>
+int cached_call(int device, int64_t n, int64_t d, int kind, Body body) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    apm_ctx*& c = g_cache[std::make_tuple(device, n, d, kind)];
+    try {
+        body(c);
+    } catch (const HipError& e) {
+        if (c) {
+            free_ctx(c);
+            c = nullptr;
         }
+        return fail(nullptr, APM_E_HIP, e.msg);
+    }
+    return APM_SUCCESS;
+}
+
+// ---- the batched theta-calls (apm_predict, apm_laplace_grad, apm_ep_eval, apm_ep_predict,
+// apm_ep_grad, apm_is_predict): at most max_batch rows of theta, a fit, a tail on the chains that
+// are OK, NaN rows for the others (the source map, says what a new one supplies)
+
+// What such a call has checked, in the one order all of them keep: the context, `early`, the
+// likelihood, the covariance kind, m, count, ldo, ldt, ldg, and last whatever else the entry point
+// names (rest_bad: evaluated only with a context).
+struct ThetaArgs {
+    const char* early = nullptr;  // a refusal that needs no context (apm_is_predict's est)
+    bool probit_only = false;
+    const char* device_why = "";  // why a PRECOMPUTED context is refused: "needs ... (...)"
+    bool batch = false;           // count in [1, max_batch]
+    int64_t count = 0;
+    bool rows = false;            // m > 0 and ldo >= m, a message each
+    int64_t m = 0, ldo = 0;
+    bool lds = false;             // ldt, ldg >= theta length, a message each
+    int64_t ldt = 0, ldg = 0;
+    const char* rest_msg = "bad arguments";
+};
+template <class Rest>
+int check_theta_call(apm_ctx* c, const char* who, const ThetaArgs& a, Rest rest_bad) {
+    const auto no = [&](apm_ctx* cc, const char* m) {
+        return fail(cc, APM_E_INVALID, std::string(who) + ": " + m);
+    };
+    if (!c) return no(nullptr, "null context");
+    if (a.early) return no(c, a.early);
+    if (a.probit_only && c->lik != APM_LIK_PROBIT)
+        return no(c, "probit only (the logit's tilted moments need quadrature)");
+    if (c->kind == APM_KERNEL_PRECOMPUTED) return no(c, a.device_why);
+    if (a.rows && a.m <= 0) return no(c, "m <= 0");
+    if (a.batch && (a.count <= 0 || a.count > c->max_batch))
+        return no(c, "count outside [1, max_batch]");
+    if (a.rows && a.ldo < a.m) return no(c, "ldo < m");
+    if (a.lds && a.ldt < c->P) return no(c, "ldt < theta length");
+    if (a.lds && a.ldg < c->P) return no(c, "ldg < theta length");
+    if (rest_bad()) return no(c, a.rest_msg);
+    return APM_SUCCESS;
+}
+
+// NaN where the chain's status is not OK: in its row of each (pointer, row stride, width), a null
+// pointer skipped, and in its entry of the per-chain scalars
+struct Rows {
+    double* p;
+    int64_t ld, width;
+};
+void finish_rows(int64_t count, const int* status, std::initializer_list<Rows> rows,
+                 std::initializer_list<double*> scalars = {}) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int64_t b = 0; b < count; ++b) {
+        if (status[b] == APM_STATUS_OK) continue;
+        for (const Rows& r : rows)
+            if (r.p) std::fill(r.p + b * r.ld, r.p + b * r.ld + r.width, nan);
+        for (double* s : scalars)
+            if (s) s[b] = nan;
+    }
+}
+
+// an EP fit's statuses and sweep counts to the caller (after the sync behind ep_*fit*)
+void ep_report(const EpFit& f, int64_t count, int* status, int64_t* n_sweeps) {
+    for (int64_t b = 0; b < count; ++b) {
+        status[b] = f.st[b];
+        if (n_sweeps) n_sweeps[b] = f.sweeps[b];
+    }
+}
+
+// count staged rows of `width` doubles -> the caller's rows (row stride ld), if asked for
+void rows_out(double* dst, int64_t ld, const std::vector<double>& src, int64_t count,
+              int64_t width) {
+    if (dst)
+        for (int64_t b = 0; b < count; ++b)
+            std::copy(src.begin() + b * width, src.begin() + (b + 1) * width, dst + b * ld);
 }
 
 }  // namespace
@@ -158,34 +212,25 @@ void* apm_stream(apm_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 int apm_u_upload(apm_ctx* c, int64_t ubuf, const double* U, int64_t ldu) {
     if (!c || !U || ubuf < 0 || ubuf >= c->n_ubufs || ldu < c->S)
         return fail(c, APM_E_INVALID, "apm_u_upload: bad arguments");
-    const SkewScope skew(c);
-    try {
-        HIPC(hipSetDevice(c->device));
+    return ctx_call(c, SKEW, [&] {
         HIPC(hipMemcpy2DAsync(c->U64, sizeof(double) * c->S, U, sizeof(double) * ldu,
                               sizeof(double) * c->S, c->n, hipMemcpyHostToDevice, c->stream));
         launch_u_convert(c->U64, c->S, c->n, c->S, c->Up, ubuf, c->stream);
         sync(c);
-    } catch (const HipError& e) {
-        return fail(c, APM_E_HIP, e.msg);
-    }
-    return APM_SUCCESS;
+    });
 }
 
 int apm_u_download(apm_ctx* c, int64_t ubuf, double* U, int64_t ldu) {
     if (!c || !U || ubuf < 0 || ubuf >= c->n_ubufs || ldu < c->S)
         return fail(c, APM_E_INVALID, "apm_u_download: bad arguments");
-    try {
-        HIPC(hipSetDevice(c->device));
+    return ctx_call(c, NO_SKEW, [&] {
         std::vector<double> h((size_t)c->np * c->sp);
         HIPC(hipMemcpyAsync(h.data(), c->Up.base + ubuf * c->Up.stride, sizeof(double) * h.size(),
                             hipMemcpyDeviceToHost, c->stream));
         sync(c);
         for (int i = 0; i < c->n; ++i)
             for (int s = 0; s < c->S; ++s) U[(int64_t)i * ldu + s] = h[(size_t)i * c->sp + s];
-    } catch (const HipError& e) {
-        return fail(c, APM_E_HIP, e.msg);
-    }
-    return APM_SUCCESS;
+    });
 }
 
 int apm_u_normal(apm_ctx* c, int64_t count, const int64_t* ubufs, const uint64_t* seeds,
@@ -193,9 +238,7 @@ int apm_u_normal(apm_ctx* c, int64_t count, const int64_t* ubufs, const uint64_t
     if (!c || count <= 0 || count > c->max_batch || !ubufs || !seeds || !counters)
         return fail(c, APM_E_INVALID, "apm_u_normal: bad arguments");
     if (!check_idx(c, count, ubufs, c->n_ubufs, "ubuf")) return APM_E_INVALID;
-    const SkewScope skew(c);
-    try {
-        HIPC(hipSetDevice(c->device));
+    return ctx_call(c, SKEW, [&] {
         std::memcpy(blk_field(c, BLK_I3), ubufs, sizeof(int64_t) * count);
         std::memcpy(blk_field(c, BLK_SEEDS), seeds, sizeof(uint64_t) * count);
         std::memcpy(blk_field(c, BLK_CTRS), counters, sizeof(uint64_t) * count);
@@ -204,10 +247,7 @@ int apm_u_normal(apm_ctx* c, int64_t count, const int64_t* ubufs, const uint64_t
         launch_u_normal(c->Up, c->d_i3, c->d_seeds, c->d_ctrs, c->n, c->S, (int)count,
                         c->stream);
         sync(c);
-    } catch (const HipError& e) {
-        return fail(c, APM_E_HIP, e.msg);
-    }
-    return APM_SUCCESS;
+    });
 }
 
 int apm_u_combine(apm_ctx* c, int64_t count, const int64_t* dst, const int64_t* a,
@@ -217,9 +257,7 @@ int apm_u_combine(apm_ctx* c, int64_t count, const int64_t* dst, const int64_t* 
     if (!check_idx(c, count, dst, c->n_ubufs, "dst") || !check_idx(c, count, a, c->n_ubufs, "a") ||
         !check_idx(c, count, b, c->n_ubufs, "b"))
         return APM_E_INVALID;
-    const SkewScope skew(c);
-    try {
-        HIPC(hipSetDevice(c->device));
+    return ctx_call(c, SKEW, [&] {
         const int64_t B = c->max_batch;
         std::memcpy(blk_field(c, BLK_I3), dst, sizeof(int64_t) * count);
         std::memcpy(blk_field(c, BLK_A), a, sizeof(int64_t) * count);
@@ -231,10 +269,7 @@ int apm_u_combine(apm_ctx* c, int64_t count, const int64_t* dst, const int64_t* 
         launch_u_combine(c->Up, c->d_i3, c->d_i3 + BLK_A * B, c->d_i3 + BLK_B * B, c->d_ca,
                          c->d_cb, c->n, c->S, (int)count, c->stream);
         sync(c);
-    } catch (const HipError& e) {
-        return fail(c, APM_E_HIP, e.msg);
-    }
-    return APM_SUCCESS;
+    });
 }
 
 int apm_theta_eval(apm_ctx* c, int est, int64_t count, const double* thetas, int64_t ldt,
@@ -252,9 +287,7 @@ int apm_theta_eval(apm_ctx* c, int est, int64_t count, const double* thetas, int
             !check_idx(c, count, ubufs, c->n_ubufs, "ubuf"))
             return APM_E_INVALID;
     }
-    const SkewScope skew(c);
-    try {
-        HIPC(hipSetDevice(c->device));
+    return ctx_call(c, SKEW, [&] {
         const double* th = upload_thetas(c, count, thetas, ldt);
         // fp16x3 Newton updates need |L_ij| <= sqrt(1 + K_ii) < 65504 (chol32_update.hip): per chain;
         // the posterior bottom block's operands |L'_ij| <= sqrt(1 + n K_ii) (postcov.hip)
@@ -267,10 +300,7 @@ int apm_theta_eval(apm_ctx* c, int est, int64_t count, const double* thetas, int
         upload_h3(c, (int)count);
         if (est != APM_EST_LAPLACE) upload_idx(c, (int)count, slots, ubufs);
         theta_eval_impl(c, est, (int)count, true, out_logf, status, nops);
-    } catch (const HipError& e) {
-        return fail(c, APM_E_HIP, e.msg);
-    }
-    return APM_SUCCESS;
+    });
 }
 
 int apm_theta_eval_K(apm_ctx* c, int est, const double* K, int64_t ldk, int64_t ubuf,
@@ -283,9 +313,7 @@ int apm_theta_eval_K(apm_ctx* c, int est, const double* K, int64_t ldk, int64_t 
     if (est != APM_EST_LAPLACE &&
         (slot < 0 || slot >= c->n_slots || ubuf < 0 || ubuf >= c->n_ubufs))
         return fail(c, APM_E_INVALID, "apm_theta_eval_K: slot/ubuf out of range");
-    const SkewScope skew(c);
-    try {
-        HIPC(hipSetDevice(c->device));
+    return ctx_call(c, SKEW, [&] {
         std::vector<double> Kp;  // (alive until theta_eval_impl's syncs)
         const double kmax = upload_padded_K(c, K, ldk, Kp);
         pin_h3(c)[0] = c->h3 && kmax < 1.8e8;  // sqrt(1 + K_ii) < 1.4e4 (chol32_update.hip)
@@ -295,10 +323,7 @@ int apm_theta_eval_K(apm_ctx* c, int est, const double* K, int64_t ldk, int64_t 
         upload_h3(c, 1);
         upload_idx(c, 1, &slot, &ubuf);  // (the pinned copy is the slot the read-back marks)
         theta_eval_impl(c, est, 1, false, out_logf, status, nops);
-    } catch (const HipError& e) {
-        return fail(c, APM_E_HIP, e.msg);
-    }
-    return APM_SUCCESS;
+    });
 }
 
 int apm_u_eval(apm_ctx* c, int64_t count, const int64_t* slots, const int64_t* ubufs,
@@ -308,9 +333,7 @@ int apm_u_eval(apm_ctx* c, int64_t count, const int64_t* slots, const int64_t* u
     if (!check_idx(c, count, slots, c->n_slots, "slot") ||
         !check_idx(c, count, ubufs, c->n_ubufs, "ubuf"))
         return APM_E_INVALID;
-    const SkewScope skew(c);
-    try {
-        HIPC(hipSetDevice(c->device));
+    return ctx_call(c, SKEW, [&] {
         upload_idx(c, (int)count, slots, ubufs);
         HIPC(hipMemsetAsync(c->status, 0, sizeof(int) * count, c->stream));
         bool wide = false;
@@ -318,10 +341,7 @@ int apm_u_eval(apm_ctx* c, int64_t count, const int64_t* slots, const int64_t* u
         u_eval_device(c, (int)count, wide);
         read_back(c, {RB{c->out, (int)sizeof(double) * (int)count, out_logf},
                       RB{c->status, (int)sizeof(int) * (int)count, status}});
-    } catch (const HipError& e) {
-        return fail(c, APM_E_HIP, e.msg);
-    }
-    return APM_SUCCESS;
+    });
 }
 
 // ---- block estimates and weight diagnostics of the IS estimate (host_is_diag.cpp) ------------
@@ -347,15 +367,10 @@ int is_diag_call(apm_ctx* c, const char* who, int64_t count, const int64_t* slot
     if (!check_idx(c, count, slots, c->n_slots, "slot") ||
         !check_idx(c, count, ubufs, c->n_ubufs, "ubuf"))
         return APM_E_INVALID;
-    const SkewScope skew(c);
-    try {
-        HIPC(hipSetDevice(c->device));
+    return ctx_call(c, SKEW, [&] {
         is_diag_run(c, (int)count, slots, ubufs, draws ? seeds : nullptr, counters, n_rep, block,
                     logf, ess, wmax, ldo, status);
-    } catch (const HipError& e) {
-        return fail(c, APM_E_HIP, e.msg);
-    }
-    return APM_SUCCESS;
+    });
 }
 
 }  // namespace
@@ -412,8 +427,7 @@ int64_t apm_cache_refcount(const apm_ctx* c, int64_t slot) {
 int apm_slot_read(apm_ctx* c, int64_t slot, double* L, int64_t ldl, double* f_post, double* g,
                   double* cst) {
     if (!c || slot < 0 || slot >= c->n_slots) return fail(c, APM_E_INVALID, "apm_slot_read: bad slot");
-    try {
-        HIPC(hipSetDevice(c->device));
+    return ctx_call(c, NO_SKEW, [&] {
         const int64_t np = c->np;
         if (L || g) {
             std::vector<float> h((size_t)((np + 64) * np));
@@ -435,10 +449,7 @@ int apm_slot_read(apm_ctx* c, int64_t slot, double* L, int64_t ldl, double* f_po
             HIPC(hipMemcpyAsync(cst, c->Sl.cst + slot, sizeof(double), hipMemcpyDeviceToHost,
                                 c->stream));
         sync(c);
-    } catch (const HipError& e) {
-        return fail(c, APM_E_HIP, e.msg);
-    }
-    return APM_SUCCESS;
+    });
 }
 
 int apm_gram(int device, int kind, const double* X, int64_t n, int64_t d, int64_t ldx,
@@ -448,10 +459,7 @@ int apm_gram(int device, int kind, const double* X, int64_t n, int64_t d, int64_
         return fail(nullptr, APM_E_INVALID, "apm_gram: bad arguments");
     const int64_t P = kernel_kind_of(kind).theta_len(d);
     if (n_theta < P) return fail(nullptr, APM_E_INVALID, "apm_gram: theta too short");
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto key = std::make_tuple(device, n, d, kind + 16);
-    apm_ctx*& c = g_cache[key];
-    try {
+    return cached_call(device, n, d, kind + 16, [&](apm_ctx*& c) {
         if (!c) {
             c = new apm_ctx();
             init_ctx(c, device, kind, X, n, d, ldx, nullptr, eps, 1, 1, 1, 1);
@@ -471,14 +479,7 @@ int apm_gram(int device, int kind, const double* X, int64_t n, int64_t d, int64_
         HIPC(hipMemcpy2DAsync(K, sizeof(double) * ldk, c->K.base, sizeof(double) * c->np,
                               sizeof(double) * n, n, hipMemcpyDeviceToHost, c->stream));
         sync(c);
-    } catch (const HipError& e) {
-        if (c) {
-            free_ctx(c);
-            c = nullptr;
-        }
-        return fail(nullptr, APM_E_HIP, e.msg);
-    }
-    return APM_SUCCESS;
+    });
 }
 
 int apm_gram_cross(int device, int kind, const double* Xs, int64_t m, const double* X, int64_t n,
@@ -518,90 +519,62 @@ int apm_gram_cross(int device, int kind, const double* Xs, int64_t m, const doub
 int apm_predict(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, const double* Xs,
                 int64_t m, int64_t ldxs, double* mean, double* var, double* prob, int64_t ldo,
                 int* status, int64_t* n_iter) {
-    if (!c) return fail(nullptr, APM_E_INVALID, "apm_predict: null context");
-    if (c->kind == APM_KERNEL_PRECOMPUTED)
-        return fail(c, APM_E_INVALID, "apm_predict: needs an ISO or ARD context (the cross-"
-                                      "covariance is built on the device)");
-    if (m <= 0) return fail(c, APM_E_INVALID, "apm_predict: m <= 0");
-    if (count <= 0 || count > c->max_batch)
-        return fail(c, APM_E_INVALID, "apm_predict: count outside [1, max_batch]");
-    if (ldo < m) return fail(c, APM_E_INVALID, "apm_predict: ldo < m");
-    if (!thetas || !Xs || !status || ldt < c->P || ldxs < c->d)
-        return fail(c, APM_E_INVALID, "apm_predict: bad arguments");
-    const SkewScope skew(c);
-    try {
-        HIPC(hipSetDevice(c->device));
+    ThetaArgs a;
+    a.device_why = "needs an ISO or ARD context (the cross-covariance is built on the device)";
+    a.batch = a.rows = true;
+    a.count = count, a.m = m, a.ldo = ldo;
+    const int rc = check_theta_call(c, "apm_predict", a, [&] {
+        return !thetas || !Xs || !status || ldt < c->P || ldxs < c->d;
+    });
+    if (rc != APM_SUCCESS) return rc;
+    return ctx_call(c, SKEW, [&] {
         upload_thetas(c, count, thetas, ldt);
         std::vector<double> lml((size_t)count);
-        if (laplace_then_live(c, (int)count, lml.data(), status, n_iter)) {
+        if (laplace_then_live(c, (int)count, lml.data(), status, n_iter))
             predict_all(c, count, thetas, ldt, Xs, m, ldxs, mean, var, prob, ldo);
-        }
-        const double nan = std::numeric_limits<double>::quiet_NaN();
-        for (int64_t b = 0; b < count; ++b)
-            if (status[b] != APM_STATUS_OK)
-                for (double* o : {mean, var, prob})
-                    if (o) std::fill(o + b * ldo, o + b * ldo + m, nan);
-    } catch (const HipError& e) {
-        return fail(c, APM_E_HIP, e.msg);
-    }
-    return APM_SUCCESS;
+        finish_rows(count, status, {{mean, ldo, m}, {var, ldo, m}, {prob, ldo, m}});
+    });
 }
 
 int apm_is_predict(apm_ctx* c, int est, int64_t count, const double* thetas, int64_t ldt,
                    const int64_t* ubufs, const int64_t* slots, const double* Xs, int64_t m,
                    int64_t ldxs, double* out_logf, double* prob, double* mean, double* var,
                    int64_t ldo, double* ess, int* status, int64_t* nops) {
-    if (!c) return fail(nullptr, APM_E_INVALID, "apm_is_predict: null context");
-    if (est != APM_EST_IS && est != APM_EST_IS_EP)
-        return fail(c, APM_E_INVALID, "apm_is_predict: APM_EST_IS or APM_EST_IS_EP only");
-    if (c->kind == APM_KERNEL_PRECOMPUTED)
-        return fail(c, APM_E_INVALID, "apm_is_predict: needs a context whose covariance is built "
-                                      "on the device (the cross-covariance is)");
-    if (m <= 0 || ldo < m || !Xs || ldxs < c->d)
-        return fail(c, APM_E_INVALID, "apm_is_predict: bad test inputs or ldo < m");
+    ThetaArgs a;
+    if (est != APM_EST_IS && est != APM_EST_IS_EP) a.early = "APM_EST_IS or APM_EST_IS_EP only";
+    a.device_why = "needs a context whose covariance is built on the device (the cross-"
+                   "covariance is)";
+    a.rest_msg = "bad test inputs or ldo < m";
+    int rc = check_theta_call(c, "apm_is_predict", a, [&] {
+        return m <= 0 || ldo < m || !Xs || ldxs < c->d;
+    });
     // the theta-call itself: apm_theta_eval's checks (count, the logit's IS_EP refusal, indices),
     // staging and values
-    const int rc = apm_theta_eval(c, est, count, thetas, ldt, ubufs, slots, out_logf, status, nops);
+    if (rc == APM_SUCCESS)
+        rc = apm_theta_eval(c, est, count, thetas, ldt, ubufs, slots, out_logf, status, nops);
     if (rc != APM_SUCCESS) return rc;
-    const SkewScope skew(c);
-    try {
+    return ctx_call(c, SKEW, [&] {
         int ok = 0;
         for (int64_t b = 0; b < count; ++b) ok += status[b] == APM_STATUS_OK;
         if (ok)
             is_predict_tail(c, (int)count, thetas, ldt, status, Xs, m, ldxs, prob, mean, var, ldo,
                             ess);
-        const double nan = std::numeric_limits<double>::quiet_NaN();
-        for (int64_t b = 0; b < count; ++b) {
-            if (status[b] != APM_STATUS_OK) {
-                for (double* o : {mean, var, prob})
-                    if (o) std::fill(o + b * ldo, o + b * ldo + m, nan);
-                if (ess) ess[b] = nan;
-            } else if (nops) {
-                nops[b] += 2;  // the tail's chol(K) and chol(J M J); the row solves count as
-                               // apm_predict's do: not at all
-            }
-        }
-    } catch (const HipError& e) {
-        return fail(c, APM_E_HIP, e.msg);
-    }
-    return APM_SUCCESS;
+        finish_rows(count, status, {{mean, ldo, m}, {var, ldo, m}, {prob, ldo, m}}, {ess});
+        // the tail's chol(K) and chol(J M J); the row solves count as apm_predict's do: not at all
+        for (int64_t b = 0; nops && b < count; ++b) nops[b] += status[b] == APM_STATUS_OK ? 2 : 0;
+    });
 }
 
 int apm_laplace_grad(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, double* lml,
                      double* grad, int64_t ldg, int* status, int64_t* n_iter) {
-    if (!c) return fail(nullptr, APM_E_INVALID, "apm_laplace_grad: null context");
-    if (c->kind == APM_KERNEL_PRECOMPUTED)
-        return fail(c, APM_E_INVALID, "apm_laplace_grad: needs an ISO or ARD context (dK/dtheta "
-                                      "is built on the device)");
-    if (count <= 0 || count > c->max_batch)
-        return fail(c, APM_E_INVALID, "apm_laplace_grad: count outside [1, max_batch]");
-    if (ldt < c->P) return fail(c, APM_E_INVALID, "apm_laplace_grad: ldt < theta length");
-    if (ldg < c->P) return fail(c, APM_E_INVALID, "apm_laplace_grad: ldg < theta length");
-    if (!thetas || !grad || !status)
-        return fail(c, APM_E_INVALID, "apm_laplace_grad: bad arguments");
-    const SkewScope skew(c);
-    try {
-        HIPC(hipSetDevice(c->device));
+    ThetaArgs a;
+    a.device_why = "needs an ISO or ARD context (dK/dtheta is built on the device)";
+    a.batch = a.lds = true;
+    a.count = count, a.ldt = ldt, a.ldg = ldg;
+    const int rc = check_theta_call(c, "apm_laplace_grad", a,
+                                    [&] { return !thetas || !grad || !status; });
+    if (rc != APM_SUCCESS) return rc;
+    return ctx_call(c, SKEW, [&] {
         upload_thetas(c, count, thetas, ldt);
         std::vector<double> val((size_t)count), gh((size_t)count * c->P);
         if (laplace_then_live(c, (int)count, val.data(), status, n_iter)) {
@@ -611,16 +584,10 @@ int apm_laplace_grad(apm_ctx* c, int64_t count, const double* thetas, int64_t ld
                                 hipMemcpyDeviceToHost, c->stream));
             sync(c);
         }
-        const double nan = std::numeric_limits<double>::quiet_NaN();
-        for (int64_t b = 0; b < count; ++b) {
-            const bool good = status[b] == APM_STATUS_OK;
-            if (lml) lml[b] = good ? val[b] : nan;
-            for (int p = 0; p < c->P; ++p) grad[b * ldg + p] = good ? gh[b * c->P + p] : nan;
-        }
-    } catch (const HipError& e) {
-        return fail(c, APM_E_HIP, e.msg);
-    }
-    return APM_SUCCESS;
+        rows_out(lml, 1, val, count, 1);
+        rows_out(grad, ldg, gh, count, c->P);
+        finish_rows(count, status, {{grad, ldg, c->P}}, {lml});
+    });
 }
 
 int apm_laplace(int device, const double* K, int64_t n, int64_t ldk, const double* y,
@@ -638,46 +605,14 @@ int apm_laplace_lik(int device, int lik, const double* K, int64_t n, int64_t ldk
         (calc_cov && (!C_out || ldc < n)) || (calc_lml && !lml_out) ||
         (lik != APM_LIK_PROBIT && lik != APM_LIK_LOGIT))
         return fail(nullptr, APM_E_INVALID, "apm_laplace: bad arguments");
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto key = std::make_tuple(device, n, (int64_t)0, (int)APM_KERNEL_PRECOMPUTED);
-    apm_ctx*& c = g_cache[key];
-    try {
+    return cached_call(device, n, 0, APM_KERNEL_PRECOMPUTED, [&](apm_ctx*& c) {
         standalone_ctx(c, device, n, y);
         c->tol = diff_f_tol;
         c->max_iters = max_iters;
         c->lik = lik;  // (the shape's cached context serves both likelihoods)
-        std::vector<double> Kp;  // (alive until the syncs below)
-        upload_padded_K(c, K, ldk, Kp);
-        HIPC(hipMemsetD32Async(c->active, 1, 1, c->stream));
-        HIPC(hipMemsetAsync(c->status, 0, sizeof(int), c->stream));
-        HIPC(hipMemsetAsync(c->n_iter, 0, sizeof(int), c->stream));
-        std::vector<int> st(1, 0);
-        c->live_n = 1;
-        newton(c, 1, st, false, 1);
-        int it = 0;
-        HIPC(hipMemcpyAsync(&it, c->n_iter, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        sync(c);
-        *status = st[0];
-        if (n_iter_out) *n_iter_out = it;
-        if (st[0] != APM_STATUS_OK) return APM_SUCCESS;
-        HIPC(hipMemcpyAsync(f_out, c->v.f, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-        if (calc_lml) {
-            launch_laplace_lml(c->lik, c->v, c->y, (int)n, c->ldet, c->lstride, c->nb, c->out,
-                               live_of(c), 1, c->stream);
-            HIPC(hipMemcpyAsync(lml_out, c->out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        }
-        if (calc_cov) {
-            covariance_out(c, C_out, ldc);
-        }
-        sync(c);
-    } catch (const HipError& e) {
-        if (c) {
-            free_ctx(c);
-            c = nullptr;
-        }
-        return fail(nullptr, APM_E_HIP, e.msg);
-    }
-    return APM_SUCCESS;
+        laplace_on_K(c, K, ldk, f_out, calc_cov ? C_out : nullptr, ldc,
+                     calc_lml ? lml_out : nullptr, n_iter_out, status);
+    });
 }
 
 // ---- expectation propagation (host_ep.cpp) -----------------------------------
@@ -685,26 +620,6 @@ namespace {
 
 bool ep_settings_ok(double damping, double diff_tol, int64_t max_sweeps) {
     return damping > 0.0 && damping <= 1.0 && diff_tol >= 0.0 && max_sweeps >= 1;
-}
-
-// the Gram of the call's thetas (K's lower tiles, as a Laplace theta-call) and the EP fit
-int ep_gram_fit(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt,
-                std::vector<int>& st_h) {
-    upload_thetas(c, count, thetas, ldt);
-    HIPC(hipMemsetD32Async(c->active, 1, count, c->stream));
-    HIPC(hipMemsetAsync(c->status, 0, sizeof(int) * count, c->stream));
-    c->k_full = false;
-    launch_gram(c->K, c->X, c->d, c->n, c->d, c->theta, c->P, c->kind, c->eps, c->np, live_of(c),
-                (int)count, c->stream, /*both=*/false);
-    return ep_fit(c, (int)count, st_h);
-}
-
-// count x n device vectors (row stride src_ld) -> host rows (row stride ldo), if asked for
-void ep_fetch(apm_ctx* c, double* dst, int64_t ldo, const double* src, int64_t src_ld,
-              int64_t count) {
-    if (dst)
-        HIPC(hipMemcpy2DAsync(dst, sizeof(double) * ldo, src, sizeof(double) * src_ld,
-                              sizeof(double) * c->n, count, hipMemcpyDeviceToHost, c->stream));
 }
 
 }  // namespace
@@ -724,26 +639,18 @@ int apm_set_ep(apm_ctx* ctx, double damping, double diff_tol, int64_t max_sweeps
 int apm_ep_eval(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, double* logz,
                 double* mu, double* var, double* tau, double* nu, int64_t ldo, int* status,
                 int64_t* n_sweeps) {
-    if (!c) return fail(nullptr, APM_E_INVALID, "apm_ep_eval: null context");
-    if (c->lik != APM_LIK_PROBIT)
-        return fail(c, APM_E_INVALID, "apm_ep_eval: probit only (the logit's tilted moments need "
-                                      "quadrature)");
-    if (c->kind == APM_KERNEL_PRECOMPUTED)
-        return fail(c, APM_E_INVALID, "apm_ep_eval: needs an ISO or ARD context (apm_ep takes a "
-                                      "K of the caller's)");
-    if (count <= 0 || count > c->max_batch)
-        return fail(c, APM_E_INVALID, "apm_ep_eval: count outside [1, max_batch]");
-    if (!thetas || !status || ldt < c->P || ((mu || var || tau || nu) && ldo < c->n))
-        return fail(c, APM_E_INVALID, "apm_ep_eval: bad arguments");
-    const SkewScope skew(c);
-    try {
-        HIPC(hipSetDevice(c->device));
-        std::vector<int> st_h;
-        ep_gram_fit(c, count, thetas, ldt, st_h);
-        std::vector<int> it_h((size_t)count);
+    ThetaArgs a;
+    a.probit_only = a.batch = true;
+    a.device_why = "needs an ISO or ARD context (apm_ep takes a K of the caller's)";
+    a.count = count;
+    const int rc = check_theta_call(c, "apm_ep_eval", a, [&] {
+        return !thetas || !status || ldt < c->P || ((mu || var || tau || nu) && ldo < c->n);
+    });
+    if (rc != APM_SUCCESS) return rc;
+    return ctx_call(c, SKEW, [&] {
+        EpFit fit;
+        ep_gram_fit(c, count, thetas, ldt, fit);
         std::vector<double> lz((size_t)count);
-        HIPC(hipMemcpyAsync(it_h.data(), c->n_iter, sizeof(int) * count, hipMemcpyDeviceToHost,
-                            c->stream));
         HIPC(hipMemcpyAsync(lz.data(), c->ep.logz, sizeof(double) * count, hipMemcpyDeviceToHost,
                             c->stream));
         ep_fetch(c, mu, ldo, c->v.f, c->v.vstride, count);
@@ -751,108 +658,62 @@ int apm_ep_eval(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, do
         ep_fetch(c, tau, ldo, c->ep.tau, c->ep.stride, count);
         ep_fetch(c, nu, ldo, c->ep.nu, c->ep.stride, count);
         sync(c);
-        const double nan = std::numeric_limits<double>::quiet_NaN();
-        for (int64_t b = 0; b < count; ++b) {
-            status[b] = st_h[b];
-            if (n_sweeps) n_sweeps[b] = it_h[b];
-            const bool good = st_h[b] == APM_STATUS_OK;
-            if (logz) logz[b] = good ? lz[b] : nan;
-            if (!good)
-                for (double* o : {mu, var, tau, nu})
-                    if (o) std::fill(o + b * ldo, o + b * ldo + c->n, nan);
-        }
-    } catch (const HipError& e) {
-        return fail(c, APM_E_HIP, e.msg);
-    }
-    return APM_SUCCESS;
+        ep_report(fit, count, status, n_sweeps);
+        rows_out(logz, 1, lz, count, 1);
+        finish_rows(count, status,
+                    {{mu, ldo, c->n}, {var, ldo, c->n}, {tau, ldo, c->n}, {nu, ldo, c->n}}, {logz});
+    });
 }
 
 int apm_ep_predict(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, const double* Xs,
                    int64_t m, int64_t ldxs, double* mean, double* var, double* prob, int64_t ldo,
                    int* status, int64_t* n_sweeps) {
-    if (!c) return fail(nullptr, APM_E_INVALID, "apm_ep_predict: null context");
-    if (c->lik != APM_LIK_PROBIT)
-        return fail(c, APM_E_INVALID, "apm_ep_predict: probit only (the logit's tilted moments "
-                                      "need quadrature)");
-    if (c->kind == APM_KERNEL_PRECOMPUTED)
-        return fail(c, APM_E_INVALID, "apm_ep_predict: needs an ISO or ARD context (the cross-"
-                                      "covariance is built on the device)");
-    if (m <= 0) return fail(c, APM_E_INVALID, "apm_ep_predict: m <= 0");
-    if (count <= 0 || count > c->max_batch)
-        return fail(c, APM_E_INVALID, "apm_ep_predict: count outside [1, max_batch]");
-    if (ldo < m) return fail(c, APM_E_INVALID, "apm_ep_predict: ldo < m");
-    if (!thetas || !Xs || !status || ldt < c->P || ldxs < c->d)
-        return fail(c, APM_E_INVALID, "apm_ep_predict: bad arguments");
-    const SkewScope skew(c);
-    try {
-        HIPC(hipSetDevice(c->device));
-        std::vector<int> st_h;
-        const int ok = ep_gram_fit(c, count, thetas, ldt, st_h);
-        std::vector<int> it_h((size_t)count);
-        HIPC(hipMemcpyAsync(it_h.data(), c->n_iter, sizeof(int) * count, hipMemcpyDeviceToHost,
-                            c->stream));
+    ThetaArgs a;
+    a.probit_only = a.batch = a.rows = true;
+    a.device_why = "needs an ISO or ARD context (the cross-covariance is built on the device)";
+    a.count = count, a.m = m, a.ldo = ldo;
+    const int rc = check_theta_call(c, "apm_ep_predict", a, [&] {
+        return !thetas || !Xs || !status || ldt < c->P || ldxs < c->d;
+    });
+    if (rc != APM_SUCCESS) return rc;
+    return ctx_call(c, SKEW, [&] {
+        EpFit fit;
+        ep_gram_fit(c, count, thetas, ldt, fit);
         sync(c);
-        if (ok) {  // predict_block reads S^1/2 (v.Ws), a and the factor of each chain's last sweep
-            predict_all(c, count, thetas, ldt, Xs, m, ldxs, mean, var, prob, ldo);
-        }
-        const double nan = std::numeric_limits<double>::quiet_NaN();
-        for (int64_t b = 0; b < count; ++b) {
-            status[b] = st_h[b];
-            if (n_sweeps) n_sweeps[b] = it_h[b];
-            if (st_h[b] != APM_STATUS_OK)
-                for (double* o : {mean, var, prob})
-                    if (o) std::fill(o + b * ldo, o + b * ldo + m, nan);
-        }
-    } catch (const HipError& e) {
-        return fail(c, APM_E_HIP, e.msg);
-    }
-    return APM_SUCCESS;
+        ep_report(fit, count, status, n_sweeps);
+        // predict_block reads S^1/2 (v.Ws), a and the factor of each chain's last sweep
+        if (fit.ok) predict_all(c, count, thetas, ldt, Xs, m, ldxs, mean, var, prob, ldo);
+        finish_rows(count, status, {{mean, ldo, m}, {var, ldo, m}, {prob, ldo, m}});
+    });
 }
 
 int apm_ep_grad(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, double* logz,
                 double* grad, int64_t ldg, int* status, int64_t* n_sweeps) {
-    if (!c) return fail(nullptr, APM_E_INVALID, "apm_ep_grad: null context");
-    if (c->lik != APM_LIK_PROBIT)
-        return fail(c, APM_E_INVALID, "apm_ep_grad: probit only (the logit's tilted moments need "
-                                      "quadrature)");
-    if (c->kind == APM_KERNEL_PRECOMPUTED)
-        return fail(c, APM_E_INVALID, "apm_ep_grad: needs an ISO or ARD context (dK/dtheta is "
-                                      "built on the device)");
-    if (count <= 0 || count > c->max_batch)
-        return fail(c, APM_E_INVALID, "apm_ep_grad: count outside [1, max_batch]");
-    if (ldt < c->P) return fail(c, APM_E_INVALID, "apm_ep_grad: ldt < theta length");
-    if (ldg < c->P) return fail(c, APM_E_INVALID, "apm_ep_grad: ldg < theta length");
-    if (!thetas || !grad || !status) return fail(c, APM_E_INVALID, "apm_ep_grad: bad arguments");
-    const SkewScope skew(c);
-    try {
-        HIPC(hipSetDevice(c->device));
-        std::vector<int> st_h;
-        const int ok = ep_gram_fit(c, count, thetas, ldt, st_h);
-        std::vector<int> it_h((size_t)count);
+    ThetaArgs a;
+    a.probit_only = a.batch = a.lds = true;
+    a.device_why = "needs an ISO or ARD context (dK/dtheta is built on the device)";
+    a.count = count, a.ldt = ldt, a.ldg = ldg;
+    const int rc =
+        check_theta_call(c, "apm_ep_grad", a, [&] { return !thetas || !grad || !status; });
+    if (rc != APM_SUCCESS) return rc;
+    return ctx_call(c, SKEW, [&] {
+        EpFit fit;
+        ep_gram_fit(c, count, thetas, ldt, fit);
         std::vector<double> lz((size_t)count), gh((size_t)count * c->P);
-        HIPC(hipMemcpyAsync(it_h.data(), c->n_iter, sizeof(int) * count, hipMemcpyDeviceToHost,
-                            c->stream));
         HIPC(hipMemcpyAsync(lz.data(), c->ep.logz, sizeof(double) * count, hipMemcpyDeviceToHost,
                             c->stream));
-        if (ok) {  // S^1/2 (v.Ws), a and the factor of each chain's last sweep are in place
+        if (fit.ok) {  // S^1/2 (v.Ws), a and the factor of each chain's last sweep are in place
             grad_buffers(c);
             ep_grad_block(c, (int)count);
             HIPC(hipMemcpyAsync(gh.data(), c->gout, sizeof(double) * count * c->P,
                                 hipMemcpyDeviceToHost, c->stream));
         }
         sync(c);
-        const double nan = std::numeric_limits<double>::quiet_NaN();
-        for (int64_t b = 0; b < count; ++b) {
-            status[b] = st_h[b];
-            if (n_sweeps) n_sweeps[b] = it_h[b];
-            const bool good = st_h[b] == APM_STATUS_OK;
-            if (logz) logz[b] = good ? lz[b] : nan;
-            for (int p = 0; p < c->P; ++p) grad[b * ldg + p] = good ? gh[b * c->P + p] : nan;
-        }
-    } catch (const HipError& e) {
-        return fail(c, APM_E_HIP, e.msg);
-    }
-    return APM_SUCCESS;
+        ep_report(fit, count, status, n_sweeps);
+        rows_out(logz, 1, lz, count, 1);
+        rows_out(grad, ldg, gh, count, c->P);
+        finish_rows(count, status, {{grad, ldg, c->P}}, {logz});
+    });
 }
 
 int apm_ep(int device, const double* K, int64_t n, int64_t ldk, const double* y, int calc_cov,
@@ -862,10 +723,8 @@ int apm_ep(int device, const double* K, int64_t n, int64_t ldk, const double* y,
     if (!K || !y || n <= 0 || ldk < n || !status || !ep_settings_ok(damping, diff_tol, max_sweeps) ||
         (calc_cov && (!C_out || ldc < n)))
         return fail(nullptr, APM_E_INVALID, "apm_ep: bad arguments");
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto key = std::make_tuple(device, n, (int64_t)0, (int)APM_KERNEL_PRECOMPUTED);
-    apm_ctx*& c = g_cache[key];  // (apm_laplace's cached context of the shape)
-    try {
+    // (apm_laplace's cached context of the shape)
+    return cached_call(device, n, 0, APM_KERNEL_PRECOMPUTED, [&](apm_ctx*& c) {
         standalone_ctx(c, device, n, y);
         c->ep_damping = damping;
         c->ep_tol = diff_tol;
@@ -873,20 +732,13 @@ int apm_ep(int device, const double* K, int64_t n, int64_t ldk, const double* y,
         c->lik = APM_LIK_PROBIT;  // (augmented() and the shared kernels read it)
         std::vector<double> Kp;  // (alive until the syncs below)
         upload_padded_K(c, K, ldk, Kp);
-        std::vector<int> st;
-        ep_fit(c, 1, st);
-        int it = 0;
-        HIPC(hipMemcpyAsync(&it, c->n_iter, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        EpFit fit;
+        ep_fit_counted(c, 1, fit);
         sync(c);
-        *status = st[0];
-        if (n_sweeps_out) *n_sweeps_out = it;
-        const double nan = std::numeric_limits<double>::quiet_NaN();
-        if (st[0] != APM_STATUS_OK) {
-            if (logz_out) *logz_out = nan;
-            for (double* o : {mu_out, var_out, tau_out, nu_out})
-                if (o) std::fill(o, o + n, nan);
-            return APM_SUCCESS;
-        }
+        ep_report(fit, 1, status, n_sweeps_out);
+        finish_rows(1, status, {{mu_out, n, n}, {var_out, n, n}, {tau_out, n, n}, {nu_out, n, n}},
+                    {logz_out});
+        if (*status != APM_STATUS_OK) return;
         if (logz_out)
             HIPC(hipMemcpyAsync(logz_out, c->ep.logz, sizeof(double), hipMemcpyDeviceToHost,
                                 c->stream));
@@ -894,18 +746,9 @@ int apm_ep(int device, const double* K, int64_t n, int64_t ldk, const double* y,
         ep_fetch(c, var_out, n, c->ep.var, c->ep.stride, 1);
         ep_fetch(c, tau_out, n, c->ep.tau, c->ep.stride, 1);
         ep_fetch(c, nu_out, n, c->ep.nu, c->ep.stride, 1);
-        if (calc_cov) {
-            covariance_out(c, C_out, ldc);
-        }
+        if (calc_cov) covariance_out(c, C_out, ldc);
         sync(c);
-    } catch (const HipError& e) {
-        if (c) {
-            free_ctx(c);
-            c = nullptr;
-        }
-        return fail(nullptr, APM_E_HIP, e.msg);
-    }
-    return APM_SUCCESS;
+    });
 }
 
 int apm_selftest_tile(int device, const double* A, const double* B, double* C) {
@@ -948,18 +791,14 @@ int apm_selftest_philox(int device, int64_t n, const uint32_t* in, uint32_t* out
 int apm_guard_read(apm_ctx* c, int64_t count, double* r) {
     if (!c || !r || count <= 0 || count > c->max_batch)
         return fail(c, APM_E_INVALID, "apm_guard_read: bad arguments");
-    try {
-        HIPC(hipSetDevice(c->device));
+    return ctx_call(c, NO_SKEW, [&] {
         std::vector<double> h((size_t)4 * c->max_batch);
         HIPC(hipMemcpyAsync(h.data(), c->guard + 2 * c->max_batch, sizeof(double) * h.size(),
                             hipMemcpyDeviceToHost, c->stream));
         sync(c);
         for (int64_t b = 0; b < count; ++b)
             for (int k = 0; k < 4; ++k) r[4 * b + k] = h[(size_t)k * c->max_batch + b];
-    } catch (const HipError& e) {
-        return fail(c, APM_E_HIP, e.msg);
-    }
-    return APM_SUCCESS;
+    });
 }
 
 int apm_prof_enable(apm_ctx* c, int on) {
@@ -970,21 +809,16 @@ int apm_prof_enable(apm_ctx* c, int on) {
 
 int apm_prof_marker(apm_ctx* c, int id) {
     if (!c || id < 0 || id > 3) return fail(c, APM_E_INVALID, "apm_prof_marker: bad arguments");
-    try {
-        HIPC(hipSetDevice(c->device));
+    return ctx_call(c, NO_SKEW, [&] {
         launch_marker(id, c->stream);
-    } catch (const HipError& e) {
-        return fail(c, APM_E_HIP, e.msg);
-    }
-    return APM_SUCCESS;
+    });
 }
 
 int apm_prof_read(apm_ctx* c, int kind, double* total_ms, int64_t* launches, double* work,
                   int reset) {
     if (!c || kind < 0 || kind >= APM_PROF_NKINDS)
         return fail(c, APM_E_INVALID, "apm_prof_read: bad arguments");
-    try {
-        HIPC(hipSetDevice(c->device));
+    return ctx_call(c, NO_SKEW, [&] {
         sync(c);
         if (kind == APM_PROF_DF_TIMEOUTS || kind == APM_PROF_TRSV_TIMEOUTS) {
             unsigned long long* d = spin_words(c) + (kind == APM_PROF_TRSV_TIMEOUTS ? 1 : 0);
@@ -994,14 +828,14 @@ int apm_prof_read(apm_ctx* c, int kind, double* total_ms, int64_t* launches, dou
             if (launches) *launches = (int64_t)h;
             if (work) *work = 0.0;
             if (reset) HIPC(hipMemset(d, 0, sizeof(h)));
-            return APM_SUCCESS;
+            return;
         }
         if (kind == APM_PROF_POST64_RERUNS) {
             if (total_ms) *total_ms = 0.0;
             if (launches) *launches = c->n_post64;
             if (work) *work = 0.0;
             if (reset) c->n_post64 = 0;
-            return APM_SUCCESS;
+            return;
         }
         if (kind == APM_PROF_ICM_CHECKS || kind == APM_PROF_GUARD) {
             int64_t& n = kind == APM_PROF_GUARD ? c->n_guard : c->n_icm_check;
@@ -1009,14 +843,14 @@ int apm_prof_read(apm_ctx* c, int kind, double* total_ms, int64_t* launches, dou
             if (launches) *launches = n;
             if (work) *work = 0.0;
             if (reset) n = 0;
-            return APM_SUCCESS;
+            return;
         }
         if (kind == APM_PROF_STATS) {
             if (total_ms) *total_ms = 0.0;
             if (launches) *launches = c->n_fp64_rerun;
             if (work) *work = (double)c->n_refine_steps;
             if (reset) c->n_fp64_rerun = c->n_refine_steps = 0;
-            return APM_SUCCESS;
+            return;
         }
         double ms = 0.0, wk = 0.0;
         int64_t cnt = 0;
@@ -1035,10 +869,7 @@ int apm_prof_read(apm_ctx* c, int kind, double* total_ms, int64_t* launches, dou
             c->recs.clear();
             c->evnext = 0;
         }
-    } catch (const HipError& e) {
-        return fail(c, APM_E_HIP, e.msg);
-    }
-    return APM_SUCCESS;
+    });
 }
 
 }  // extern "C"

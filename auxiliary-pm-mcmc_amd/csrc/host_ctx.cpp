@@ -302,6 +302,19 @@ void init_ctx(apm_ctx* c, int device, int kind, const double* X, int64_t n, int6
     HIPC(hipMemset(c->Up.base32, 0, sizeof(float) * n_ubufs * np * c->sp));
 }
 
+void standalone_ctx(apm_ctx*& c, int device, int64_t n, const double* y) {
+    if (!c) {
+        c = new apm_ctx();
+        init_ctx(c, device, APM_KERNEL_PRECOMPUTED, nullptr, n, 0, 0, y, 1e-8, 1, 1, 1, 1);
+    } else {
+        HIPC(hipSetDevice(device));
+        std::vector<double> yp((size_t)c->np, 0.0);
+        for (int64_t i = 0; i < n; ++i) yp[i] = y[i];
+        HIPC(hipMemcpyAsync(c->y, yp.data(), sizeof(double) * c->np, hipMemcpyHostToDevice,
+                            c->stream));
+    }
+}
+
 void free_ctx(apm_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);

@@ -76,4 +76,28 @@ int ep_fit(apm_ctx* c, int count, std::vector<int>& st_h) {
     return ok;
 }
 
+void ep_fit_counted(apm_ctx* c, int count, EpFit& f) {
+    f.ok = ep_fit(c, count, f.st);
+    f.sweeps.assign(count, 0);
+    HIPC(hipMemcpyAsync(f.sweeps.data(), c->n_iter, sizeof(int) * count, hipMemcpyDeviceToHost,
+                        c->stream));
+}
+
+void ep_gram_fit(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, EpFit& f) {
+    upload_thetas(c, count, thetas, ldt);
+    HIPC(hipMemsetD32Async(c->active, 1, count, c->stream));
+    HIPC(hipMemsetAsync(c->status, 0, sizeof(int) * count, c->stream));
+    c->k_full = false;
+    launch_gram(c->K, c->X, c->d, c->n, c->d, c->theta, c->P, c->kind, c->eps, c->np, live_of(c),
+                (int)count, c->stream, /*both=*/false);
+    ep_fit_counted(c, (int)count, f);
+}
+
+void ep_fetch(apm_ctx* c, double* dst, int64_t ldo, const double* src, int64_t src_ld,
+              int64_t count) {
+    if (dst)
+        HIPC(hipMemcpy2DAsync(dst, sizeof(double) * ldo, src, sizeof(double) * src_ld,
+                              sizeof(double) * c->n, count, hipMemcpyDeviceToHost, c->stream));
+}
+
 }  // namespace apm_host

@@ -42,7 +42,6 @@ void is_predict_buffers(apm_ctx* c) {
 void is_predict_tail(apm_ctx* c, int count, const double* thetas, int64_t ldt, int* st_h,
                      const double* Xs, int64_t m, int64_t ldxs, double* prob, double* mean,
                      double* var, int64_t ldo, double* ess) {
-    predict_buffers(c);
     is_predict_buffers(c);
     const Live lv = live_of(c);
     hipStream_t s = c->stream;
@@ -53,9 +52,7 @@ void is_predict_tail(apm_ctx* c, int count, const double* thetas, int64_t ldt, i
     c->live_n = 0;
     for (int b = 0; b < count; ++b) c->live_n += st_h[b] == APM_STATUS_OK;
 
-    std::vector<double> xs, sig((size_t)count);  // (alive until the blocks' syncs)
-    for (int b = 0; b < count; ++b) sig[b] = std::exp(thetas[b * ldt]);
-    HIPC(hipMemcpyAsync(c->psig, sig.data(), sizeof(double) * count, hipMemcpyHostToDevice, s));
+    TestInputs in(c, count, thetas, ldt, Xs, m, ldxs);  // (alive until the blocks' syncs)
 
     launch_is_weights(c->partial, c->pstride, nb, c->S, c->sp, c->Sl.cst, c->d_slots, c->is_w,
                       c->is_ess, lv, count, s);
@@ -90,12 +87,7 @@ void is_predict_tail(apm_ctx* c, int count, const double* thetas, int64_t ldt, i
     so.ex = &ex2;
 
     for (int64_t r0 = 0; r0 < m; r0 += np) {
-        const int ms = (int)std::min<int64_t>(np, m - r0), mb = (ms + 63) / 64;
-        xs.resize((size_t)ms * c->d);
-        for (int i = 0; i < ms; ++i)
-            for (int k = 0; k < c->d; ++k) xs[(size_t)i * c->d + k] = Xs[(r0 + i) * ldxs + k];
-        HIPC(hipMemcpyAsync(c->pxs, xs.data(), sizeof(double) * ms * c->d, hipMemcpyHostToDevice,
-                            s));
+        const int ms = in.upload(r0), mb = (ms + 63) / 64;
         launch_gram_cross(c->A, np, c->pxs, ms, mb, c->X, c->d, c->n, c->d, nb, c->theta, c->P,
                           c->psig, c->kind, c->is_ones, c->v.a, vs, c->ppart, (int64_t)nb * np, lv,
                           0, count, s);
@@ -107,16 +99,8 @@ void is_predict_tail(apm_ctx* c, int count, const double* thetas, int64_t ldt, i
                             c->is_c, np, c->is_part, np, lv, count, s);
         launch_is_finish(c->is_part, np, nst, ms, c->is_vstar, c->pmean, c->pvar, c->pprob, np, lv,
                          count, s);
-        const std::pair<double*, const double*> outs[3] = {
-            {mean, c->pmean}, {var, c->pvar}, {prob, c->pprob}};
-        for (int b = 0; b < count; ++b) {
-            if (st_h[b] != APM_STATUS_OK) continue;  // (its device rows were never written)
-            for (const auto& o : outs)
-                if (o.first)
-                    HIPC(hipMemcpyAsync(o.first + b * ldo + r0, o.second + (int64_t)b * np,
-                                        sizeof(double) * ms, hipMemcpyDeviceToHost, s));
-        }
-        sync(c);  // (xs is reused by the next block)
+        in.rows_back(r0, ms, st_h, mean, var, prob, ldo);
+        sync(c);  // (the staged block is reused by the next one)
     }
     std::vector<int> st2((size_t)count);
     std::vector<double> ess_h((size_t)count);

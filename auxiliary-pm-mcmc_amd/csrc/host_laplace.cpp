@@ -2,6 +2,8 @@
 // predictive distribution at test inputs and the gradient of the log marginal likelihood, each
 // a pass of chol_solve_rows over free rows of the work matrix; and the gradient of log Z_EP on an
 // EP fit's last factor, which is the Laplace gradient's second pass.
+#include <cmath>
+
 #include "apm_host.h"
 
 namespace apm_host {
@@ -14,6 +16,47 @@ void augmented(apm_ctx* c, int count) {
     launch_form_aug(c->K, c->A, c->v, c->np, lv, count, c->stream);
     const int nb = c->nb;
     chol_solve_rows(c, c->A, nb, /*row_start=*/nb, /*R=*/2 * nb + 1, /*Cb=*/2 * nb, count);
+}
+
+void covariance_out(apm_ctx* c, double* C_out, int64_t ldc) {
+    const int np = c->np;
+    augmented(c, 1);
+    std::vector<double> Cb((size_t)np * np);
+    HIPC(hipMemcpy2DAsync(Cb.data(), sizeof(double) * np, c->A.base + (int64_t)np * c->A.ld + np,
+                          sizeof(double) * c->A.ld, sizeof(double) * np, np,
+                          hipMemcpyDeviceToHost, c->stream));
+    sync(c);
+    for (int64_t i = 0; i < c->n; ++i)
+        for (int64_t j = 0; j <= i; ++j) {
+            C_out[i * ldc + j] = Cb[(size_t)i * np + j];
+            C_out[j * ldc + i] = Cb[(size_t)i * np + j];
+        }
+}
+
+void laplace_on_K(apm_ctx* c, const double* K, int64_t ldk, double* f_out, double* C_out,
+                  int64_t ldc, double* lml_out, int64_t* n_iter_out, int* status) {
+    std::vector<double> Kp;  // (alive until the syncs below)
+    upload_padded_K(c, K, ldk, Kp);
+    HIPC(hipMemsetD32Async(c->active, 1, 1, c->stream));
+    HIPC(hipMemsetAsync(c->status, 0, sizeof(int), c->stream));
+    HIPC(hipMemsetAsync(c->n_iter, 0, sizeof(int), c->stream));
+    std::vector<int> st(1, 0);
+    c->live_n = 1;
+    newton(c, 1, st, false, 1);
+    int it = 0;
+    HIPC(hipMemcpyAsync(&it, c->n_iter, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    sync(c);
+    *status = st[0];
+    if (n_iter_out) *n_iter_out = it;
+    if (st[0] != APM_STATUS_OK) return;
+    HIPC(hipMemcpyAsync(f_out, c->v.f, sizeof(double) * c->n, hipMemcpyDeviceToHost, c->stream));
+    if (lml_out) {
+        launch_laplace_lml(c->lik, c->v, c->y, c->n, c->ldet, c->lstride, c->nb, c->out,
+                           live_of(c), 1, c->stream);
+        HIPC(hipMemcpyAsync(lml_out, c->out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (C_out) covariance_out(c, C_out, ldc);
+    sync(c);
 }
 
 int laplace_then_live(apm_ctx* c, int count, double* lml, int* status, int64_t* n_iter) {
@@ -31,10 +74,11 @@ int laplace_then_live(apm_ctx* c, int count, double* lml, int* status, int64_t* 
 }
 
 // Laplace predictive (predict.hip) of one block of ms <= np test inputs (packed
-// ms x d at xs) for the chains left live by an fp64 Laplace theta-call: W^1/2 . k* into the free
-// rows [np, np + 64 mb) of A and mu*'s partials, the panel solves and outer updates of those
-// rows against the last Newton factor (as augmented(), without the bottom-right SYRK), the row
-// reduction; outputs in pmean / pvar / pprob (row stride np). predict_buffers() first.
+// ms x d in pxs: TestInputs::upload) for the chains left live by an fp64 Laplace theta-call:
+// W^1/2 . k* into the free rows [np, np + 64 mb) of A and mu*'s partials, the panel solves and
+// outer updates of those rows against the last Newton factor (as augmented(), without the
+// bottom-right SYRK), the row reduction; outputs in pmean / pvar / pprob (row stride np).
+// predict_buffers() first.
 void predict_buffers(apm_ctx* c) {
     if (c->pxs) return;
     const int64_t np = c->np, B = c->max_batch;
@@ -46,17 +90,65 @@ void predict_buffers(apm_ctx* c) {
     c->psig = c->pprob + B * np;
 }
 
-void predict_block(apm_ctx* c, int count, const double* xs, int ms) {
+void predict_block(apm_ctx* c, int count, int ms) {
     const Live lv = live_of(c);
     const int nb = c->nb, mb = (ms + 63) / 64;
     const int64_t np = c->np;
-    HIPC(hipMemcpyAsync(c->pxs, xs, sizeof(double) * ms * c->d, hipMemcpyHostToDevice, c->stream));
     launch_gram_cross(c->A, np, c->pxs, ms, mb, c->X, c->d, c->n, c->d, nb, c->theta, c->P,
                       c->psig, c->kind, c->v.Ws, c->v.a, c->v.vstride, c->ppart, nb * np, lv, 0,
                       count, c->stream);
     chol_solve_rows(c, c->A, nb, /*row_start=*/nb, /*R=*/nb + mb, /*Cb=*/nb, count);
     launch_predict_reduce(c->lik, c->A, np, ms, mb, nb, c->psig, c->ppart, nb * np, c->pmean,
                           c->pvar, c->pprob, np, lv, count, c->stream);
+}
+
+TestInputs::TestInputs(apm_ctx* c_, int count_, const double* thetas, int64_t ldt,
+                       const double* Xs_, int64_t m_, int64_t ldxs_)
+    : c(c_), count(count_), Xs(Xs_), m(m_), ldxs(ldxs_), sig((size_t)count_) {
+    predict_buffers(c);
+    for (int b = 0; b < count; ++b) sig[b] = std::exp(thetas[b * ldt]);
+    HIPC(hipMemcpyAsync(c->psig, sig.data(), sizeof(double) * count, hipMemcpyHostToDevice,
+                        c->stream));
+}
+
+int TestInputs::upload(int64_t r0) {
+    const int ms = (int)std::min<int64_t>(c->np, m - r0);
+    xs.resize((size_t)ms * c->d);
+    for (int i = 0; i < ms; ++i)
+        for (int k = 0; k < c->d; ++k) xs[(size_t)i * c->d + k] = Xs[(r0 + i) * ldxs + k];
+    HIPC(hipMemcpyAsync(c->pxs, xs.data(), sizeof(double) * ms * c->d, hipMemcpyHostToDevice,
+                        c->stream));
+    return ms;
+}
+
+void TestInputs::rows_back(int64_t r0, int ms, const int* only_ok, double* mean, double* var,
+                           double* prob, int64_t ldo) {
+    const std::pair<double*, const double*> outs[3] = {
+        {mean, c->pmean}, {var, c->pvar}, {prob, c->pprob}};
+    for (const auto& o : outs) {
+        if (!o.first) continue;
+        if (!only_ok) {
+            HIPC(hipMemcpy2DAsync(o.first + r0, sizeof(double) * ldo, o.second,
+                                  sizeof(double) * c->np, sizeof(double) * ms, count,
+                                  hipMemcpyDeviceToHost, c->stream));
+            continue;
+        }
+        for (int b = 0; b < count; ++b)
+            if (only_ok[b] == APM_STATUS_OK)
+                HIPC(hipMemcpyAsync(o.first + b * ldo + r0, o.second + (int64_t)b * c->np,
+                                    sizeof(double) * ms, hipMemcpyDeviceToHost, c->stream));
+    }
+}
+
+void predict_all(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, const double* Xs,
+                 int64_t m, int64_t ldxs, double* mean, double* var, double* prob, int64_t ldo) {
+    TestInputs in(c, (int)count, thetas, ldt, Xs, m, ldxs);
+    for (int64_t r0 = 0; r0 < m; r0 += c->np) {
+        const int ms = in.upload(r0);
+        predict_block(c, (int)count, ms);
+        in.rows_back(r0, ms, nullptr, mean, var, prob, ldo);
+        sync(c);  // (the staged block is reused by the next one)
+    }
 }
 
 // Gradient of the Laplace LML w.r.t. theta (gradient.hip) for the chains left live

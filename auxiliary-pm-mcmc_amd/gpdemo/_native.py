@@ -153,6 +153,10 @@ def default_device():
     return int(os.environ.get('APM_DEVICE', os.environ.get('LOCAL_RANK', '0')))
 
 
+def _device(device):
+    return default_device() if device is None else device
+
+
 # ----------------------------------------------------------------------------- stand-alone calls
 
 
@@ -169,8 +173,8 @@ def gram(kind, K, X, theta, epsilon, device=None):
         raise IndexError('Out of bounds on buffer access (axis 0)')
     out = K if (isinstance(K, np.ndarray) and K.dtype == np.float64 and K.flags.c_contiguous
                 and K.flags.writeable) else np.empty((n, n))
-    _check(lib.apm_gram(default_device() if device is None else device, kind, _ptr(X), n, d, d,
-                        _ptr(theta), theta.shape[0], float(epsilon), out.ctypes.data, n))
+    _check(lib.apm_gram(_device(device), kind, _ptr(X), n, d, d, _ptr(theta), theta.shape[0],
+                        float(epsilon), out.ctypes.data, n))
     if out is not K:
         K[...] = out
     return None
@@ -188,9 +192,8 @@ def gram_cross(kind, X_test, X, theta, device=None):
     if theta.shape[0] < (2 if kind in _ISO_KINDS else d + 1):
         raise IndexError('Out of bounds on buffer access (axis 0)')
     Ks = np.empty((Xs.shape[0], n))
-    _check(lib.apm_gram_cross(default_device() if device is None else device, kind, _ptr(Xs),
-                              Xs.shape[0], _ptr(X), n, d, d, _ptr(theta), theta.shape[0],
-                              _ptr(Ks), n))
+    _check(lib.apm_gram_cross(_device(device), kind, _ptr(Xs), Xs.shape[0], _ptr(X), n, d, d,
+                              _ptr(theta), theta.shape[0], _ptr(Ks), n))
     return Ks
 
 
@@ -205,7 +208,7 @@ def laplace(K, y, calc_cov, calc_lml, diff_f_tol, max_iters, device=None, likeli
     lml = np.zeros(1)
     nit = np.zeros(1, dtype=np.int64)
     st = np.zeros(1, dtype=np.int32)
-    dev = default_device() if device is None else device
+    dev = _device(device)
     tail = (_ptr(K), n, n, _ptr(y), int(bool(calc_cov)), int(bool(calc_lml)), float(diff_f_tol),
             int(max_iters), _ptr(f), _ptr(C), n, _ptr(lml), _ptr(nit), _ptr(st))
     if lik == LIK_PROBIT:  # (the entry point the reference's function maps onto)
@@ -227,7 +230,7 @@ def ep(K, y, calc_cov, damping, diff_tol, max_sweeps, device=None):
     logz = np.zeros(1)
     nsw = np.zeros(1, dtype=np.int64)
     st = np.zeros(1, dtype=np.int32)
-    _check(lib.apm_ep(default_device() if device is None else device, _ptr(K), n, n, _ptr(y),
+    _check(lib.apm_ep(_device(device), _ptr(K), n, n, _ptr(y),
                       int(bool(calc_cov)), float(damping), float(diff_tol), int(max_sweeps),
                       _ptr(mu), _ptr(var), _ptr(tau), _ptr(nu), _ptr(C), n, _ptr(logz), _ptr(nsw),
                       _ptr(st)))
@@ -238,8 +241,7 @@ def selftest_tile(A, B, C, device=None):
     lib = load_library()
     A, B = _f64(A), _f64(B)
     C = _f64(C).copy()
-    _check(lib.apm_selftest_tile(default_device() if device is None else device, _ptr(A), _ptr(B),
-                                 _ptr(C)))
+    _check(lib.apm_selftest_tile(_device(device), _ptr(A), _ptr(B), _ptr(C)))
     return C
 
 
@@ -248,8 +250,7 @@ def selftest_philox(blocks, device=None):
     lib = load_library()
     inp = np.ascontiguousarray(blocks, dtype=np.uint32).reshape(-1, 6)
     out = np.empty((inp.shape[0], 4), dtype=np.uint32)
-    _check(lib.apm_selftest_philox(default_device() if device is None else device, inp.shape[0],
-                                   _ptr(inp), _ptr(out)))
+    _check(lib.apm_selftest_philox(_device(device), inp.shape[0], _ptr(inp), _ptr(out)))
     return out
 
 
@@ -311,7 +312,7 @@ class Context(object):
         lik = likelihood_code(likelihood)
         lib = load_library()
         self.lib = lib
-        self.device = default_device() if device is None else device
+        self.device = _device(device)
         y = _f64(y)
         self.n = y.shape[0]
         if kernel_kind == KERNEL_PRECOMPUTED:
@@ -383,11 +384,8 @@ class Context(object):
 
     # --- estimator calls
     def theta_eval(self, est, thetas, ubufs=None, slots=None):
-        th = np.atleast_2d(_f64(thetas))
+        th = self._thetas(thetas, self.batch_hist['theta'])
         count = th.shape[0]
-        self.batch_hist['theta'][count] += 1
-        if th.shape[1] < self.theta_len:
-            raise IndexError('Out of bounds on buffer access (axis 0)')
         out = np.full(count, np.nan)
         st = np.zeros(count, dtype=np.int32)
         nops = np.zeros(count, dtype=np.int64)
@@ -406,27 +404,52 @@ class Context(object):
                                          _ptr(out), _ptr(st), _ptr(nops)), self._h)
         return out, st, nops
 
+    def _thetas(self, thetas, hist=None):
+        th = np.atleast_2d(_f64(thetas))
+        if hist is not None:  # (a call is counted before its thetas are checked)
+            hist[th.shape[0]] += 1
+        if th.shape[1] < self.theta_len:
+            # kernels.pyx indexes theta[k+1] / theta[1] with bounds checking -> IndexError
+            raise IndexError('Out of bounds on buffer access (axis 0)')
+        return th
+
+    def _test_inputs(self, X_test):
+        Xs = _f64(X_test)
+        if Xs.ndim != 2 or Xs.shape[1] != self.d:
+            raise ValueError('X_test has shape {0}, expected (m, {1})'.format(Xs.shape, self.d))
+        return Xs
+
+    def _batched(self, fn, th, trailing, args):
+        """One library call per `max_batch` rows of th: NaN-filled float outputs (T,) + shape for
+        every shape in `trailing`, int32 statuses and int64 counts (T,). `args(thp, out, st, cnt)`
+        lists what follows (handle, count) in fn's argument order, given a batch's offset pointers
+        (out: one per float output). Returns ``(*outputs, status, counts)``."""
+        T = th.shape[0]
+        outs = [np.full((T,) + tuple(shape), np.nan) for shape in trailing]
+        st = np.zeros(T, dtype=np.int32)
+        cnt = np.zeros(T, dtype=np.int64)
+        for t0 in range(0, T, self.max_batch):
+            _check(fn(self._h, min(self.max_batch, T - t0),
+                      *args(th[t0:].ctypes.data, [o[t0:].ctypes.data for o in outs],
+                            st[t0:].ctypes.data, cnt[t0:].ctypes.data)), self._h)
+        return tuple(outs) + (st, cnt)
+
+    def _predictive(self, fn, thetas, X_test):
+        th, Xs = self._thetas(thetas), self._test_inputs(X_test)
+        m = Xs.shape[0]
+        return self._batched(fn, th, [(m,)] * 3, lambda thp, o, st, cnt: (
+            thp, th.shape[1], _ptr(Xs), m, self.d, o[0], o[1], o[2], m, st, cnt))
+
+    def _gradient(self, fn, thetas):
+        th, P = self._thetas(thetas), self.theta_len
+        return self._batched(fn, th, [(), (P,)], lambda thp, o, st, cnt: (
+            thp, th.shape[1], o[0], o[1], P, st, cnt))
+
     def predict(self, thetas, X_test):
         """Laplace predictive at X_test (m, d) for every row of thetas, `max_batch` at a time:
         ``(mean, var, prob, status, n_iter)``, the first three (T, m) with NaN rows where
         status != 0 (include/apm.h apm_predict)."""
-        th = np.atleast_2d(_f64(thetas))
-        if th.shape[1] < self.theta_len:
-            raise IndexError('Out of bounds on buffer access (axis 0)')
-        Xs = _f64(X_test)
-        if Xs.ndim != 2 or Xs.shape[1] != self.d:
-            raise ValueError('X_test has shape {0}, expected (m, {1})'.format(Xs.shape, self.d))
-        T, m = th.shape[0], Xs.shape[0]
-        mean, var, prob = (np.full((T, m), np.nan) for _ in range(3))
-        st = np.zeros(T, dtype=np.int32)
-        nit = np.zeros(T, dtype=np.int64)
-        for t0 in range(0, T, self.max_batch):
-            cnt = min(self.max_batch, T - t0)
-            _check(self.lib.apm_predict(
-                self._h, cnt, th[t0:].ctypes.data, th.shape[1], _ptr(Xs), m, self.d,
-                mean[t0:].ctypes.data, var[t0:].ctypes.data, prob[t0:].ctypes.data, m,
-                st[t0:].ctypes.data, nit[t0:].ctypes.data), self._h)
-        return mean, var, prob, st, nit
+        return self._predictive(self.lib.apm_predict, thetas, X_test)
 
     def is_predict(self, est, thetas, ubufs, slots, X_test):
         """Importance-sampling predictive at X_test (m, d) for up to `max_batch` chains: the
@@ -435,14 +458,8 @@ class Context(object):
         of the chains' U buffers: ``(logf, prob, mean, var, ess, status, n_cubic_ops)``, prob /
         mean / var (count, m) and ess (count,) NaN where status != 0 (include/apm.h
         apm_is_predict)."""
-        th = np.atleast_2d(_f64(thetas))
-        count = th.shape[0]
-        if th.shape[1] < self.theta_len:
-            raise IndexError('Out of bounds on buffer access (axis 0)')
-        Xs = _f64(X_test)
-        if Xs.ndim != 2 or Xs.shape[1] != self.d:
-            raise ValueError('X_test has shape {0}, expected (m, {1})'.format(Xs.shape, self.d))
-        m = Xs.shape[0]
+        th, Xs = self._thetas(thetas), self._test_inputs(X_test)
+        count, m = th.shape[0], Xs.shape[0]
         ub = np.ascontiguousarray(ubufs, dtype=np.int64)
         sl = np.ascontiguousarray(slots, dtype=np.int64)
         if ub.shape != (count,) or sl.shape != (count,):
@@ -462,20 +479,7 @@ class Context(object):
         """Laplace log marginal likelihood and its gradient with respect to theta for every row
         of thetas, `max_batch` at a time: ``(lml (T,), grad (T, P), status, n_iter)`` with NaN
         where status != 0 (include/apm.h apm_laplace_grad)."""
-        th = np.atleast_2d(_f64(thetas))
-        if th.shape[1] < self.theta_len:
-            raise IndexError('Out of bounds on buffer access (axis 0)')
-        T, P = th.shape[0], self.theta_len
-        lml = np.full(T, np.nan)
-        grad = np.full((T, P), np.nan)
-        st = np.zeros(T, dtype=np.int32)
-        nit = np.zeros(T, dtype=np.int64)
-        for t0 in range(0, T, self.max_batch):
-            cnt = min(self.max_batch, T - t0)
-            _check(self.lib.apm_laplace_grad(
-                self._h, cnt, th[t0:].ctypes.data, th.shape[1], lml[t0:].ctypes.data,
-                grad[t0:].ctypes.data, P, st[t0:].ctypes.data, nit[t0:].ctypes.data), self._h)
-        return lml, grad, st, nit
+        return self._gradient(self.lib.apm_laplace_grad, thetas)
 
     def set_ep(self, damping=0.8, diff_tol=1e-8, max_sweeps=100):
         _check(self.lib.apm_set_ep(self._h, float(damping), float(diff_tol), int(max_sweeps)),
@@ -485,62 +489,21 @@ class Context(object):
         """Expectation-propagation fit for every row of thetas, `max_batch` at a time:
         ``(logz (T,), mu, var, tau, nu (each (T, n)), status, n_sweeps)`` with NaN where
         status != 0 (include/apm.h apm_ep_eval)."""
-        th = np.atleast_2d(_f64(thetas))
-        if th.shape[1] < self.theta_len:
-            raise IndexError('Out of bounds on buffer access (axis 0)')
-        T, n = th.shape[0], self.n
-        logz = np.full(T, np.nan)
-        mu, var, tau, nu = (np.full((T, n), np.nan) for _ in range(4))
-        st = np.zeros(T, dtype=np.int32)
-        nsw = np.zeros(T, dtype=np.int64)
-        for t0 in range(0, T, self.max_batch):
-            cnt = min(self.max_batch, T - t0)
-            _check(self.lib.apm_ep_eval(
-                self._h, cnt, th[t0:].ctypes.data, th.shape[1], logz[t0:].ctypes.data,
-                mu[t0:].ctypes.data, var[t0:].ctypes.data, tau[t0:].ctypes.data,
-                nu[t0:].ctypes.data, n, st[t0:].ctypes.data, nsw[t0:].ctypes.data), self._h)
-        return logz, mu, var, tau, nu, st, nsw
+        th, n = self._thetas(thetas), self.n
+        return self._batched(self.lib.apm_ep_eval, th, [()] + [(n,)] * 4,
+                             lambda thp, o, st, cnt: (thp, th.shape[1]) + tuple(o) + (n, st, cnt))
 
     def ep_predict(self, thetas, X_test):
         """EP predictive at X_test (m, d) for every row of thetas, `max_batch` at a time:
         ``(mean, var, prob, status, n_sweeps)``, the first three (T, m) with NaN rows where
         status != 0 (include/apm.h apm_ep_predict)."""
-        th = np.atleast_2d(_f64(thetas))
-        if th.shape[1] < self.theta_len:
-            raise IndexError('Out of bounds on buffer access (axis 0)')
-        Xs = _f64(X_test)
-        if Xs.ndim != 2 or Xs.shape[1] != self.d:
-            raise ValueError('X_test has shape {0}, expected (m, {1})'.format(Xs.shape, self.d))
-        T, m = th.shape[0], Xs.shape[0]
-        mean, var, prob = (np.full((T, m), np.nan) for _ in range(3))
-        st = np.zeros(T, dtype=np.int32)
-        nsw = np.zeros(T, dtype=np.int64)
-        for t0 in range(0, T, self.max_batch):
-            cnt = min(self.max_batch, T - t0)
-            _check(self.lib.apm_ep_predict(
-                self._h, cnt, th[t0:].ctypes.data, th.shape[1], _ptr(Xs), m, self.d,
-                mean[t0:].ctypes.data, var[t0:].ctypes.data, prob[t0:].ctypes.data, m,
-                st[t0:].ctypes.data, nsw[t0:].ctypes.data), self._h)
-        return mean, var, prob, st, nsw
+        return self._predictive(self.lib.apm_ep_predict, thetas, X_test)
 
     def ep_grad(self, thetas):
         """log Z_EP and its gradient with respect to theta for every row of thetas, `max_batch`
         at a time: ``(logz (T,), grad (T, P), status, n_sweeps)`` with NaN where status != 0
         (include/apm.h apm_ep_grad)."""
-        th = np.atleast_2d(_f64(thetas))
-        if th.shape[1] < self.theta_len:
-            raise IndexError('Out of bounds on buffer access (axis 0)')
-        T, P = th.shape[0], self.theta_len
-        logz = np.full(T, np.nan)
-        grad = np.full((T, P), np.nan)
-        st = np.zeros(T, dtype=np.int32)
-        nsw = np.zeros(T, dtype=np.int64)
-        for t0 in range(0, T, self.max_batch):
-            cnt = min(self.max_batch, T - t0)
-            _check(self.lib.apm_ep_grad(
-                self._h, cnt, th[t0:].ctypes.data, th.shape[1], logz[t0:].ctypes.data,
-                grad[t0:].ctypes.data, P, st[t0:].ctypes.data, nsw[t0:].ctypes.data), self._h)
-        return logz, grad, st, nsw
+        return self._gradient(self.lib.apm_ep_grad, thetas)
 
     def u_eval(self, slots, ubufs):
         sl = np.ascontiguousarray(slots, dtype=np.int64)

@@ -17,8 +17,10 @@ run each in a process of its own (the knobs are read when a context is created):
 
 The default setting of a shape runs every call (IS theta-call + u-call + slot read, PriorMC,
 Laplace, apm_theta_eval_K, apm_predict with one and three row tiles of test inputs,
-apm_laplace_grad, apm_laplace with its covariance); a knob setting repeats the IS call, which is
-what the knobs reach. After every call the launch counts of all APM_PROF_* kinds (profiling
+apm_laplace_grad, apm_ep_eval / apm_ep_predict / apm_ep_grad, the EST_IS_EP theta-call,
+apm_is_predict with both proposals and one and two blocks of test inputs, apm_u_eval_diag,
+apm_is_spread, apm_laplace and apm_ep with their covariances); a knob setting repeats the IS call,
+which is what the knobs reach. After every call the launch counts of all APM_PROF_* kinds (profiling
 level 2) are saved beside the arrays.
 
     python tools/ab_values.py --compare a.npz b.npz      (or two directories of npz files)
@@ -135,6 +137,38 @@ def run_small(case, outdir):
         for k, a in zip(('lml', 'grad', 'st', 'nit'), ctx.laplace_grad(th)):
             out['grad_' + k] = a
         launches(ctx, 'grad')
+        Xs = edge_cases.predict_inputs(c, 40, 1000.0)
+        for call, names, fn in (
+                ('ep', ('logz', 'mu', 'var', 'tau', 'nu', 'st', 'nsw'), lambda: ctx.ep(th)),
+                ('eppred', ('mean', 'var', 'prob', 'st', 'nsw'), lambda: ctx.ep_predict(th, Xs)),
+                ('epgrad', ('logz', 'grad', 'st', 'nsw'), lambda: ctx.ep_grad(th))):
+            for k, a in zip(names, fn()):
+                out['{0}_{1}'.format(call, k)] = a
+            launches(ctx, call)
+        ctx.close()
+        ctx = context()
+        v1, st, nops = ctx.theta_eval(_native.EST_IS_EP, th, idx, idx)
+        v2, st2 = ctx.u_eval(idx, idx)
+        out.update(isep_v1=v1, isep_st=st, isep_nops=nops, isep_v2=v2, isep_st2=st2)
+        slots(ctx, 'isep')
+        launches(ctx, 'isep')
+        # one block of test inputs and two (n1089: one, and two replicates, to stay short)
+        big = n > 1024
+        for est, nm in ((_native.EST_IS, 'ispred'), (_native.EST_IS_EP, 'iseppred')):
+            for m in (40,) if big else (40, ctx.padded_n + 1):
+                call = '{0}{1}'.format(nm, m)
+                res = ctx.is_predict(est, th, idx, idx, edge_cases.predict_inputs(c, m, 1000.0))
+                for k, a in zip(('logf', 'prob', 'mean', 'var', 'ess', 'st', 'nops'), res):
+                    out['{0}_{1}'.format(call, k)] = a
+                launches(ctx, call)
+        for k, a in zip(('logf', 'ess', 'wmax', 'st'), ctx.u_eval_diag(idx, idx, 4)):
+            out['diag_' + k] = a
+        launches(ctx, 'diag')
+        res = ctx.is_spread(idx, idx, np.full(B, 11, dtype=np.uint64),
+                            np.arange(B, dtype=np.uint64), 2 if big else 3, 8)
+        for k, a in zip(('logf', 'ess', 'wmax', 'st'), res):
+            out['spread_' + k] = a
+        launches(ctx, 'spread')
         ctx.close()
         # a host K: the device's own Gram at the first theta (compared as well)
         K = np.empty((n, n))
@@ -155,6 +189,9 @@ def run_small(case, outdir):
         f, C, lml, nit, st = _native.laplace(K, y, True, True, 1e-4, 1000)
         out.update(lapcov_f=f, lapcov_C=C, lapcov_lml=np.array(lml), lapcov_nit=np.array(nit),
                    lapcov_st=np.array(st))
+        for k, a in zip(('mu', 'var', 'tau', 'nu', 'C', 'logz', 'nsw', 'st'),
+                        _native.ep(K, y, True, 0.8, 1e-8, 100)):
+            out['epcov_' + k] = np.array(a)
     os.makedirs(outdir, exist_ok=True)
     np.savez(os.path.join(outdir, case.replace(':', '__').replace('=', '_') + '.npz'), **out)
     print('{0}: {1} arrays'.format(case, len(out)))
