@@ -142,6 +142,31 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// |row[0 .. ncols)|^2 on every lane of a wave, in one order for every kernel that takes it
+// (k_grad_rows, k_ep_sites, k_predict_reduce, k_is_rows): 16-byte pieces, lane l the pieces at
+// columns 2l, 2l + 128, .. in order (fma on x, then on y), then the wave's butterfly. piece(c, v)
+// sees every piece the lane loads (k_is_rows stores it reversed).
+template <class F>
+__device__ __forceinline__ double row_sqnorm_d2(const double* row, int ncols, int lane, F&& piece) {
+    double s = 0.0;
+    for (int c = 2 * lane; c < ncols; c += 128) {
+        const d2_t v = *reinterpret_cast<const d2_t*>(row + c);
+        s = fma(v.x, v.x, s);
+        s = fma(v.y, v.y, s);
+        piece(c, v);
+    }
+    return wave_sum_d(s);
+}
+__device__ __forceinline__ double row_sqnorm_d2(const double* row, int ncols, int lane) {
+    return row_sqnorm_d2(row, ncols, lane, [](int, d2_t) {});
+}
+// pb[0] + pb[stride] + .. + pb[(nb - 1) stride] in order: a row's mu* from the partials that
+// k_gram_cross leaves per tile column
+__device__ __forceinline__ double sum_tile_partials(const double* pb, int nb, int64_t stride) {
+    double s = 0.0;
+    for (int tj = 0; tj < nb; ++tj) s += pb[tj * stride];
+    return s;
+}
 __device__ __forceinline__ double wave_max_d(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));

@@ -6,6 +6,7 @@
 
 #include "apm_common.h"
 #include "tile_lists.h"  // the update lists the launchers below run over (plain C++)
+#include "tri_index.h"   // lower_tri_index (plain C++ as well)
 
 // A batched fp64 matrix: chain b's element (r, c) lives at base[b*cstride + r*ld + c].
 struct MatB {
@@ -26,6 +27,9 @@ struct Live {
     const int* active;
     int* status;
 };
+__device__ __forceinline__ bool live_chain(const Live& lv, int b) {
+    return lv.active[b] != 0 && lv.status[b] == 0;
+}
 
 // ---- chol.hip -------------------------------------------------------------------------------
 // Blocked right-looking Cholesky building blocks over TB x TB tiles (lower triangle).

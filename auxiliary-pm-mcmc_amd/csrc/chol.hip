@@ -11,10 +11,6 @@
 #include "apm_internal.h"
 #include "diag.h"
 #include "tile64.h"
-__device__ __forceinline__ bool chain_live(const Live& lv, int b) {
-    return lv.active[b] != 0 && lv.status[b] == 0;
-}
-
 // ------------------------------------------------------------------------------- diagonal tile
 // Stand-alone diag step (one wave per chain): tile (k, k) -> LDS, diag_compute + diag_store (diag.h). Used for
 // the first column of every factorisation; every later diagonal tile is factored inside the
@@ -24,7 +20,7 @@ __global__ __launch_bounds__(64) void k_chol_diag(Mat A, int k, TS* Dinv, int64_
                                                   double* ldet, int64_t lstride, Live live,
                                                   int fail_code) {
     const int b = blockIdx.x;
-    if (!chain_live(live, b)) return;
+    if (!live_chain(live, b)) return;
     __shared__ DiagSmemT<TS> S;  // fp32 tiles (Newton matrix): fp32 arithmetic
     const int lane = threadIdx.x;
     TS* At = A.base + b * A.cstride + (int64_t)(k * 64) * A.ld + k * 64;
@@ -69,7 +65,7 @@ __global__ __launch_bounds__(256) void k_chol_panel(MatB A, int k, int i0, int g
                                                     const double* Dinv, int64_t dstride,
                                                     Live live) {
     const int b = blockIdx.y;
-    if (!chain_live(live, b)) return;
+    if (!live_chain(live, b)) return;
     int i = i0 + blockIdx.x;
     if (i >= glo) i += ghi - glo;  // skip the row tiles [glo, ghi) (known-zero rows)
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wr = w >> 1, wc = w & 1;
@@ -147,7 +143,7 @@ __global__ __launch_bounds__(256, UPD_WPE) void k_chol_update(MatB A, int k0, in
         b = (int)(w / nt);
         t = (int)(w % nt) + (fd.enabled ? 1 : 0);
     }
-    if (!chain_live(live, b)) return;
+    if (!live_chain(live, b)) return;
     const unsigned ij = tiles[t];
     const int i = (int)(ij >> 16), j = (int)(ij & 0xffff);
     double* Ab = A.base + b * A.cstride;
@@ -393,7 +389,7 @@ __global__ __launch_bounds__(256, 2) void k_chol_update_t128(MatB A, int k0, int
         b = (int)(w / nt);
         t = (int)(w % nt) + (fd.enabled ? 1 : 0);
     }
-    if (!chain_live(live, b)) return;
+    if (!live_chain(live, b)) return;
     if (plus == 2)  // A_ij = I_ij + Y_i Y_j^T (the SYRK of the UL factorisation, postcov.hip)
         update_t128_body<false, true>(A, k0, kc, tiles[t], b, fused, live, fd, sm.g, sm.d, S);
     else if (plus)  // A_ij += ...
@@ -419,7 +415,7 @@ __global__ __launch_bounds__(256) void k_trsv_lt_step(MatB A, int J, int64_t rro
                                                       const double* Dinv, int64_t dstride,
                                                       double* z, int64_t zstride, Live live) {
     const int b = blockIdx.y;
-    if (!chain_live(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int I = blockIdx.x;
     const int tid = threadIdx.x, c = tid & 63, q = tid >> 6;
     __shared__ double rj[64];

@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256, BULK ? DF_BULK_WPE : DF_WPE) void k_chol_panel
         if (threadIdx.x == 0) live.status[b] = fd.fail_code;
         if (pub) publish(base + DF_FAILED);
     };
-    if (!live32(live, b)) {
+    if (!live_chain(live, b)) {
         if (pub) publish(base + DF_FAILED);
         return;
     }
@@ -404,7 +404,7 @@ __global__ __launch_bounds__(256) void k_zinv_level32(MatF A, int K, int m,
                                                       Planes16 zpl, Live live,
                                                       const int* __restrict__ h3ok) {
     const int b = blockIdx.x >> 2, w = blockIdx.x & 3;
-    if (!live32(live, b) || (h3ok && !h3ok[b])) return;
+    if (!live_chain(live, b) || (h3ok && !h3ok[b])) return;
     const int p = w / m, tb = w % m;
     const int r0 = 2 * m * p + m, c0 = 2 * m * p;
     __shared__ GemmSmem32 sm;
@@ -497,7 +497,7 @@ __global__ __launch_bounds__(512, 1) void k_panel_inv_gemm32(MatF A, int K, int 
     const long w = xcd_remap32((long)blockIdx.x, (long)npair * nchains);
     const int b = (int)(w / npair), i0 = Kend + 2 * (int)(w % npair);
     const bool two = i0 + 1 < nb;  // (an odd count leaves the last workgroup one row tile)
-    if (!live32(live, b) || (h3ok && !h3ok[b])) return;
+    if (!live_chain(live, b) || (h3ok && !h3ok[b])) return;
     float* Ab = A.base + b * A.cstride + (int64_t)(i0 * 64) * A.ld + K * 64;
     const int rt = wv >> 2, c0 = wv & 3, c1 = 7 - (wv & 3);
     f4_t acc0[4][4], acc1[4][4];

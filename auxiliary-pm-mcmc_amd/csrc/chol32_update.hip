@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void k_chol_update32(MatF A, int k0, int kc,
     } sm;
     int b, t;
     const bool fused = update_item32(fd, ntiles, nchains, b, t);
-    if (!live32(live, b)) return;
+    if (!live_chain(live, b)) return;
     const unsigned ij = tiles[t];
     const int i = (int)(ij >> 16), j = (int)(ij & 0xffff);
     float* Ab = A.base + b * A.cstride;
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void k_rhs_row_update32(MatF A, int k0, int kc
                                                           int ntiles, int nchains, Live live) {
     const long w = xcd_remap32((long)blockIdx.x, (long)ntiles * nchains);
     const int b = (int)(w / ntiles);
-    if (!live32(live, b)) return;
+    if (!live_chain(live, b)) return;
     const unsigned e = tiles[w % ntiles];
     rhs_row_update32(A.base + b * A.cstride, A.ld, (int)(e >> 18), (int)((e >> 4) & 0x3fff),
                      e & 4u, e & 8u, k0, kc, threadIdx.x);
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(256, 2) void k_chol_update32_t128(MatF A, int k0, i
     } sm;
     int b, t;
     const bool fused = update_item32(fd, ntiles, nchains, b, t);
-    if (!live32(live, b)) return;
+    if (!live_chain(live, b)) return;
     const unsigned e = tiles[t];
     const int ti = (int)(e >> 18), tj = (int)((e >> 4) & 0x3fff);
     const bool rv0 = e & 1u, rv1 = e & 2u, cv0 = e & 4u, cv1 = e & 8u;
@@ -480,7 +480,7 @@ __global__ __launch_bounds__(512, 1) void k_chol_update32_q256(MatF A, int k0, i
     __shared__ GemmSmemQ sm;
     const long w = xcd_remap32((long)blockIdx.x, (long)nq * nchains);
     const int b = (int)(w / nq), t = (int)(w % nq);
-    if (!live32(live, b) || (h3ok && !h3ok[b])) return;
+    if (!live_chain(live, b) || (h3ok && !h3ok[b])) return;
     const unsigned e = quads[t];
     const int I = (int)(e >> 20), J = (int)((e >> 8) & 0xfff), rm = (e >> 4) & 15, cm = e & 15;
     auto rt = [&](int a) { return (rm >> a) & 1 ? I + a : I; };

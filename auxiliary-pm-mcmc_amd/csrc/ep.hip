@@ -13,14 +13,10 @@
 // moments need quadrature.
 #include "apm_internal.h"
 
-__device__ __forceinline__ bool live_e(const Live& lv, int b) {
-    return lv.active[b] != 0 && lv.status[b] == 0;
-}
-
 // S^1/2 and nu~ into the Newton vectors (Ws, W, b); rows >= n have tau~ = nu~ = 0 throughout
 __global__ __launch_bounds__(256) void k_ep_prep(EpVecs e, NewtonVecs v, int np, Live live) {
     const int b = blockIdx.y;
-    if (!live_e(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= np) return;
     const double t = e.tau[b * e.stride + i];
@@ -35,15 +31,14 @@ void launch_ep_prep(EpVecs e, NewtonVecs v, int np, Live live, int nchains, hipS
 }
 
 // One wave per (chain, training row r): the squared norm of row np + r of the work matrix over
-// its first 64 nb columns (16-byte loads, consecutive lanes consecutive pieces, each lane its
-// pieces in order, then the wave's butterfly: k_grad_rows' order), then on lane 0 the marginal
+// its first 64 nb columns (row_sqnorm_d2, as k_grad_rows), then on lane 0 the marginal
 // variance, the cavity, the tilted moments, the damped candidate sites and the row's terms of
 // log Z_EP and of the stop measure. Rows >= n get exact zeros and enter no sum.
 __global__ __launch_bounds__(256) void k_ep_sites(MatB A, MatB K, int n, int nb, NewtonVecs v,
                                                   const double* __restrict__ y, EpVecs e,
                                                   double damping, Live live) {
     const int b = blockIdx.y;
-    if (!live_e(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int np = 64 * nb;
     if (r >= np) return;
@@ -55,14 +50,7 @@ __global__ __launch_bounds__(256) void k_ep_sites(MatB A, MatB K, int n, int nb,
         }
         return;
     }
-    const double* row = A.base + b * A.cstride + (int64_t)(np + r) * A.ld;
-    double s = 0.0;
-    for (int c = 2 * lane; c < np; c += 128) {
-        const d2_t x = *reinterpret_cast<const d2_t*>(row + c);
-        s = fma(x.x, x.x, s);
-        s = fma(x.y, x.y, s);
-    }
-    s = wave_sum_d(s);
+    const double s = row_sqnorm_d2(A.base + b * A.cstride + (int64_t)(np + r) * A.ld, np, lane);
     if (lane != 0) return;
     const double var = K.base[b * K.cstride + (int64_t)r * K.ld + r] - s;
     const double tau = e.tau[o], nu = e.nu[o], yi = y[r];
@@ -156,7 +144,7 @@ void launch_ep_chain(EpVecs e, NewtonVecs v, int n, int np, const double* ldet, 
 // thread, one 16-byte access per vector (vstride and np are multiples of 64).
 __global__ __launch_bounds__(256) void k_ep_handoff(NewtonVecs v, int n, int np, Live live) {
     const int b = blockIdx.y;
-    if (!live_e(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int i = 2 * (blockIdx.x * 256 + threadIdx.x);
     if (i >= np) return;
     const int64_t o = b * v.vstride + i;

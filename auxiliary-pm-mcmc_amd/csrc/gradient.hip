@@ -13,11 +13,7 @@
 //   the SE family, cov_G (apm_internal.h) for Matern 3/2 and 5/2
 // with W, L, a of the last Newton iteration (latent_posterior_approximations.py:81-106).
 #include "apm_internal.h"
-
-#define GK 32         // features per LDS chunk (k_gram's)
-#define GP (128 + 2)  // LDS row pitch in doubles (k_gram's)
-// lane (g = lane >> 3 or lane & 7) -> its 8 rows (columns) of the wave's 64x64 tile (k_gram's)
-#define R8(g, p) (((p) >> 2) * 32 + 4 * (g) + ((p) & 3))
+#include "pair_tile.h"
 
 // nothing moves across: neither the compiler's passes (memory clobber) nor the machine scheduler
 #define APM_WALL()                           \
@@ -26,13 +22,8 @@
         __builtin_amdgcn_sched_barrier(0);   \
     } while (0)
 
-__device__ __forceinline__ bool live_g(const Live& lv, int b) {
-    return lv.active[b] != 0 && lv.status[b] == 0;
-}
-
 // One wave per (chain, training row r): dS_r from the squared norm of row np + r of the work
-// matrix over its first 64 nb columns (the row of (K W^1/2) L^-T; 16-byte loads, consecutive
-// lanes consecutive pieces, each lane its pieces in order, then the wave's butterfly) and K's own
+// matrix over its first 64 nb columns (the row of (K W^1/2) L^-T; row_sqnorm_d2) and K's own
 // diagonal entry, then g_r and s2_r at the mode. Rows >= n get exact zeros.
 template <int LIK>
 __global__ __launch_bounds__(256) void k_grad_rows(MatB A, MatB K, int n, int nb,
@@ -42,7 +33,7 @@ __global__ __launch_bounds__(256) void k_grad_rows(MatB A, MatB K, int n, int nb
                                                    double* __restrict__ s2, int64_t gstride,
                                                    Live live) {
     const int b = blockIdx.y;
-    if (!live_g(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int np = 64 * nb;
     if (r >= np) return;
@@ -51,14 +42,7 @@ __global__ __launch_bounds__(256) void k_grad_rows(MatB A, MatB K, int n, int nb
         if (lane == 0) dS[o] = g[o] = s2[o] = 0.0;
         return;
     }
-    const double* row = A.base + b * A.cstride + (int64_t)(np + r) * A.ld;
-    double s = 0.0;
-    for (int c = 2 * lane; c < np; c += 128) {
-        const d2_t v = *reinterpret_cast<const d2_t*>(row + c);
-        s = fma(v.x, v.x, s);
-        s = fma(v.y, v.y, s);
-    }
-    s = wave_sum_d(s);
+    const double s = row_sqnorm_d2(A.base + b * A.cstride + (int64_t)(np + r) * A.ld, np, lane);
     if (lane != 0) return;
     const double ds = K.base[b * K.cstride + (int64_t)r * K.ld + r] - s;
     const double fi = f[b * vstride + r], yi = y[r];
@@ -81,7 +65,7 @@ void launch_grad_rows(int lik, MatB A, MatB K, int n, int nb, const double* f, c
 __global__ __launch_bounds__(256) void k_grad_fill(MatB A, const double* __restrict__ Ws,
                                                    int64_t vstride, int nb, Live live) {
     const int b = blockIdx.y;
-    if (!live_g(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int t = blockIdx.x, nbl = nb * nb;
     int ti, tj;
     int64_t c0 = 0;
@@ -89,11 +73,7 @@ __global__ __launch_bounds__(256) void k_grad_fill(MatB A, const double* __restr
         ti = t / nb;
         tj = t % nb;
     } else {  // lower-triangular tile index -> (ti, tj) of the bottom-right block
-        const int u = t - nbl;
-        ti = (int)floor((sqrt(8.0 * u + 1.0) - 1.0) * 0.5);
-        while (ti * (ti + 1) / 2 > u) --ti;
-        while ((ti + 1) * (ti + 2) / 2 <= u) ++ti;
-        tj = u - ti * (ti + 1) / 2;
+        lower_tri_index(t - nbl, ti, tj);
         c0 = (int64_t)nb * 64;
     }
     const bool dg = t < nbl && ti == tj;
@@ -125,7 +105,7 @@ __global__ __launch_bounds__(256) void k_grad_q(const double* __restrict__ s2,
                                                 double* __restrict__ q, int64_t gstride, int n,
                                                 int np, Live live) {
     const int b = blockIdx.y;
-    if (!live_g(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= np) return;
     const int64_t o = b * gstride + i;
@@ -138,28 +118,11 @@ void launch_grad_q(const double* s2, const double* u, double* q, int64_t gstride
                np, live);
 }
 
-// k_grad_reduce's staging step (both of a Matern family's passes take it): features [k0, k0 + kc)
-// of the super-tile's rows and columns -> LDS, pre-scaled by 1/tau_k
-#define GRAD_STAGE(k0, kc)                                                                       \
-    do {                                                                                         \
-        __syncthreads();                                                                         \
-        if (tid < kc) itau[tid] = exp(-th[ard == 0 ? 1 : 1 + k0 + tid]);                         \
-        __syncthreads();                                                                         \
-        for (int e = tid; e < 128 * GK; e += 256) {                                              \
-            const int r = e / GK, k = e % GK; /* consecutive lanes: consecutive features */      \
-            const int gi = si * 128 + r, gj = sj * 128 + r;                                      \
-            const double sc = (k < kc) ? itau[k] : 0.0;                                          \
-            xi[k][r] = (k < kc && gi < n) ? X[(int64_t)gi * ldx + k0 + k] * sc : 0.0;            \
-            xj[k][r] = (k < kc && gj < n) ? X[(int64_t)gj * ldx + k0 + k] * sc : 0.0;            \
-        }                                                                                        \
-        __syncthreads();                                                                         \
-    } while (0)
-
 // The contraction sum_ik M_ik (dK/dtheta_j)_ik for every j in one pass over the inputs: k_gram's
 // tiling - one workgroup of 4 waves per lower 128x128 super-tile (si, sj) and chain, wave w the
 // 64x64 tile (2si + w/2, 2sj + w%2) (the upper tile of a diagonal super-tile and tiles beyond the
-// padded size are skipped), 8x8 pairs per lane, features pre-scaled by 1/tau_k while staged
-// through LDS in chunks of GK. Per pair the lane first forms w = c M_ik S_ik once: M from Rn (the
+// padded size are skipped), 8x8 pairs per lane, the staging and the operand load of pair_tile.h.
+// Per pair the lane first forms w = c M_ik S_ik once: M from Rn (the
 // bottom-right block of the work matrix, -R in its lower tiles), a, q and g; S from K off the
 // diagonal and s = exp(theta_0) on it (no epsilon); c the count of the symmetric sum - 2 for
 // i > k, 1 on the diagonal, 0 for the upper half of a diagonal tile and for any row or column
@@ -172,9 +135,9 @@ void launch_grad_q(const double* s2, const double* u, double* q, int64_t gstride
 //
 // FAM (APM_FAM_*): for the SE family the one weight w serves theta_0 and the length scales
 // (G = S). For a Matern family the length scales need c M G, and G needs the pair's complete r^2
-// before the per-feature sums start; a second 8x8 block of registers is not available (254
+// before the per-feature sums start; a second 8x8 block of registers is not available (242
 // VGPRs), so the kernel makes two passes over the staged feature chunks: the first accumulates
-// r^2 into w (k_gram's loop, k in order), the K / R / vector stage adds c M S into theta_0's sum
+// r^2 into w (pair_r2_chunk, k in order), the K / R / vector stage adds c M S into theta_0's sum
 // and overwrites w with c M G (cov_G of the lane's own r^2), the second is the SE pass. Every
 // sum keeps the order above. ard: theta[1 + k] scales feature k, else theta[1] every feature.
 template <int FAM>
@@ -184,17 +147,12 @@ __global__ __launch_bounds__(256, FAM == APM_FAM_SE ? 1 : 2) void k_grad_reduce(
     int64_t vstride, const double* __restrict__ qvec, const double* __restrict__ gvec,
     int64_t gstride, double* __restrict__ part, int64_t pstride, int P, Live live) {
     const int b = blockIdx.y;
-    if (!live_g(live, b)) return;
-    // lower-triangular super-tile index -> (si, sj), si >= sj
+    if (!live_chain(live, b)) return;
     const int t = blockIdx.x;
-    int si = (int)floor((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
-    while (si * (si + 1) / 2 > t) --si;
-    while ((si + 1) * (si + 2) / 2 <= t) ++si;
-    const int sj = t - si * (si + 1) / 2;
+    int si, sj;  // the lower super-tile, si >= sj
+    lower_tri_index(t, si, sj);
 
-    __shared__ __attribute__((aligned(16))) double xi[GK][GP];
-    __shared__ __attribute__((aligned(16))) double xj[GK][GP];
-    __shared__ double itau[GK];
+    __shared__ PairTile lds;
     __shared__ double red[4][GK];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int tr = lane >> 3, tc = lane & 7;
@@ -206,36 +164,15 @@ __global__ __launch_bounds__(256, FAM == APM_FAM_SE ? 1 : 2) void k_grad_reduce(
 
     double w[8][8];
     double s0 = 0.0;
-    if constexpr (FAM != APM_FAM_SE) {  // first pass: w <- the pairs' r^2 (k_gram's loop)
+    if constexpr (FAM != APM_FAM_SE) {  // first pass: w <- the pairs' r^2
 #pragma unroll
         for (int p = 0; p < 8; ++p)
 #pragma unroll
             for (int q = 0; q < 8; ++q) w[p][q] = 0.0;
         for (int k0 = 0; k0 < d; k0 += GK) {
             const int kc = min(GK, d - k0);
-            GRAD_STAGE(k0, kc);
-            if (mine) {
-                for (int k = 0; k < kc; ++k) {
-                    double a[8], c[8];
-#pragma unroll
-                    for (int h = 0; h < 4; ++h) {
-                        const d2_t va = *reinterpret_cast<const d2_t*>(&xi[k][ro + R8(tr, 2 * h)]);
-                        const d2_t vc = *reinterpret_cast<const d2_t*>(&xj[k][co + R8(tc, 2 * h)]);
-                        a[2 * h] = va.x;
-                        a[2 * h + 1] = va.y;
-                        c[2 * h] = vc.x;
-                        c[2 * h + 1] = vc.y;
-                    }
-#pragma unroll
-                    for (int p = 0; p < 8; ++p) {
-                        double df[8];
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) df[q] = a[p] - c[q];  // pre-scaled by 1/tau_k
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) w[p][q] = fma(df[q], df[q], w[p][q]);
-                    }
-                }
-            }
+            pair_stage(lds, th, ard, k0, kc, X, ldx, n, si * 128, X, ldx, n, sj * 128);
+            if (mine) pair_r2_chunk(lds, kc, ro, tr, co, tc, w);
         }
     }
     if (mine) {
@@ -361,20 +298,12 @@ __global__ __launch_bounds__(256, FAM == APM_FAM_SE ? 1 : 2) void k_grad_reduce(
     double iso = 0.0;  // (thread 0: the features' sums in order)
     for (int k0 = 0; k0 < d; k0 += GK) {
         const int kc = min(GK, d - k0);
-        GRAD_STAGE(k0, kc);
+        pair_stage(lds, th, ard, k0, kc, X, ldx, n, si * 128, X, ldx, n, sj * 128);
         for (int k = 0; k < kc; ++k) {
             double sk = 0.0;
             if (mine) {
                 double a[8], c[8];
-#pragma unroll
-                for (int h = 0; h < 4; ++h) {
-                    const d2_t va = *reinterpret_cast<const d2_t*>(&xi[k][ro + R8(tr, 2 * h)]);
-                    const d2_t vc = *reinterpret_cast<const d2_t*>(&xj[k][co + R8(tc, 2 * h)]);
-                    a[2 * h] = va.x;
-                    a[2 * h + 1] = va.y;
-                    c[2 * h] = vc.x;
-                    c[2 * h + 1] = vc.y;
-                }
+                pair_operands(lds, k, ro, tr, co, tc, a, c);
                 double sp[8];  // one chain of 8 fmas per row: 8 independent chains in flight
 #pragma unroll
                 for (int p = 0; p < 8; ++p) {
@@ -427,7 +356,7 @@ __global__ __launch_bounds__(256) void k_grad_sum(const double* __restrict__ par
                                                   int64_t pstride, int nst, int P,
                                                   double* __restrict__ grad, Live live) {
     const int b = blockIdx.y;
-    if (!live_g(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= P) return;
     const double* pb = part + b * pstride + p;

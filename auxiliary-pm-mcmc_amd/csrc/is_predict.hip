@@ -12,10 +12,6 @@
 #include "gh_table.h"
 #include "tile64.h"
 
-__device__ __forceinline__ bool live_ip(const Live& lv, int b) {
-    return lv.active[b] != 0 && lv.status[b] == 0;
-}
-
 // ------------------------------------------------------------------------------- weights
 // Per chain: log w_s = cst + sum_i partial[i][s] as k_lme forms it (the per-sample values the
 // theta-call's k_ugemm left in `partial`, added in the same order), wbar_s = exp(log w_s - max) /
@@ -28,7 +24,7 @@ __global__ __launch_bounds__(256) void k_is_weights(const double* __restrict__ p
                                                     double* __restrict__ wbar,
                                                     double* __restrict__ ess, Live live) {
     const int b = blockIdx.x;
-    if (!live_ip(live, b)) return;
+    if (!live_chain(live, b)) return;
     __shared__ double red[4];
     const double* pb = partial + b * pstride;
     double* wb = wbar + (int64_t)b * sp;
@@ -72,7 +68,7 @@ void launch_is_weights(const double* partial, int64_t pstride, int nb, int S, in
 __global__ __launch_bounds__(256) void k_is_ut(UPool P, const int64_t* __restrict__ ubufs, int np,
                                                double* __restrict__ Ut, Live live) {
     const int b = blockIdx.z;
-    if (!live_ip(live, b)) return;
+    if (!live_chain(live, b)) return;
     __shared__ double T[64][65];
     const double* U = P.base + ubufs[b] * P.stride;
     const int k0 = blockIdx.x * 64, s0 = blockIdx.y * 64;
@@ -95,8 +91,8 @@ void launch_is_ut(UPool P, const int64_t* ubufs, int np, double* Ut, Live live, 
 
 // ------------------------------------------------------------------------------- the p-rows
 // One wave per (chain, row r < 64 mb) of the solved rows p_r^T = k*_r^T L_K^-T in A's rows
-// [row0, ..) x columns [0, 64 nb): v*_r = sig[b] - |p_r|^2 (k_predict_reduce's order: each lane its
-// pieces in order, then the wave's butterfly; nothing is clamped), c_r = the tile-column partials
+// [row0, ..) x columns [0, 64 nb): v*_r = sig[b] - |p_r|^2 (row_sqnorm_d2, as k_predict_reduce;
+// nothing is clamped), c_r = the tile-column partials
 // of k*_r . a in order, and the reversed row p_r^T J into columns [64 nb, 128 nb) of the same row
 // (the right-hand side of the solve against L'). Rows >= ms are exact zeros (k_gram_cross).
 __global__ __launch_bounds__(256) void k_is_rows(MatB A, int64_t row0, int ms, int mb, int nb,
@@ -106,27 +102,17 @@ __global__ __launch_bounds__(256) void k_is_rows(MatB A, int64_t row0, int ms, i
                                                  double* __restrict__ cvec, int64_t ostride,
                                                  Live live) {
     const int b = blockIdx.y;
-    if (!live_ip(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= 64 * mb) return;
     const int np = 64 * nb;
     double* row = A.base + b * A.cstride + (row0 + r) * A.ld;
-    double s = 0.0;
-    for (int c = 2 * lane; c < np; c += 128) {
-        const d2_t v = *reinterpret_cast<const d2_t*>(row + c);
-        s = fma(v.x, v.x, s);
-        s = fma(v.y, v.y, s);
+    const double s = row_sqnorm_d2(row, np, lane, [&](int c, d2_t v) {
         *reinterpret_cast<d2_t*>(row + np + (np - 2 - c)) = d2_t{v.y, v.x};
-    }
-    s = wave_sum_d(s);
+    });
     if (lane != 0) return;
-    double mu = 0.0;
-    if (r < ms) {
-        const double* pb = part + b * pstride + r;
-        for (int tj = 0; tj < nb; ++tj) mu += pb[(int64_t)tj * (64 * mb)];
-    }
     vstar[b * ostride + r] = sig[b] - s;
-    cvec[b * ostride + r] = mu;
+    cvec[b * ostride + r] = r < ms ? sum_tile_partials(part + b * pstride + r, nb, 64 * mb) : 0.0;
 }
 
 void launch_is_rows(MatB A, int64_t row0, int ms, int mb, int nb, const double* sig,
@@ -188,7 +174,7 @@ __global__ __launch_bounds__(256) void k_is_pred_gemm(
     const double* __restrict__ cvec, int64_t ostride, double* __restrict__ pp, int64_t npr,
     Live live) {
     const int b = blockIdx.z;
-    if (!live_ip(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int tj = blockIdx.x, ti = blockIdx.y, nst = gridDim.x;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wr = w >> 1, wc = w & 1;
     __shared__ GemmSmem sm;
@@ -254,7 +240,7 @@ __global__ __launch_bounds__(256) void k_is_finish(const double* __restrict__ pp
                                                    double* __restrict__ prob, int64_t ostride,
                                                    Live live) {
     const int b = blockIdx.y;
-    if (!live_ip(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r >= ms) return;
     double q[3];

@@ -10,16 +10,12 @@
 // extra row below B, so the factorisation of the (np+64) x np trapezoid returns it in that row.
 #include "apm_internal.h"
 
-__device__ __forceinline__ bool live_b(const Live& lv, int b) {
-    return lv.active[b] != 0 && lv.status[b] == 0;
-}
-
 // ------------------------------------------------------------------------------- vectors
 template <int LIK>
 __global__ __launch_bounds__(256) void k_newton_prep(NewtonVecs v, const double* __restrict__ y,
                                                      int n, int np, Live live) {
     const int b = blockIdx.y;
-    if (!live_b(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= np) return;
     const int64_t o = b * v.vstride + i;
@@ -47,7 +43,7 @@ __global__ __launch_bounds__(256) void k_gemv(MatB M, const double* __restrict__
                                               int64_t xstride, double* __restrict__ out,
                                               int64_t ostride, int np, Live live) {
     const int b = blockIdx.y;
-    if (!live_b(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const double* xb = x + b * xstride;
     for (int row = blockIdx.x * 16 + w * 4; row < blockIdx.x * 16 + w * 4 + 4; ++row) {
@@ -70,20 +66,12 @@ void launch_gemv(MatB M, const double* x, int64_t xstride, double* out, int64_t 
                        ostride, np, live);
 }
 
-__device__ __forceinline__ void tri_decode(int t, int& ti, int& tj) {
-    int i = (int)floor((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
-    while (i * (i + 1) / 2 > t) --i;
-    while ((i + 1) * (i + 2) / 2 <= t) ++i;
-    ti = i;
-    tj = t - i * (i + 1) / 2;
-}
-
 // B = I + W^1/2 K W^1/2 into the lower tiles of A's top-left np x np, and the extra row block
 // rows [np, np+64): row np = W^1/2 (K b) (the Newton right-hand side), the others zero.
 __global__ __launch_bounds__(256) void k_form_B(MatB K, MatB A, NewtonVecs v, int nb,
                                                 Live live) {
     const int b = blockIdx.y;
-    if (!live_b(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int t = blockIdx.x, ntri = nb * (nb + 1) / 2;
     const double* Kb = K.base + b * K.cstride;
     double* Ab = A.base + b * A.cstride;
@@ -91,7 +79,7 @@ __global__ __launch_bounds__(256) void k_form_B(MatB K, MatB A, NewtonVecs v, in
     const int tid = threadIdx.x;
     if (t < ntri) {
         int ti, tj;
-        tri_decode(t, ti, tj);
+        lower_tri_index(t, ti, tj);
         for (int e = tid; e < 4096; e += 256) {
             const int r = ti * 64 + (e >> 6), c = tj * 64 + (e & 63);
             const double kv = Kb[(int64_t)r * K.ld + c];
@@ -116,7 +104,7 @@ void launch_form_B(MatB K, MatB A, NewtonVecs v, int np, Live live, int nchains,
 
 __global__ __launch_bounds__(256) void k_newton_update(NewtonVecs v, int np, Live live) {
     const int b = blockIdx.y;
-    if (!live_b(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= np) return;
     const int64_t o = b * v.vstride + i;
@@ -161,9 +149,9 @@ void launch_newton_check(NewtonVecs v, int n, int np, double tol, int* active, c
 // lower tiles of src's np x np -> dst (PriorMC: factor K itself)
 __global__ __launch_bounds__(256) void k_copy_lower(MatB src, MatB dst, Live live) {
     const int b = blockIdx.y;
-    if (!live_b(live, b)) return;
+    if (!live_chain(live, b)) return;
     int ti, tj;
-    tri_decode(blockIdx.x, ti, tj);
+    lower_tri_index(blockIdx.x, ti, tj);
     const double* S = src.base + b * src.cstride;
     double* D = dst.base + b * dst.cstride;
     d2_t v[8];  // 16-byte pieces, all loads in flight before the stores
@@ -197,7 +185,7 @@ void launch_copy_lower(MatB src, MatB dst, int np, Live live, int nchains, hipSt
 __global__ __launch_bounds__(256) void k_form_aug(MatB K, MatB A, NewtonVecs v, int nb,
                                                   Live live, int lower_only) {
     const int b = blockIdx.y;
-    if (!live_b(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int t = blockIdx.x;
     const int nbl = nb * nb, ntri = nb * (nb + 1) / 2;
     const double* Kb = K.base + b * K.cstride;
@@ -215,7 +203,7 @@ __global__ __launch_bounds__(256) void k_form_aug(MatB K, MatB A, NewtonVecs v, 
         }
     } else if (t < nbl + ntri) {  // bottom-right lower tiles: K
         int ti, tj;
-        tri_decode(t - nbl, ti, tj);
+        lower_tri_index(t - nbl, ti, tj);
         for (int e = tid; e < 4096; e += 256) {
             const int r = ti * 64 + (e >> 6), c = tj * 64 + (e & 63);
             Ab[(np + r) * A.ld + np + c] = Kb[(int64_t)r * K.ld + c];
@@ -285,7 +273,7 @@ __global__ __launch_bounds__(256) void k_slot_write_L(MatB A, SlotSet S,
                                                       const double* __restrict__ fvec,
                                                       double* rowe) {
     const int b = blockIdx.y;
-    if (live.status[b] != 0 || live.active[b] == 0) return;
+    if (!live_chain(live, b)) return;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int r = blockIdx.x * 4 + w;  // 0 .. np+63
     const double* Ab = A.base + b * A.cstride;
@@ -340,7 +328,7 @@ __global__ __launch_bounds__(256) void k_slot_write_L64(MatB A, SlotSet S,
                                                         const int64_t* __restrict__ slots,
                                                         int mode, int np, Live live) {
     const int b = blockIdx.y;
-    if (live.status[b] != 0 || live.active[b] == 0 || !S.wide[slots[b]] || mode == 3) return;
+    if (!live_chain(live, b) || !S.wide[slots[b]] || mode == 3) return;
     double* const L0 = S.L64[slots[b]];
     if (!L0) return;  // no buffer yet: the host attaches one and writes the slot again
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -367,7 +355,7 @@ __global__ __launch_bounds__(256) void k_slot_write_vec(MatB A, NewtonVecs v, co
                                                         int mode, int n, Live live) {
     (void)A;
     const int b = blockIdx.x;
-    if (live.status[b] != 0 || live.active[b] == 0) return;
+    if (!live_chain(live, b)) return;
     __shared__ double red[4];
     const int64_t np = (int64_t)nb * 64;
     const int64_t so = slots[b] * S.vstride;
@@ -479,7 +467,7 @@ __global__ __launch_bounds__(256) void k_guard_check(const double* __restrict__ 
                                                      const double* fvec, int fail_code,
                                                      Live live) {
     const int b = blockIdx.x;
-    if (live.status[b] != 0 || live.active[b] == 0) return;
+    if (!live_chain(live, b)) return;
     __shared__ double red[4];
     const int64_t np = (int64_t)nb * 64;
     const int64_t sl = slots[b];

@@ -27,7 +27,7 @@
 __global__ __launch_bounds__(256) void k_row32(MatF Bf, int64_t row, int np, double* out,
                                                int64_t ostride, Live live) {
     const int b = blockIdx.y;
-    if (!live32(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c < np) out[b * ostride + c] = (double)Bf.base[b * Bf.cstride + row * Bf.ld + c];
 }
@@ -49,12 +49,6 @@ void launch_row32(MatF Bf, int64_t row, int np, double* out, int64_t ostride, Li
 // I + W^1/2 K W^1/2 (fusing k_form_B32 into the x = b pass).
 // TPW > 1: a workgroup takes TPW consecutive tiles of its chain, the next tile's 32 KB loaded
 // into registers while the current one is reduced (the same per-tile sums: bitwise equal)
-__device__ __forceinline__ void symv_tile_ij(int t, int& ti, int& tj) {
-    ti = (int)floor((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
-    while (ti * (ti + 1) / 2 > t) --ti;
-    while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
-    tj = t - ti * (ti + 1) / 2;
-}
 template <int TPW>
 __global__ __launch_bounds__(256) void k_symv_part(MatB K, const double* __restrict__ x,
                                                    int64_t xstride, double* __restrict__ part,
@@ -62,14 +56,14 @@ __global__ __launch_bounds__(256) void k_symv_part(MatB K, const double* __restr
                                                    const double* __restrict__ Ws, int64_t wstride,
                                                    Live live) {
     const int b = blockIdx.y;
-    if (!live32(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int ntile = nb * (nb + 1) / 2;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int rg = tid >> 4, cg = tid & 15;  // rows 4rg .. 4rg+3, columns 4cg .. 4cg+3
     __shared__ double cs[4][64];
     auto load = [&](int t, d2_t (&v)[4][2]) {
         int ti, tj;
-        symv_tile_ij(t, ti, tj);
+        lower_tri_index(t, ti, tj);
         const double* Kt =
             K.base + b * K.cstride + (int64_t)(ti * 64 + 4 * rg) * K.ld + tj * 64 + 4 * cg;
 #pragma unroll
@@ -85,7 +79,7 @@ __global__ __launch_bounds__(256) void k_symv_part(MatB K, const double* __restr
         d2_t vn[4][2];
         if (TPW > 1 && tt + 1 < TPW && t + 1 < ntile) load(t + 1, vn);
         int ti, tj;
-        symv_tile_ij(t, ti, tj);
+        lower_tri_index(t, ti, tj);
         const double* xb = x + b * xstride;
         const d2_t xj0 = *reinterpret_cast<const d2_t*>(xb + tj * 64 + 4 * cg);
         const d2_t xj1 = *reinterpret_cast<const d2_t*>(xb + tj * 64 + 4 * cg + 2);
@@ -170,7 +164,7 @@ __global__ __launch_bounds__(256) void k_symv_reduce(const double* __restrict__ 
                                                      const double* __restrict__ Ws,
                                                      int64_t wstride, Live live) {
     const int b = blockIdx.y;
-    if (!live32(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
     const int np = nb * 64;
     if (i >= np) return;
@@ -224,7 +218,7 @@ __global__ __launch_bounds__(256) void k_trsv_fwd32(MatF A, int J, const float* 
                                                     int64_t dstride, double* r, double* y,
                                                     int64_t vstride, Live live) {
     const int b = blockIdx.y;
-    if (!live32(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int I = J + blockIdx.x;
     const int tid = threadIdx.x, c = tid & 63, q = tid >> 6;
     __shared__ float T[64][65];
@@ -260,7 +254,7 @@ __global__ __launch_bounds__(256) void k_trsv_bwd32(MatF A, int J, const float* 
                                                     int64_t dstride, double* r, double* z,
                                                     int64_t vstride, Live live) {
     const int b = blockIdx.y;
-    if (!live32(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int I = blockIdx.x;
     const int tid = threadIdx.x, c = tid & 63, q = tid >> 6;
     __shared__ double vj[64];
@@ -313,7 +307,7 @@ __global__ __launch_bounds__(256) void k_trsv_bwd32(MatF A, int J, const float* 
 __global__ __launch_bounds__(256) void k_nan_fill(double* out, int64_t vstride, int np,
                                                   Live live) {
     const int b = blockIdx.y;
-    if (!live32(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < np) out[b * vstride + i] = __builtin_nan("");
 }
@@ -341,7 +335,7 @@ __global__ __launch_bounds__(256) void k_trsv32_mw(MatF A, int nb, const float* 
         return;
     }
     const int b = (int)(tk / G), g = (int)(tk % G);
-    if (!live32(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int row = t >> 2, q = t & 3;  // tile row, 16-column quarter
     extern __shared__ double trm_sm[];
@@ -555,7 +549,7 @@ __global__ __launch_bounds__(256) void k_refine(int mode, const double* __restri
                                                 const double* __restrict__ Kt, double* out,
                                                 int64_t vstride, int np, Live live) {
     const int b = blockIdx.y;
-    if (!live32(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= np) return;
     const int64_t o = b * vstride + i;
@@ -583,7 +577,7 @@ __global__ __launch_bounds__(256) void k_refine_check(const double* __restrict__
                                                       int fail_code, int step, int last,
                                                       double* prev, int* refining, Live live) {
     const int b = blockIdx.x;
-    if (!live32(live, b)) return;
+    if (!live_chain(live, b)) return;
     double mx = 0.0, md = 0.0;
 #pragma unroll 4  // (loads of 4 steps in flight)
     for (int i = threadIdx.x; i < np; i += 256) {
@@ -622,7 +616,7 @@ void launch_refine_check(const double* x, const double* d, int64_t vstride, int 
 
 __global__ void k_refine_mask(Live live, int* refining, int nchains) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < nchains) refining[b] = live32(live, b) ? 1 : 0;
+    if (b < nchains) refining[b] = live_chain(live, b) ? 1 : 0;
 }
 
 void launch_refine_mask(Live live, int* refining, int nchains, hipStream_t s) {

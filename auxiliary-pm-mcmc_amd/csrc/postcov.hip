@@ -11,16 +11,12 @@
 //   g = C_chol^-1 f_post = U^T L_K^-1 f_post = J L'^T J h,  h = L_K^-1 f_post,  log|B| = log|M|.
 #include "apm_internal.h"
 
-__device__ __forceinline__ bool live_pc(const Live& lv, int b) {
-    return lv.active[b] != 0 && lv.status[b] == 0;
-}
-
 // rows [row0, row0+64) of A over columns [0, ncols): row row0 = vec, the others 0
 __global__ __launch_bounds__(256) void k_set_rhs(MatB A, int64_t row0, int ncols,
                                                  const double* __restrict__ vec, int64_t vstride,
                                                  Live live) {
     const int b = blockIdx.y;
-    if (!live_pc(live, b)) return;
+    if (!live_chain(live, b)) return;
     double* Ab = A.base + b * A.cstride;
     const int c0 = blockIdx.x * 64;
     for (int e = threadIdx.x; e < 4096; e += 256) {
@@ -39,7 +35,7 @@ void launch_set_rhs(MatB A, int64_t row0, int ncols, const double* vec, int64_t 
 __global__ __launch_bounds__(256) void k_get_row(MatB A, int64_t row, int n, double* out,
                                                  int64_t ostride, Live live) {
     const int b = blockIdx.y;
-    if (!live_pc(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c < n) out[b * ostride + c] = A.base[b * A.cstride + row * A.ld + c];
 }
@@ -105,7 +101,7 @@ __global__ __launch_bounds__(256) void k_form_y2_rev(MatB L, MatB dst, int64_t d
                                                      int64_t vstride, int nb, Live live,
                                                      int zero_all) {
     const int b = blockIdx.y;
-    if (!live_pc(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int half = (nb + 1) / 2;
     const int sr = blockIdx.x / half, c1 = blockIdx.x % half, c2 = nb - 1 - c1;
     double* Lr = L.base + b * L.cstride + (int64_t)(sr * 64) * L.ld;
@@ -142,11 +138,9 @@ void launch_form_y2_rev(MatB L, MatB dst, int64_t dcol0, const double* Ws, int64
 // lower tiles of M <- I
 __global__ __launch_bounds__(256) void k_identity_lower(MatB M, Live live) {
     const int b = blockIdx.y;
-    if (!live_pc(live, b)) return;
-    int ti = (int)floor((sqrt(8.0 * blockIdx.x + 1.0) - 1.0) * 0.5);
-    while (ti * (ti + 1) / 2 > (int)blockIdx.x) --ti;
-    while ((ti + 1) * (ti + 2) / 2 <= (int)blockIdx.x) ++ti;
-    const int tj = blockIdx.x - ti * (ti + 1) / 2;
+    if (!live_chain(live, b)) return;
+    int ti, tj;
+    lower_tri_index(blockIdx.x, ti, tj);
     double* D = M.base + b * M.cstride + (int64_t)(ti * 64) * M.ld + tj * 64;
 #pragma unroll
     for (int h = 0; h < 8; ++h) {
@@ -172,12 +166,9 @@ __global__ __launch_bounds__(256) void k_trmv_part(MatB L, const double* __restr
                                                    int64_t vstride, double* __restrict__ part,
                                                    int64_t pstride, int nb, Live live) {
     const int b = blockIdx.y;
-    if (!live_pc(live, b)) return;
-    const int t = blockIdx.x;
-    int ti = (int)floor((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
-    while (ti * (ti + 1) / 2 > t) --ti;
-    while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
-    const int tj = t - ti * (ti + 1) / 2;
+    if (!live_chain(live, b)) return;
+    int ti, tj;
+    lower_tri_index(blockIdx.x, ti, tj);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int rg = tid >> 4, cg = tid & 15;
     const int np = nb * 64;
@@ -226,7 +217,7 @@ __global__ __launch_bounds__(256) void k_trmv_reduce(const double* __restrict__ 
                                                      double* __restrict__ out, int64_t vstride,
                                                      Live live) {
     const int b = blockIdx.y;
-    if (!live_pc(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int c = blockIdx.x * 256 + threadIdx.x;
     const int np = nb * 64;
     if (c >= np) return;
@@ -267,7 +258,7 @@ __global__ __launch_bounds__(256) void k_post32_convert(MatB A, MatF S, const do
                                                         int64_t d32stride, int nb, int outer,
                                                         int k0, int k1, Live live, Planes16 pl) {
     const int b = blockIdx.y;
-    if (!live_pc(live, b)) return;
+    if (!live_chain(live, b)) return;
     const int nc = k1 - k0, T = (nb - k0) * nc;
     const int t = blockIdx.x;
     const double* src;

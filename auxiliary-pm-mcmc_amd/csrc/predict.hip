@@ -9,17 +9,13 @@
 // with W, L, a of the last Newton iteration (latent_posterior_approximations.py:81-112).
 #include "apm_internal.h"
 #include "gh_table.h"
-
-#define GK 32         // features per LDS chunk (k_gram's)
-#define GP (128 + 2)  // LDS row pitch in doubles (k_gram's)
-// lane (g = lane >> 3 or lane & 7) -> its 8 rows (columns) of the wave's 64x64 tile (k_gram's)
-#define R8(g, p) (((p) >> 2) * 32 + 4 * (g) + ((p) & 3))
+#include "pair_tile.h"
 
 // Rectangular twin of k_gram: one workgroup of 4 waves per 128x128 super-tile (si over the test
 // rows, sj over the training columns), wave w the 64x64 tile (2si + w/2, 2sj + w%2), 8x8 pairs per
-// lane, features pre-scaled by 1/tau_k while staged through LDS in chunks of GK and summed over k
-// in order - the arithmetic of k_gram. s = exp(theta_0) comes from the host (sig[b], libm's exp,
-// the same value in k* and in the prior variance k** of k_predict_reduce), so an uninformed test
+// lane, the staging and the distance loop of pair_tile.h. s = exp(theta_0) comes from the host
+// (sig[b], libm's exp, the same value in k* and in the prior variance k** of k_predict_reduce), so
+// an uninformed test
 // point returns bitwise the caller's exp(theta_0); K's own s is the device's exp and may differ
 // from it in the last bit. Every (row, column) value depends on its own pair of points only, and
 // the partial sums of mu* on the column position only: a chain's outputs do not depend on its
@@ -33,14 +29,12 @@ __global__ __launch_bounds__(256, 2) void k_gram_cross(
     const double* __restrict__ Ws, const double* __restrict__ avec, int64_t vstride,
     double* __restrict__ part, int64_t pstride, Live live, int plain) {
     const int b = blockIdx.y;
-    if (live.active && (live.active[b] == 0 || live.status[b] != 0)) return;
+    if (live.active && !live_chain(live, b)) return;
     const int nsc = (nb + 1) / 2;
     const int si = blockIdx.x / nsc, sj = blockIdx.x % nsc;
 
-    __shared__ __attribute__((aligned(16))) double xi[GK][GP];
-    __shared__ __attribute__((aligned(16))) double xj[GK][GP];
-    __shared__ double itau[GK];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    __shared__ PairTile lds;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int tr = lane >> 3, tc = lane & 7;
     const int ti = 2 * si + (wv >> 1), tj = 2 * sj + (wv & 1);
     const bool mine = ti < mb && tj < nb;  // (wave-uniform)
@@ -56,39 +50,8 @@ __global__ __launch_bounds__(256, 2) void k_gram_cross(
 
     for (int k0 = 0; k0 < d; k0 += GK) {
         const int kc = min(GK, d - k0);
-        __syncthreads();
-        if (tid < kc) itau[tid] = exp(-th[ard ? 1 + k0 + tid : 1]);
-        __syncthreads();
-        for (int e = tid; e < 128 * GK; e += 256) {
-            const int r = e / GK, k = e % GK;  // consecutive lanes: consecutive features of a row
-            const int gi = si * 128 + r, gj = sj * 128 + r;
-            const double sc = (k < kc) ? itau[k] : 0.0;
-            xi[k][r] = (k < kc && gi < ms) ? Xs[(int64_t)gi * d + k0 + k] * sc : 0.0;
-            xj[k][r] = (k < kc && gj < n) ? X[(int64_t)gj * ldx + k0 + k] * sc : 0.0;
-        }
-        __syncthreads();
-        if (mine) {
-            for (int k = 0; k < kc; ++k) {
-                double a[8], c[8];
-#pragma unroll
-                for (int h = 0; h < 4; ++h) {
-                    const d2_t va = *reinterpret_cast<const d2_t*>(&xi[k][ro + R8(tr, 2 * h)]);
-                    const d2_t vc = *reinterpret_cast<const d2_t*>(&xj[k][co + R8(tc, 2 * h)]);
-                    a[2 * h] = va.x;
-                    a[2 * h + 1] = va.y;
-                    c[2 * h] = vc.x;
-                    c[2 * h + 1] = vc.y;
-                }
-#pragma unroll
-                for (int p = 0; p < 8; ++p) {
-                    double df[8];
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) df[q] = a[p] - c[q];  // pre-scaled by 1/tau_k
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) acc[p][q] = fma(df[q], df[q], acc[p][q]);
-                }
-            }
-        }
+        pair_stage(lds, th, ard, k0, kc, Xs, d, ms, si * 128, X, ldx, n, sj * 128);
+        if (mine) pair_r2_chunk(lds, kc, ro, tr, co, tc, acc);
     }
     if (!mine) return;  // (after the last barrier)
 
@@ -136,11 +99,7 @@ __global__ __launch_bounds__(256, 2) void k_gram_cross(
         s += __shfl_xor(s, 2, 64);
         s += __shfl_xor(s, 4, 64);
         if (tc == 0) pb[R8(tr, p)] = s;
-        double* dst = Ab + (row0 + ti * 64 + R8(tr, p)) * out.ld + tj * 64 + 4 * tc;
-        *reinterpret_cast<d2_t*>(dst) = d2_t{acc[p][0], acc[p][1]};
-        *reinterpret_cast<d2_t*>(dst + 2) = d2_t{acc[p][2], acc[p][3]};
-        *reinterpret_cast<d2_t*>(dst + 32) = d2_t{acc[p][4], acc[p][5]};
-        *reinterpret_cast<d2_t*>(dst + 34) = d2_t{acc[p][6], acc[p][7]};
+        pair_store_row(Ab + (row0 + ti * 64 + R8(tr, p)) * out.ld + tj * 64 + 4 * tc, acc[p]);
     }
 }
 
@@ -158,8 +117,7 @@ void launch_gram_cross(MatB out, int64_t row0, const double* Xs, int ms, int mb,
 }
 
 // One wave per (chain, test row): the squared norm of the row of V^T = (W^1/2 . k*)^T L^-T over
-// the 64 nb columns (16-byte loads, consecutive lanes consecutive pieces; each lane its pieces in
-// order, then the wave's butterfly), mu* from the tile-column partials in order, and the probit
+// the 64 nb columns (row_sqnorm_d2), mu* from the tile-column partials in order, and the probit
 // average through erfc, whose lower tail keeps its relative accuracy (Phi(z) = erfc(-z/sqrt2)/2).
 // The logit has no closed form: pi* = sum_q w_q sigma(mu* + sqrt(2 var*) x_q) over the
 // Gauss-Hermite table (gh_table.h), one pair of nodes +-x_q per lane and the
@@ -176,22 +134,14 @@ __global__ __launch_bounds__(256) void k_predict_reduce(
     const double* __restrict__ part, int64_t pstride, double* __restrict__ mean,
     double* __restrict__ var, double* __restrict__ prob, int64_t ostride, Live live) {
     const int b = blockIdx.y;
-    if (live.active[b] == 0 || live.status[b] != 0) return;
+    if (!live_chain(live, b)) return;
     const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= ms) return;
-    const double* row = A.base + b * A.cstride + (row0 + r) * A.ld;
-    double s = 0.0;
-    for (int c = 2 * lane; c < 64 * nb; c += 128) {
-        const d2_t v = *reinterpret_cast<const d2_t*>(row + c);
-        s = fma(v.x, v.x, s);
-        s = fma(v.y, v.y, s);
-    }
-    s = wave_sum_d(s);
-    if constexpr (LIK == APM_LIK_LOGIT) {  // (every lane has s; the wave stays whole)
-        const double* pb = part + b * pstride + r;
-        double mu = 0.0;
-        for (int tj = 0; tj < nb; ++tj) mu += pb[(int64_t)tj * (64 * mb)];
-        const double v = sig[b] - s;
+    // (every lane has the norm, mu* and v; the logit's wave stays whole)
+    const double s = row_sqnorm_d2(A.base + b * A.cstride + (row0 + r) * A.ld, 64 * nb, lane);
+    const double mu = sum_tile_partials(part + b * pstride + r, nb, 64 * mb);
+    const double v = sig[b] - s;
+    if constexpr (LIK == APM_LIK_LOGIT) {
         const double sd = v > 0.0 ? sqrt(2.0 * v) : 0.0;
         double acc = 0.0;
         for (int q = lane; q < APM_GH_PAIRS; q += 64) {
@@ -206,10 +156,6 @@ __global__ __launch_bounds__(256) void k_predict_reduce(
         prob[b * ostride + r] = mu < 0.0 ? acc : 0.5 + acc;
     } else {
         if (lane != 0) return;
-        const double* pb = part + b * pstride + r;
-        double mu = 0.0;
-        for (int tj = 0; tj < nb; ++tj) mu += pb[(int64_t)tj * (64 * mb)];
-        const double v = sig[b] - s;
         const double z = mu / sqrt(1.0 + v);
         mean[b * ostride + r] = mu;
         var[b * ostride + r] = v;

@@ -66,10 +66,6 @@ __device__ __forceinline__ void plane_put(unsigned short* P, const Planes16& pl,
 // D reg r of lane l is (row 4*(l>>4) + r, col l&15)  (cdna_hip_programming.md §3)
 #define F32_CROW(l, r) (4 * ((l) >> 4) + (r))
 
-__device__ __forceinline__ bool live32(const Live& lv, int b) {
-    return lv.active[b] != 0 && lv.status[b] == 0;
-}
-
 __device__ __forceinline__ void tile32_load(f4_t (&acc)[2][2], const float* T, int64_t ld, int wr,
                                             int wc, int lane) {
 #pragma unroll

@@ -8,8 +8,11 @@ case), the outputs and slot factors saved to an npz.
 Small shapes (`--small`): every host path of the library at the sizes where its schedule
 changes - N = 64 and 65 (nb = 1, 2: the 64x64 update and identity-SYRK path against the smallest
 128x128 / single-launch SYRK path), N = 1089 with d = 5 ARD (nb = 18: three outer panels, a
-partial Gram copy, the Newton lookahead with far updates, explicit-inverse panels) and a Matern
-5/2 ARD context at N = 200. One case is one shape under one setting of the environment knobs;
+partial Gram copy, the Newton lookahead with far updates, explicit-inverse panels), a Matern
+5/2 ARD context at N = 200, and two isotropic kinds whose features need a second LDS chunk of the
+pair-distance tile (csrc/pair_tile.h): SE at N = 130, d = 40 (a second chunk of 8 features) and
+Matern 3/2 at N = 129, d = 33 (the two-pass gradient, a second chunk of one feature, a last tile
+of one row). One case is one shape under one setting of the environment knobs;
 run each in a process of its own (the knobs are read when a context is created):
 
     python tools/ab_values.py --list-small
@@ -37,7 +40,8 @@ sys.path.insert(0, os.path.join(REPO, 'tests'))  # grad_restatement.make_case, e
 
 # name -> (n, d, kernel kind name, data seed); 65 and 1089 take tests/edge_cases.py's seeds
 SMALL_SHAPES = {'n64': (64, 4, 'KERNEL_ARD', 3064), 'n65': (65, 4, 'KERNEL_ARD', None),
-                'n1089': (1089, 5, 'KERNEL_ARD', None), 'm200': (200, 4, 'KERNEL_M52_ARD', 5200)}
+                'n1089': (1089, 5, 'KERNEL_ARD', None), 'm200': (200, 4, 'KERNEL_M52_ARD', 5200),
+                'iso130': (130, 40, 'KERNEL_ISO', 3170), 'm129': (129, 33, 'KERNEL_M32_ISO', 5162)}
 # the knobs that reach a rare host path: fp64 Newton; fp32 operands; fp64 rerun, then chol(K)
 # again on the main stream; the fp64 bottom block with its gap; attach / rewrite of fp64 slot
 # factors; the reference-route check of every chain (the value tests/test_gpu_configs.py uses)
@@ -88,7 +92,8 @@ def run_small(case, outdir):
     import grad_restatement as gr
     n, d, kind_name, seed = SMALL_SHAPES[shape]
     kind = getattr(_native, kind_name)
-    c = gr.make_case(n, d, 'ard', edge_cases.SEEDS[n] if seed is None else seed)
+    c = gr.make_case(n, d, 'iso' if kind_name.endswith('_ISO') else 'ard',
+                     edge_cases.SEEDS[n] if seed is None else seed)
     X, y, th = c['X'], c['y'], c['thetas']
     B = th.shape[0]
     idx = np.arange(B)
