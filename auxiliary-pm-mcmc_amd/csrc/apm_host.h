@@ -192,10 +192,15 @@ struct __attribute__((visibility("hidden"))) apm_ctx {
     int* hmask = nullptr;  // pinned: the chains of such a recomputation
     int64_t n_post64 = 0;
     // the Newton factorisation's dataflow launches also write the panel's fp16x3 operand planes
-    // (Planes16), which the trailing updates stage with LDS-DMA (two buffers by panel parity: the
-    // lookahead's far update reads panel K's while the dataflow launch of K + 1 writes its own)
+    // (Planes16), which the trailing updates stage with LDS-DMA. plane_bufs buffers of max_batch
+    // chains each, one behind the other: one per outer panel for the left-looking far updates
+    // (far_left: panel q's far tiles take panels 0 .. q-2 in one launch, chol_range32), or two by
+    // panel parity for the right-looking ones (the lookahead's far update reads panel K's while
+    // the dataflow launch of K + 1 writes its own): APM_FAR_LEFT=0, or the allocation failed
     unsigned short* planes = nullptr;
     int64_t plane_cs = 0;  // halves per chain and buffer
+    int plane_bufs = 2;
+    bool far_left = false;
     // explicit-inverse panels (chol32_panel.hip k_zinv_* / k_panel_inv_gemm32): the dataflow launch
     // walks the diagonal block and the right-hand-side row only; Z = inv(L_D) per chain (fp32
     // scratch zt: Z, Z^T, T^T; fp16x3 planes zplanes) and one GEMM per row tile below

@@ -165,10 +165,12 @@ void launch_chol_update32_t128(MatF A, int k0, int kc, const unsigned* tiles, in
                                int role = UPD32_NEWTON, Planes16 pl = Planes16{nullptr, 0, 0, 0});
 // the far trailing updates of the fp32 factorisations on 256x256 quad tiles: fp16x3 operands
 // from the planes only, rows below the appended right-hand side, chains with h3ok set
-// (role: UPD32_NEWTON or UPD32_POST)
+// (role: UPD32_NEWTON or UPD32_POST). npan > 1 (UPD32_NEWTON only): the depth is that of npan
+// consecutive outer panels of kc tiles, pl the first one's planes and the next ones' pstep
+// entries further on each
 void launch_chol_update32_q256(MatF A, int k0, int kc, const unsigned* quads, int nq, Live live,
                                int nchains, hipStream_t s, const int* h3ok, Planes16 pl,
-                               int role = UPD32_NEWTON);
+                               int role = UPD32_NEWTON, int npan = 1, int64_t pstep = 0);
 // the appended right-hand-side row beside the quad tiles, whose lists stop above it: tiles = the
 // super-tiles of row tile rhs alone (build_update_supertiles(rhs, rhs + 1, ..., solo = rhs))
 void launch_rhs_row_update32(MatF A, int k0, int kc, const unsigned* tiles, int ntiles, Live live,

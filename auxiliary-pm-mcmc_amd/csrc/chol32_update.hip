@@ -466,6 +466,11 @@ void launch_chol_update32_t128(MatF A, int k0, int kc, const unsigned* tiles, in
 // the appended right-hand side (the caller launches k_rhs_row_update32 for that row, and
 // k_chol_update32_t128 for any batch with a chain outside fp16's range). Same slices in the same
 // order as k_chol_update32_t128 (h3_mma), so the tiles are bitwise those of the 128-row kernel.
+// npan > 1 (ROLE 0, the left-looking far updates of chol_range32): the depth loop walks the slices
+// of npan consecutive outer panels, kc tiles each, whose planes lie pstep entries apart from pl on
+// (panel 0's slices, then panel 1's, ...) between the one old-tile load and the one store: the
+// sum the tiles receive from npan single-panel launches, in their order, without the npan - 1
+// stores and reloads of fp32 in between (which are exact), so bitwise theirs.
 struct __attribute__((aligned(16))) GemmSmemQ {
     _Float16 q[2][4][256][LPH];  // [buffer][A hi, A lo, B hi, B lo][row][k] (HS layout)
 };
@@ -474,7 +479,8 @@ __global__ __launch_bounds__(512, 1) void k_chol_update32_q256(MatF A, int k0, i
                                                                const unsigned* __restrict__ quads,
                                                                int nq, int nchains, Live live,
                                                                const int* __restrict__ h3ok,
-                                                               Planes16 pl) {
+                                                               Planes16 pl, int npan,
+                                                               int64_t pstep) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, wr = wv >> 2, wc = wv & 3;
     const int r16 = lane & 15, kq = lane >> 4;
     __shared__ GemmSmemQ sm;
@@ -502,16 +508,26 @@ __global__ __launch_bounds__(512, 1) void k_chol_update32_q256(MatF A, int k0, i
     const unsigned short* p1 = P + (int64_t)tb * 64 * 32;
     const int64_t sstep = (int64_t)pl.rows * 32;
     _Float16* lbase = &sm.q[0][arr][128 * half][0];
-    auto dma = [&](int sidx, int buf) {
-        stage_planes(p0 + sidx * sstep, p1 + sidx * sstep, lbase + buf * 4 * 256 * LPH);
+    const int nsub = (64 * kc) / KS128;             // slices per panel
+    const int ntot = ROLE == 0 ? npan * nsub : nsub;
+    // the slices in loop order: `off` is the next one's offset in the planes (uniform), stepping
+    // to the next panel's planes behind a panel's last slice
+    int64_t off = 0;
+    int sin = 0;
+    auto dma = [&](int buf) {
+        stage_planes(p0 + off, p1 + off, lbase + buf * 4 * 256 * LPH);
+        off += sstep;
+        if (ROLE == 0 && ++sin == nsub) {
+            sin = 0;
+            off += pstep - nsub * sstep;
+        }
     };
     auto compute = [&](int cur) {  // this wave's 8 x 4 blocks, a dropped tile's rows left out
         h3_mma<8>(acc, sm.q[cur][0], sm.q[cur][1], sm.q[cur][2], sm.q[cur][3], 128 * wr, 64 * wc,
                   r16, kq, !v0, !v1);
     };
     const bool mine = v0 || v1;
-    const int nsub = (64 * kc) / KS128;
-    dma(0, 0);
+    dma(0);
     // the old tiles, loaded while the first slice is in flight (a dropped tile reads tile (I, J)
     // instead: unconditional loads, since a per-element load-or-not makes hipcc wait for each
     // load in turn)
@@ -532,8 +548,8 @@ __global__ __launch_bounds__(512, 1) void k_chol_update32_q256(MatF A, int k0, i
         for (int bj = 0; bj < 4; ++bj) asm volatile("" : "+v"(acc[bi][bj]));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    for (int s = 0; s < nsub; ++s) {
-        if (s + 1 < nsub) dma(s + 1, (s + 1) & 1);  // lands while slice s is multiplied
+    for (int s = 0; s < ntot; ++s) {
+        if (s + 1 < ntot) dma((s + 1) & 1);  // lands while slice s is multiplied
         if (mine) compute(s & 1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -552,12 +568,15 @@ __global__ __launch_bounds__(512, 1) void k_chol_update32_q256(MatF A, int k0, i
 
 void launch_chol_update32_q256(MatF A, int k0, int kc, const unsigned* quads, int nq, Live live,
                                int nchains, hipStream_t s, const int* h3ok, Planes16 pl,
-                               int role) {
+                               int role, int npan, int64_t pstep) {
     if (nq <= 0 || !pl.base) return;
+    if (npan < 1 || (npan > 1 && (role != UPD32_NEWTON || pstep <= 0)))
+        throw HipError{"launch_chol_update32_q256: a multi-panel depth needs the Newton role "
+                       "and the planes' panel stride"};
     if (role == UPD32_POST)
         APM_LAUNCH(k_chol_update32_q256<1>, dim3((unsigned)((long)nq * nchains)), dim3(512), 0,
-                   s, A, k0, kc, quads, nq, nchains, live, h3ok, pl);
+                   s, A, k0, kc, quads, nq, nchains, live, h3ok, pl, 1, (int64_t)0);
     else
         APM_LAUNCH(k_chol_update32_q256<0>, dim3((unsigned)((long)nq * nchains)), dim3(512), 0,
-                   s, A, k0, kc, quads, nq, nchains, live, h3ok, pl);
+                   s, A, k0, kc, quads, nq, nchains, live, h3ok, pl, npan, pstep);
 }

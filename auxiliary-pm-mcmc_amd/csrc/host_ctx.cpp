@@ -258,7 +258,23 @@ void init_ctx(apm_ctx* c, int device, int kind, const double* X, int64_t n, int6
     c->icm_thr = dalloc<double>(c, B);
     if (c->mixed && c->h3) {
         c->plane_cs = 2 * np * 32 * 2 * c->outer32;  // 2 planes x rows x 2 outer32 slices x 32
-        c->planes = dalloc<unsigned short>(c, 2 * B * c->plane_cs);
+        // a buffer per outer panel for the left-looking far updates (8 of 537 MB at N = 4096 and
+        // 64 chains); without that memory, or with APM_FAR_LEFT=0, the two of the right-looking
+        // schedule. The posterior bottom block borrows the first two (post_planes_of)
+        const int npan = (c->nb + c->outer32 - 1) / c->outer32;
+        const char* fl = getenv("APM_FAR_LEFT");
+        if (npan > 2 && !(fl && atoi(fl) == 0)) {
+            void* p = nullptr;
+            if (hipMalloc(&p, sizeof(unsigned short) * npan * B * c->plane_cs) == hipSuccess) {
+                c->allocs.push_back(p);
+                c->planes = static_cast<unsigned short*>(p);
+                c->plane_bufs = npan;
+                c->far_left = true;
+            } else {
+                (void)hipGetLastError();
+            }
+        }
+        if (!c->planes) c->planes = dalloc<unsigned short>(c, 2 * B * c->plane_cs);
         c->zt = dalloc<float>(c, B * 3 * 512 * 512);
         c->zplanes = dalloc<unsigned short>(c, B * 2 * 16 * 512 * 32);
     }

@@ -28,9 +28,12 @@ void trsv32(apm_ctx* c, bool fwd, MatF F, const float* D, int64_t ds, const doub
         fwd, F, c->nb, D, ds, r, out, c->v.vstride, lv, count, APM_STATUS_CHOL_B,
         spin_ctl(c, true), c->stream);
 }
+// entries between the planes of two outer panels (apm_ctx::plane_bufs buffers: one per panel, or
+// two by panel parity)
+int64_t plane_step(apm_ctx* c) { return (int64_t)c->max_batch * c->plane_cs; }
 Planes16 planes_of(apm_ctx* c, int K) {
     if (!c->planes || !c->h3_now) return Planes16{nullptr, 0, 0, 0};
-    return Planes16{c->planes + ((K / c->outer32) & 1) * c->max_batch * c->plane_cs, c->plane_cs,
+    return Planes16{c->planes + plane_step(c) * ((K / c->outer32) % c->plane_bufs), c->plane_cs,
                     c->plane_cs / 2, c->np};
 }
 float* dinv32_of(apm_ctx* c) { return reinterpret_cast<float*>(c->Dinv); }
@@ -81,12 +84,44 @@ void tracked_update32(apm_ctx* c, MatF M, int k0, int kc, int i0, int R, int j0,
     }
 }
 
+// The left-looking far update of chol_range32 on stream3: the tiles of the outer panel's columns
+// [j0, jend) from their diagonal down to the right-hand-side row take the contributions of the
+// outer panels 0 .. p in one quad-tile launch of depth 64 * outer32 * (p + 1): one load and one
+// store of each tile where the right-looking schedule has p + 1 of each. A panel one tile wide
+// (the last one) takes panel p from the 64x64 kernel behind the others' quad launch, as in the
+// right-looking schedule, whose far update of that column alone is too narrow for the outer
+// kernels: that kernel adds the old tile last, so its tile is not the quad kernel's bit for bit.
+void far_update_left32(apm_ctx* c, MatF M, int p, int j0, int jend, int fail_code, int count) {
+    const int kc = c->outer32, nb = c->nb;
+    const int npan = jend - j0 >= 2 ? p + 1 : p;
+    if (npan > 0) {
+        const auto ql = quad_list(c, j0, nb, j0, jend);
+        const double fl =
+            c->prof ? update_flops(j0, nb, j0, jend, kc * npan, Gap{0, 0}) * c->live_n : 0.0;
+        ProfScope ps(c, APM_PROF_CHOL_UPDATE32, fl, c->stream3);
+        ProfScope ps_outer(c, APM_PROF_CHOL_UPDATE32_OUTER, fl, c->stream3);
+        launch_chol_update32_q256(M, 0, kc, ql.first, ql.second, live_of(c), count, c->stream3,
+                                  c->h3ok, planes_of(c, 0), UPD32_NEWTON, npan, plane_step(c));
+    }
+    if (npan <= p)
+        tracked_update32(c, M, p * kc, kc, j0, nb, j0, jend, count, -1, fail_code, c->stream3,
+                         planes_of(c, p * kc));
+}
+
 // chol_factor's twin for the fp32 Newton matrix: one dataflow launch per outer panel
 // (k_chol_panel_df32: the in-panel steps, fused diagonal tiles), the explicit-inverse panel for
 // the chains invok allows, and the trailing update with a one-panel lookahead (the far part on
-// stream3 beside the next panel's dataflow launch)
+// stream3 beside the next panel's dataflow launch). The far part is left-looking where every
+// chain takes the quad tiles and the batch the explicit-inverse panels (far_update_left32: behind
+// panel p, the columns of panel p + 2 from panels 0 .. p), else right-looking (every column
+// right of panel p + 1 from panel p). Both give the same factor bit for bit: a tile receives the
+// same slices in the same order, and the right-looking schedule's stores and reloads of fp32
+// between the panels are exact.
 void chol_range32(apm_ctx* c, MatF M, int k0, int k1, int R, int Cb, int fail_code, int count) {
     const Live lv = live_of(c);
+    const bool left = c->far_left && c->h3_now && c->h3_all && c->inv_any && c->zt && k0 == 0 &&
+                      k1 == c->nb && Cb == c->nb && R == c->nb + 1 &&
+                      (k1 + c->outer32 - 1) / c->outer32 <= c->plane_bufs;
     float* D = dinv32_of(c);
     const int64_t ds = 2 * c->dstride;
     bool have_diag = false;
@@ -121,10 +156,12 @@ void chol_range32(apm_ctx* c, MatF M, int k0, int k1, int R, int Cb, int fail_co
         const int Knext = std::min(Kend + c->outer32, Cb);
         if (Knext < Cb) {
             // the next panel's columns first (narrow, with the fused diagonal tile), its dataflow
-            // launch next on this stream, and the rest of the trailing update (far: columns >=
-            // Knext) on stream3 beside it. Edge df[p] (main -> s3): panel p's columns, planes and
-            // the previous narrow update are final. The narrow update shares its tiles with the
-            // previous panel's far update: edge far[p-1] (s3 -> main) orders it behind that.
+            // launch next on this stream, and the far update on stream3 beside it (right-looking:
+            // the rest of panel p's trailing update, columns >= Knext; left-looking: the columns
+            // of panel p + 2 from panels 0 .. p). Edge df[p] (main -> s3): panel p's columns,
+            // planes and the previous narrow update are final (and so are the earlier panels').
+            // The narrow update shares its tiles with the previous panel's far update: edge
+            // far[p-1] (s3 -> main) orders it behind that.
             HIPC(hipEventRecord(c->ev.df[p], c->stream));
             if (far_pending >= 0) HIPC(hipStreamWaitEvent(c->stream, c->ev.far[far_pending], 0));
             // (the right-hand-side row's far columns go with the narrow update on this stream)
@@ -132,8 +169,12 @@ void chol_range32(apm_ctx* c, MatF M, int k0, int k1, int R, int Cb, int fail_co
                              have_diag ? Kend : -1, fail_code, nullptr, planes_of(c, K),
                              R > c->nb ? Cb : -1);
             HIPC(hipStreamWaitEvent(c->stream3, c->ev.df[p], 0));
-            tracked_update32(c, M, K, Kend - K, Knext, std::min(R, c->nb), Knext, Cb, count, -1,
-                             fail_code, c->stream3, planes_of(c, K));
+            if (left)
+                far_update_left32(c, M, p, Knext, std::min(Knext + c->outer32, Cb), fail_code,
+                                  count);
+            else
+                tracked_update32(c, M, K, Kend - K, Knext, std::min(R, c->nb), Knext, Cb, count,
+                                 -1, fail_code, c->stream3, planes_of(c, K));
             HIPC(hipEventRecord(c->ev.far[p], c->stream3));
             far_pending = p;
             continue;

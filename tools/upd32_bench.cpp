@@ -5,6 +5,8 @@
 // triangle, the bench's roofline accounting) and an output checksum (variants must match it).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -x hip tools/upd32_bench.cpp -o tools/upd32.bin
 //   tools/upd32.bin [chains=64] [K=0] [reps=10]
+//   tools/upd32.bin far [chains=64] [reps=10]   the far launches of one factorisation at
+//       N = 4096, right-looking against left-looking: ms per launch, their sum, the checksums
 #define APM_TOOL_NO_SKEW
 #include "../auxiliary-pm-mcmc_amd/csrc/chol32_update.hip"
 #include "../auxiliary-pm-mcmc_amd/csrc/tile_lists.cpp"
@@ -33,7 +35,144 @@ static double upd_flops(int i0, int R, int j0, int jend, int kc) {
     return f;
 }
 
+// `far` mode: the far launches (k_chol_update32_q256) of one Newton factorisation, right-looking
+// (behind panel p every column right of panel p + 1, depth one panel) against left-looking
+// (behind panel p the columns of panel p + 2, depth panels 0 .. p), from the same planes. Each
+// schedule runs once from the pristine matrix for its checksum (they must be equal: the same
+// slices meet every tile in the same order), then each launch is timed on its own.
+static int far_mode(int chains, int reps) {
+    const int np = 4096, nb = np / 64, outer = 8, npan = nb / outer, nfar = npan - 2;
+    const int64_t ld = np, cs = (int64_t)np * np;
+    const int64_t pcs = (int64_t)2 * np * 64 * outer, pstep = pcs * chains;
+    float *A, *A0;
+    hipMalloc(&A, sizeof(float) * cs * chains);
+    hipMalloc(&A0, sizeof(float) * cs * chains);
+    std::vector<float> h((size_t)cs);
+    uint64_t lcg = 7;
+    for (int b = 0; b < chains; ++b) {
+        for (int64_t e = 0; e < cs; ++e) {
+            lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
+            h[e] = (float)(((double)(lcg >> 11) * (1.0 / 9007199254740992.0) - 0.5) * 2.0);
+        }
+        hipMemcpy(A0 + b * cs, h.data(), sizeof(float) * cs, hipMemcpyHostToDevice);
+    }
+    int *act, *st, *h3;
+    hipMalloc(&act, 4 * chains);
+    hipMalloc(&st, 4 * chains);
+    hipMalloc(&h3, 4 * chains);
+    std::vector<int> one(chains, 1), zero(chains, 0);
+    hipMemcpy(act, one.data(), 4 * chains, hipMemcpyHostToDevice);
+    hipMemcpy(st, zero.data(), 4 * chains, hipMemcpyHostToDevice);
+    hipMemcpy(h3, one.data(), 4 * chains, hipMemcpyHostToDevice);
+    unsigned short* planes;
+    if (hipMalloc(&planes, sizeof(unsigned short) * pstep * npan) != hipSuccess) {
+        printf("far: no memory for %d panels of planes\n", npan);
+        return 1;
+    }
+    for (int p = 0; p < npan; ++p)
+        hipLaunchKernelGGL(k_fill_planes,
+                           dim3((unsigned)(((int64_t)np * 64 * outer + 255) / 256), chains),
+                           dim3(256), 0, 0, A0, ld, cs, np, p * outer, outer,
+                           Planes16{planes + p * pstep, pcs, pcs / 2, np});
+    const MatF M{A, ld, cs};
+    const Live lv{act, st};
+    unsigned* dq[2][8];
+    int nq[2][8];
+    for (int left = 0; left < 2; ++left)
+        for (int p = 0; p < nfar; ++p) {
+            const int j0 = (p + 2) * outer;
+            const std::vector<unsigned> q =
+                build_update_quads(j0, nb, j0, left ? std::min(j0 + outer, nb) : nb);
+            nq[left][p] = (int)q.size();
+            hipMalloc(&dq[left][p], sizeof(unsigned) * q.size());
+            hipMemcpy(dq[left][p], q.data(), sizeof(unsigned) * q.size(), hipMemcpyHostToDevice);
+        }
+    auto launch = [&](int left, int p) {
+        if (left)
+            launch_chol_update32_q256(M, 0, outer, dq[1][p], nq[1][p], lv, chains, nullptr, h3,
+                                      Planes16{planes, pcs, pcs / 2, np}, UPD32_NEWTON, p + 1,
+                                      pstep);
+        else
+            launch_chol_update32_q256(M, p * outer, outer, dq[0][p], nq[0][p], lv, chains, nullptr,
+                                      h3, Planes16{planes + p * pstep, pcs, pcs / 2, np});
+    };
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0);
+    hipEventCreate(&e1);
+    std::vector<float> out((size_t)cs);
+    unsigned long long hs[2];
+    for (int left = 0; left < 2; ++left) {
+        hipMemcpy(A, A0, sizeof(float) * cs * chains, hipMemcpyDeviceToDevice);
+        for (int p = 0; p < nfar; ++p) launch(left, p);
+        hipDeviceSynchronize();
+        double sum = 0.0;
+        unsigned long long hsh = 1469598103934665603ull;
+        for (int b = 0; b < chains; b += std::max(1, chains / 4)) {
+            hipMemcpy(out.data(), A + b * cs, sizeof(float) * cs, hipMemcpyDeviceToHost);
+            for (int64_t e = 0; e < cs; ++e) {
+                sum += std::fabs((double)out[e]);
+                unsigned u;
+                std::memcpy(&u, &out[e], 4);
+                hsh = (hsh ^ u) * 1099511628211ull;
+            }
+        }
+        hs[left] = hsh;
+        double total = 0.0;
+        printf("%s-looking far launches, %d chains:", left ? "left" : "right", chains);
+        for (int p = 0; p < nfar; ++p) {
+            for (int w = 0; w < 2; ++w) launch(left, p);
+            hipEventRecord(e0, nullptr);
+            for (int r = 0; r < reps; ++r) launch(left, p);
+            hipEventRecord(e1, nullptr);
+            hipEventSynchronize(e1);
+            float ms = 0.f;
+            hipEventElapsedTime(&ms, e0, e1);
+            printf(" %.4f", ms / reps);
+            total += ms / reps;
+        }
+        printf(" ms  sum %.4f ms  checksum %.9e hash %016llx\n", total, sum, hsh);
+    }
+    printf("checksums %s\n", hs[0] == hs[1] ? "equal" : "DIFFER");
+    // the last two left-looking launches on the 128-row kernel instead: its slice loop takes any
+    // depth, so one plane set of (p + 1) * outer tile columns gives it the multi-panel launch's
+    // slices in their order (what a multi-panel loop in k_chol_update32_t128 would run)
+    const int64_t dcs = (int64_t)2 * np * 64 * outer * nfar;
+    unsigned short* deep;
+    if (hipMalloc(&deep, sizeof(unsigned short) * dcs * chains) == hipSuccess) {
+        const FusedDiag<float> fd{0, nullptr, 0, nullptr, 0, 0};
+        for (int p = nfar - 2; p < nfar; ++p) {
+            const int kc = (p + 1) * outer, j0 = (p + 2) * outer;
+            const Planes16 dp{deep, dcs, (int64_t)np * 64 * kc, np};
+            hipLaunchKernelGGL(k_fill_planes,
+                               dim3((unsigned)(((int64_t)np * 64 * kc + 255) / 256), chains),
+                               dim3(256), 0, 0, A0, ld, cs, np, 0, kc, dp);
+            const std::vector<unsigned> sl =
+                build_update_supertiles(j0, nb, j0, std::min(j0 + outer, nb), 0, 0, -1);
+            unsigned* dsl;
+            hipMalloc(&dsl, sizeof(unsigned) * sl.size());
+            hipMemcpy(dsl, sl.data(), sizeof(unsigned) * sl.size(), hipMemcpyHostToDevice);
+            auto l128 = [&]() {
+                launch_chol_update32_t128(M, 0, kc, dsl, (int)sl.size(), lv, chains, nullptr, fd,
+                                          nb, h3, -1, UPD32_NEWTON_PLANES, dp);
+            };
+            for (int w = 0; w < 2; ++w) l128();
+            hipEventRecord(e0, nullptr);
+            for (int r = 0; r < reps; ++r) l128();
+            hipEventRecord(e1, nullptr);
+            hipEventSynchronize(e1);
+            float ms = 0.f;
+            hipEventElapsedTime(&ms, e0, e1);
+            printf("left-looking launch %d on 128-row super-tiles (%zu per chain): %.4f ms\n", p,
+                   sl.size(), ms / reps);
+        }
+    }
+    return hs[0] == hs[1] ? 0 : 2;
+}
+
 int main(int argc, char** argv) {
+    //   tools/upd32.bin far [chains=64] [reps=10]
+    if (argc > 1 && !strcmp(argv[1], "far"))
+        return far_mode(argc > 2 ? atoi(argv[2]) : 64, argc > 3 ? atoi(argv[3]) : 10);
     const int chains = argc > 1 ? atoi(argv[1]) : 64, K = argc > 2 ? atoi(argv[2]) : 0;
     const int reps = argc > 3 ? atoi(argv[3]) : 10;
     // UPD_OUTER: the outer panel width in tiles (8 in the library; 16 measures what 1024-wide
