@@ -84,7 +84,7 @@ class _BatchedChains(object):
 
     def __init__(self, X, y, n_chains, n_imp, prior, kernel='ard', epsilon=1e-8,
                  max_slice_iters=1000, seed=0, estimator='is', device=None, first_chain=0,
-                 likelihood='probit', ep_settings=None):
+                 likelihood='probit', ep_settings=None, bias=False):
         _native.likelihood_code(likelihood)  # ('probit' | 'logit'; ValueError otherwise)
         self.likelihood = likelihood
         self.n_chains = int(n_chains)
@@ -94,6 +94,11 @@ class _BatchedChains(object):
         self.est = _EST[estimator]
         # 'ard' and the four Matern names select their kind; anything else is ISO, as before
         kind = _KERNEL_KINDS.get(kernel, _native.KERNEL_ISO)
+        # bias=True: the constant term exp(theta[-1]) (theta has one more entry; log_prior and
+        # prior_draw give it the length scales' prior unless a subclass says otherwise)
+        self.bias = bool(bias)
+        if self.bias:
+            kind |= _native.COV_BIAS
         C = self.n_chains
         self.ctx = _native.Context(X, y, kind, epsilon, n_imp, max_batch=C, n_slots=2 * C,
                                    n_ubufs=3 * C, device=device, likelihood=likelihood)
@@ -451,10 +456,11 @@ class BatchedAPMEllSSPlusRandDirSliceSampler(_BatchedChains):
 
     def __init__(self, X, y, n_chains, n_imp, prior, kernel='ard', epsilon=1e-8, w=1.,
                  max_steps_out=0, max_slice_iters=1000, seed=0, estimator='is', device=None,
-                 first_chain=0, likelihood='probit', ep_settings=None):
+                 first_chain=0, likelihood='probit', ep_settings=None, bias=False):
         super(BatchedAPMEllSSPlusRandDirSliceSampler, self).__init__(
             X, y, n_chains, n_imp, prior, kernel, epsilon, max_slice_iters, seed, estimator,
-            device, first_chain, likelihood=likelihood, ep_settings=ep_settings)
+            device, first_chain, likelihood=likelihood, ep_settings=ep_settings,
+            bias=bias)
         self.w = float(w)
         self.max_steps_out = int(max_steps_out)
         C = self.n_chains
@@ -823,10 +829,11 @@ class BatchedAPMEllSSPlusMHSampler(_BatchedMHMixin, _BatchedChains):
 
     def __init__(self, X, y, n_chains, n_imp, prior, prop_scales, kernel='ard', epsilon=1e-8,
                  metropolis=False, max_slice_iters=1000, seed=0, estimator='is', device=None,
-                 first_chain=0, likelihood='probit', ep_settings=None):
+                 first_chain=0, likelihood='probit', ep_settings=None, bias=False):
         super(BatchedAPMEllSSPlusMHSampler, self).__init__(
             X, y, n_chains, n_imp, prior, kernel, epsilon, max_slice_iters, seed, estimator,
-            device, first_chain, likelihood=likelihood, ep_settings=ep_settings)
+            device, first_chain, likelihood=likelihood, ep_settings=ep_settings,
+            bias=bias)
         self._init_mh(prop_scales, metropolis)
 
     def _mh_theta(self):
@@ -859,10 +866,11 @@ class BatchedPMMHSampler(_BatchedMHMixin, _BatchedChains):
 
     def __init__(self, X, y, n_chains, n_imp, prior, prop_scales, kernel='iso', epsilon=1e-8,
                  metropolis=False, seed=0, estimator='is', device=None, first_chain=0,
-                 likelihood='probit', ep_settings=None):
+                 likelihood='probit', ep_settings=None, bias=False):
         super(BatchedPMMHSampler, self).__init__(
             X, y, n_chains, n_imp, prior, kernel, epsilon, 1000, seed, estimator, device,
-            first_chain, likelihood=likelihood, ep_settings=ep_settings)
+            first_chain, likelihood=likelihood, ep_settings=ep_settings,
+            bias=bias)
         self._init_mh(prop_scales, metropolis)
 
     def set_estimator(self, estimator):
@@ -928,10 +936,11 @@ class BatchedAPMMetIndPlusSeqSliceSampler(BatchedAPMEllSSPlusRandDirSliceSampler
 
     def __init__(self, X, y, n_chains, n_imp, prior, ws, kernel='ard', epsilon=1e-8,
                  max_steps_out=0, max_slice_iters=1000, seed=0, estimator='is', device=None,
-                 first_chain=0, likelihood='probit', ep_settings=None):
+                 first_chain=0, likelihood='probit', ep_settings=None, bias=False):
         super(BatchedAPMMetIndPlusSeqSliceSampler, self).__init__(
             X, y, n_chains, n_imp, prior, kernel, epsilon, 1., max_steps_out, max_slice_iters,
-            seed, estimator, device, first_chain, likelihood=likelihood, ep_settings=ep_settings)
+            seed, estimator, device, first_chain, likelihood=likelihood, ep_settings=ep_settings,
+            bias=bias)
         self.ws = np.array(np.broadcast_to(np.asarray(ws, dtype=np.float64), (self.P,)))
 
     def _u_update(self, chains=None):
@@ -968,10 +977,11 @@ class BatchedAPMEllSSPlusEllSSSampler(BatchedAPMEllSSPlusRandDirSliceSampler):
 
     def __init__(self, X, y, n_chains, n_imp, theta_prior_std, kernel='ard', epsilon=1e-8,
                  max_slice_iters=1000, seed=0, estimator='is', device=None, first_chain=0,
-                 likelihood='probit', ep_settings=None):
+                 likelihood='probit', ep_settings=None, bias=False):
         super(BatchedAPMEllSSPlusEllSSSampler, self).__init__(
             X, y, n_chains, n_imp, {}, kernel, epsilon, 1., 0, max_slice_iters, seed, estimator,
-            device, first_chain, likelihood=likelihood, ep_settings=ep_settings)
+            device, first_chain, likelihood=likelihood, ep_settings=ep_settings,
+            bias=bias)
         self.theta_prior_std = np.array(np.broadcast_to(
             np.asarray(theta_prior_std, dtype=np.float64), (self.P,)))
         C = self.n_chains

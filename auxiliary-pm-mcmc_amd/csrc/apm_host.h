@@ -241,9 +241,11 @@ struct __attribute__((visibility("hidden"))) apm_ctx {
     bool cholk_partial = false;
     // the predictive path (apm_predict), allocated at its first call: one block of test inputs
     // (np x d), the mu* partials (max_batch x nb x np), the three outputs (max_batch x np each) and
-    // behind them the chains' s = exp(theta_0) as the host computes it (max_batch)
+    // behind them, as the host computes them (max_batch each): the chains' s = exp(theta_0) (psig,
+    // the cross-covariance's), their prior variance k** = s + beta (pkss: s itself without the
+    // constant term) and beta = exp(theta_{P-1}) (pbet: 0 without it)
     double *pxs = nullptr, *ppart = nullptr, *pmean = nullptr, *pvar = nullptr, *pprob = nullptr;
-    double* psig = nullptr;
+    double *psig = nullptr, *pkss = nullptr, *pbet = nullptr;
     // the gradient path (apm_laplace_grad), allocated at its first call: six vectors per chain
     // (dS, g, s2, t = K s2, u = -R t, q; max_batch x np each), the super-tile partials
     // (max_batch x ns (ns + 1) / 2 x P) and the gradients (max_batch x P)
@@ -355,6 +357,11 @@ void upload_h3(apm_ctx* c, int count);
 // the thetas of a call (count x P, row stride ldt) -> pinned staging -> device; returns the
 // staged copy
 const double* upload_thetas(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt);
+// beta = exp(theta_{P-1}) of a biased kind's theta (P entries), 0 for every other kind: with it
+// K_ii = exp(theta_0) + beta + eps and k** = exp(theta_0) + beta
+inline double cov_beta(int kind, int P, const double* theta) {
+    return kernel_kind_of(kind).bias ? std::exp(theta[P - 1]) : 0.0;
+}
 // the identity-padded copy of a host K (n x n, row stride ldk) -> chain 0's K, both triangles
 // (k_full), staged in Kp, which the caller keeps until its next sync; returns max |K_ii|
 double upload_padded_K(apm_ctx* c, const double* K, int64_t ldk, std::vector<double>& Kp);
@@ -445,7 +452,8 @@ int laplace_then_live(apm_ctx* c, int count, double* lml, int* status, int64_t* 
 void predict_buffers(apm_ctx* c);
 void predict_block(apm_ctx* c, int count, int ms);
 // One call's test inputs Xs (m x d, row stride ldxs), a block of at most np rows at a time: the
-// constructor uploads the chains' s = exp(theta_0) to psig (predict_buffers() first), upload()
+// constructor uploads the chains' s = exp(theta_0), s + beta and beta to psig / pkss / pbet
+// (predict_buffers() first; cov_beta), upload()
 // packs rows [r0, r0 + ms) and sends them to pxs (returns ms), rows_back() enqueues the copy of
 // the block's pmean / pvar / pprob rows to the caller's arrays (count x m, row stride ldo, any of
 // them null). The two users copy back differently on purpose: the Laplace / EP predictive every

@@ -216,32 +216,40 @@ void launch_refine(int mode, const double* Ws, const double* Kb, double* x, cons
 //   Matern 5/2  S = s (1 + sqrt5 r + 5/3 r^2) exp(-sqrt5 r)        G = 5/3 s (1 + sqrt5 r) exp(-sqrt5 r)
 // with r^2 = sum_k ((x_ik - x_jk)/tau_k)^2, s = exp(theta_0), tau_k = exp(theta_{k+1}) (ARD) or
 // exp(theta_1) for every k (iso); dK/dtheta_{k+1} = G ((x_ik - x_jk)/tau_k)^2 (gradient.hip).
+// APM_COV_BIAS (16) OR-ed onto one of the six: K = S + beta 1 1^T + eps I on the data pairs, beta =
+// exp of theta's last entry; dK/dtheta_{P-1} = beta on every data pair.
 enum { APM_FAM_SE = 0, APM_FAM_M32 = 1, APM_FAM_M52 = 2 };
 struct KernelKind {
     int family;  // APM_FAM_*, -1: not built on the device
     int iso;     // one length scale (theta has 2 entries) instead of d (d + 1 entries)
+    int bias;    // the constant term: one more theta entry, the last
     bool on_device() const { return family >= 0; }
-    int64_t theta_len(int64_t d) const { return family < 0 ? 0 : (iso ? 2 : d + 1); }
+    int64_t theta_len(int64_t d) const { return family < 0 ? 0 : (iso ? 2 : d + 1) + bias; }
 };
 inline KernelKind kernel_kind_of(int kind) {
-    switch (kind) {
-        case 0: return KernelKind{APM_FAM_SE, 1};   // APM_KERNEL_ISO
-        case 1: return KernelKind{APM_FAM_SE, 0};   // APM_KERNEL_ARD
-        case 3: return KernelKind{APM_FAM_M32, 1};  // APM_KERNEL_M32_ISO
-        case 4: return KernelKind{APM_FAM_M32, 0};  // APM_KERNEL_M32_ARD
-        case 5: return KernelKind{APM_FAM_M52, 1};  // APM_KERNEL_M52_ISO
-        case 6: return KernelKind{APM_FAM_M52, 0};  // APM_KERNEL_M52_ARD
-        default: return KernelKind{-1, 0};          // APM_KERNEL_PRECOMPUTED and unknown values
+    const int bias = (kind & 16) ? 1 : 0;  // APM_COV_BIAS
+    switch (kind & ~16) {
+        case 0: return KernelKind{APM_FAM_SE, 1, bias};   // APM_KERNEL_ISO
+        case 1: return KernelKind{APM_FAM_SE, 0, bias};   // APM_KERNEL_ARD
+        case 3: return KernelKind{APM_FAM_M32, 1, bias};  // APM_KERNEL_M32_ISO
+        case 4: return KernelKind{APM_FAM_M32, 0, bias};  // APM_KERNEL_M32_ARD
+        case 5: return KernelKind{APM_FAM_M52, 1, bias};  // APM_KERNEL_M52_ISO
+        case 6: return KernelKind{APM_FAM_M52, 0, bias};  // APM_KERNEL_M52_ARD
+        // APM_KERNEL_PRECOMPUTED (with or without the flag) and unknown values
+        default: return KernelKind{-1, 0, 0};
     }
 }
-// the launchers' dispatch on the family (a template parameter of k_gram, k_gram_cross and
-// k_grad_reduce: their epilogues differ, everything else is shared)
+// the launchers' dispatch on the family and the constant term (template parameters of k_gram,
+// k_gram_cross and k_grad_reduce: their epilogues differ, everything else is shared)
 #define APM_FAMILY_DISPATCH(family, ...)                                           \
     switch (family) {                                                              \
         case APM_FAM_M32: { constexpr int FAM = APM_FAM_M32; __VA_ARGS__; } break; \
         case APM_FAM_M52: { constexpr int FAM = APM_FAM_M52; __VA_ARGS__; } break; \
         default: { constexpr int FAM = APM_FAM_SE; __VA_ARGS__; } break;           \
     }
+#define APM_BIAS_DISPATCH(bias, ...)                        \
+    if (bias) { constexpr bool BIAS = true; __VA_ARGS__; }  \
+    else { constexpr bool BIAS = false; __VA_ARGS__; }
 #ifdef __HIPCC__
 // the covariance function of the pair's scaled squared distance r2, family FAM
 template <int FAM>
@@ -288,14 +296,18 @@ void launch_gram(MatB K, const double* X, int64_t ldx, int n, int d, const doubl
 // <- sum of k*_rc a_c over the columns of tile column tj (summed in order by k_predict_reduce).
 // plain != 0 (apm_gram_cross): out.base[r * out.ld + c] <- k*_rc for r < ms, c < n, one chain,
 // nothing else is touched (Ws, a, part, live may be null).
+// A biased kind adds bet[b] = exp(theta_{P-1}), the host's as sig[b] is, to every k*_rc with
+// r < ms, c < n (bet is not read otherwise and may be null).
 void launch_gram_cross(MatB out, int64_t row0, const double* Xs, int ms, int mb, const double* X,
                        int64_t ldx, int n, int d, int nb, const double* theta, int64_t tstride,
-                       const double* sig, int kind, const double* Ws, const double* a,
+                       const double* sig, const double* bet, int kind, const double* Ws,
+                       const double* a,
                        int64_t vstride, double* part, int64_t pstride, Live live, int plain,
                        int nchains, hipStream_t s);
 // per chain and test row r < ms: mean = sum_tj part[tj][r] (in order), var = sig[b] - |row r of V^T|^2
 // over columns [0, 64 nb) of A's rows [row0, ..), prob = Phi(mean / sqrt(1 + var)); each output
-// out[b * ostride + r]. Nothing is clamped.
+// out[b * ostride + r]. Nothing is clamped. sig[b] is the prior variance k** here (and in
+// launch_is_rows): s, or s + beta of a biased kind.
 // lik (APM_LIK_*): the logit's prob is the Gauss-Hermite average of sigma (gh_table.h)
 void launch_predict_reduce(int lik, MatB A, int64_t row0, int ms, int mb, int nb,
                            const double* sig, const double* part, int64_t pstride, double* mean,
@@ -320,7 +332,9 @@ void launch_grad_q(const double* s2, const double* u, double* q, int64_t gstride
 // part[b * pstride + t * P + j] <- super-tile t's share of sum_ik M_ik (dK/dtheta_j)_ik with
 // M = 1/2 a a^T + 1/2 Rn + 1/2 (q g^T + g q^T) (Rn = -R, lower tiles) and S from K's lower tiles
 // off the diagonal, exp(theta_0) on it; t over the ns (ns + 1) / 2 lower super-tiles, ns =
-// ceil(nb / 2). launch_grad_sum adds them in tile order into grad[b * P + j].
+// ceil(nb / 2). launch_grad_sum adds them in tile order into grad[b * P + j]. A biased kind's K
+// tiles hold S + beta: its SE instantiation forms S from the pair's own r^2, its Matern ones take
+// K - beta; both write beta sum_ik M_ik as entry P - 1.
 void launch_grad_reduce(MatB K, MatB Rn, const double* X, int64_t ldx, int n, int d, int nb,
                         const double* theta, int64_t tstride, int kind, const double* a,
                         int64_t vstride, const double* q, const double* g, int64_t gstride,

@@ -11,6 +11,7 @@
 //   dK/dtheta_0 = S (K without its jitter: s on the diagonal, not s + epsilon),
 //   dK/dtheta_{k+1} = G_ik ((x_ik - x_jk)/tau_k)^2 (ARD), the sum over k of these (iso); G = S for
 //   the SE family, cov_G (apm_internal.h) for Matern 3/2 and 5/2
+//   dK/dtheta_{P-1} = beta on every data pair (a biased kind, K = S + beta 1 1^T + epsilon I)
 // with W, L, a of the last Newton iteration (latent_posterior_approximations.py:81-106).
 #include "apm_internal.h"
 #include "pair_tile.h"
@@ -140,7 +141,16 @@ void launch_grad_q(const double* s2, const double* u, double* q, int64_t gstride
 // r^2 into w (pair_r2_chunk, k in order), the K / R / vector stage adds c M S into theta_0's sum
 // and overwrites w with c M G (cov_G of the lane's own r^2), the second is the SE pass. Every
 // sum keeps the order above. ard: theta[1 + k] scales feature k, else theta[1] every feature.
-template <int FAM>
+//
+// BIAS (the constant term): K's lower tiles hold S + beta. The SE instantiation
+// takes the two-pass route and forms S = G from the lane's own r^2 (K is not read at all); the
+// Matern ones, which have no registers left for a second exp chain beside w, take theta_0's
+// weight as K - beta, which loses up to u (S + beta) per pair (§22 bounds what that does to the
+// sum). One more sum per super-tile, beta sum c M_ik over the data pairs (dK/dtheta_{P-1} = beta
+// on every pair, the diagonal included): the pairs in the order the stage visits them (SE: a
+// row's 8 pairs, then the 8 row sums; Matern: one running sum over the two runs' rows), the
+// wave's butterfly, the 4 waves in order; it is entry P - 1 of the partials.
+template <int FAM, bool BIAS>
 __global__ __launch_bounds__(256, FAM == APM_FAM_SE ? 1 : 2) void k_grad_reduce(
     MatB K, MatB Rn, const double* __restrict__ X, int64_t ldx, int n, int d, int nb,
     const double* __restrict__ theta, int64_t tstride, int ard, const double* __restrict__ avec,
@@ -163,8 +173,8 @@ __global__ __launch_bounds__(256, FAM == APM_FAM_SE ? 1 : 2) void k_grad_reduce(
     double* pb = part + b * pstride + (int64_t)t * P;
 
     double w[8][8];
-    double s0 = 0.0;
-    if constexpr (FAM != APM_FAM_SE) {  // first pass: w <- the pairs' r^2
+    double s0 = 0.0, sb = 0.0;
+    if constexpr (FAM != APM_FAM_SE || BIAS) {  // first pass: w <- the pairs' r^2
 #pragma unroll
         for (int p = 0; p < 8; ++p)
 #pragma unroll
@@ -180,7 +190,44 @@ __global__ __launch_bounds__(256, FAM == APM_FAM_SE ? 1 : 2) void k_grad_reduce(
         const double* ab = avec + b * vstride;
         const double* qb = qvec + b * gstride;
         const double* gb = gvec + b * gstride;
-        if constexpr (FAM == APM_FAM_SE) {
+        if constexpr (BIAS && FAM == APM_FAM_SE) {
+            // the stage below without K: S = G from the lane's own r^2, and beta's sum beside
+            // theta_0's (a row's 8 pairs in order, then the 8 row sums in order)
+            double ak[8], qk[8], gk[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int gj = tj * 64 + R8(tc, q);
+                ak[q] = ab[gj];
+                qk[q] = qb[gj];
+                gk[q] = gb[gj];
+            }
+            const double* Rt = Rn.base + b * Rn.cstride + tj * 64 + 4 * tc;
+#pragma unroll
+            for (int p = 0; p < 8; ++p) {
+                const int gi = ti * 64 + R8(tr, p);
+                const double* rr = Rt + (int64_t)gi * Rn.ld;
+                const d2_t r0 = *reinterpret_cast<const d2_t*>(rr);
+                const d2_t r1 = *reinterpret_cast<const d2_t*>(rr + 2);
+                const d2_t r2 = *reinterpret_cast<const d2_t*>(rr + 32);
+                const d2_t r3 = *reinterpret_cast<const d2_t*>(rr + 34);
+                const double rv[8] = {r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, r3.x, r3.y};
+                const double ai = ab[gi], qi = qb[gi], gg = gb[gi];
+                double sp = 0.0, spb = 0.0;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const int gj = tj * 64 + R8(tc, q);
+                    const double m = 0.5 * (fma(ai, ak[q], rv[q]) + fma(qi, gk[q], gg * qk[q]));
+                    const double sv = (gi == gj) ? sigma : cov_S<FAM>(sigma, w[p][q]);
+                    const double cnt = (gi > gj) ? 2.0 : 1.0;
+                    const bool in = gi < n && gj <= gi;  // (gj <= gi < n)
+                    w[p][q] = in ? cnt * (m * sv) : 0.0;
+                    sp += w[p][q];
+                    spb += in ? cnt * m : 0.0;
+                }
+                s0 += sp;
+                sb += spb;
+            }
+        } else if constexpr (FAM == APM_FAM_SE) {
             double ak[8], qk[8], gk[8];
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
@@ -242,6 +289,8 @@ __global__ __launch_bounds__(256, FAM == APM_FAM_SE ? 1 : 2) void k_grad_reduce(
             // keeps the instantiation at 248 VGPRs without spills (the compiler otherwise hoists
             // and shares them and spills up to 114 registers).
             int trs = tr, tcs = tc;
+            double beta = 0.0;
+            if constexpr (BIAS) beta = exp(th[P - 1]);
             const double* Kt = K.base + b * K.cstride + tj * 64;
             const double* Rt = Rn.base + b * Rn.cstride + tj * 64;
             double sp[8];
@@ -274,10 +323,12 @@ __global__ __launch_bounds__(256, FAM == APM_FAM_SE ? 1 : 2) void k_grad_reduce(
                     for (int q = 0; q < 4; ++q) {
                         const int gj = tj * 64 + R8(tcs, 4 * h + q);
                         const double m = 0.5 * (fma(ai, ak[q], rv[q]) + fma(qi, gk[q], gg * qk[q]));
-                        const double sv = (gi == gj) ? sigma : kv[q];
+                        double sv = (gi == gj) ? sigma : kv[q];
+                        if constexpr (BIAS) sv = (gi == gj) ? sigma : kv[q] - beta;
                         const double cnt = (gi > gj) ? 2.0 : 1.0;
                         const bool in = gi < n && gj <= gi;  // (gj <= gi < n)
                         sp[p] += in ? cnt * (m * sv) : 0.0;
+                        if constexpr (BIAS) sb += in ? cnt * m : 0.0;
                         w[p][4 * h + q] = in ? cnt * (m * w[p][4 * h + q]) : 0.0;
                     }
                     // (the next rows' loads are not to be hoisted over this row: no room)
@@ -287,13 +338,14 @@ __global__ __launch_bounds__(256, FAM == APM_FAM_SE ? 1 : 2) void k_grad_reduce(
 #pragma unroll
             for (int p = 0; p < 8; ++p) s0 += sp[p];
         }
-    } else if constexpr (FAM == APM_FAM_SE) {  // (a Matern family's w is zero already)
+    } else if constexpr (FAM == APM_FAM_SE && !BIAS) {  // (a two-pass w is zero already)
 #pragma unroll
         for (int p = 0; p < 8; ++p)
 #pragma unroll
             for (int q = 0; q < 8; ++q) w[p][q] = 0.0;
     }
     s0 = wave_sum_d(s0);
+    if constexpr (BIAS) sb = wave_sum_d(sb);
 
     double iso = 0.0;  // (thread 0: the features' sums in order)
     for (int k0 = 0; k0 < d; k0 += GK) {
@@ -330,11 +382,16 @@ __global__ __launch_bounds__(256, FAM == APM_FAM_SE ? 1 : 2) void k_grad_reduce(
         }
     }
     __syncthreads();
-    if (lane == 0) red[wv][0] = s0;
+    if (lane == 0) {
+        red[wv][0] = s0;
+        if constexpr (BIAS) red[wv][1] = sb;
+    }
     __syncthreads();
     if (tid == 0) {
         pb[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
         if (ard == 0) pb[1] = iso;
+        if constexpr (BIAS)
+            pb[P - 1] = exp(th[P - 1]) * (((red[0][1] + red[1][1]) + red[2][1]) + red[3][1]);
     }
 }
 
@@ -345,10 +402,13 @@ void launch_grad_reduce(MatB K, MatB Rn, const double* X, int64_t ldx, int n, in
                         hipStream_t s) {
     const int ns = (nb + 1) / 2;
     const KernelKind kk = kernel_kind_of(kind);
-    APM_FAMILY_DISPATCH(kk.family,
-                        APM_LAUNCH(k_grad_reduce<FAM>, dim3(ns * (ns + 1) / 2, nchains), dim3(256), 0,
-                                   s, K, Rn, X, ldx, n, d, nb, theta, tstride, kk.iso ? 0 : 1, a,
-                                   vstride, q, g, gstride, part, pstride, P, live));
+    APM_FAMILY_DISPATCH(
+        kk.family,
+        APM_BIAS_DISPATCH(kk.bias,
+                          APM_LAUNCH((k_grad_reduce<FAM, BIAS>), dim3(ns * (ns + 1) / 2, nchains),
+                                     dim3(256), 0, s, K, Rn, X, ldx, n, d, nb, theta, tstride,
+                                     kk.iso ? 0 : 1, a, vstride, q, g, gstride, part, pstride, P,
+                                     live)));
 }
 
 // grad[b][p] = the nst super-tile partials of (chain b, parameter p) added in tile order

@@ -27,7 +27,9 @@
 // FAM (APM_FAM_*) selects the epilogue that turns a pair's r^2 into its covariance (cov_S); the
 // distance loop, the LDS staging, the tiling and the stores are the same for every family.
 // ard: theta[1 + k] scales feature k (ARD), else theta[1] scales every feature (iso).
-template <int FAM>
+// BIAS: the constant term: beta = exp of theta's last entry is added to cov_S for
+// the data pairs only, K_ii = (s + beta) + eps; a padded row or column never sees it.
+template <int FAM, bool BIAS>
 __global__ __launch_bounds__(256, 2) void k_gram(MatB K, const double* __restrict__ X, int64_t ldx,
                                                  int n, int d, const double* __restrict__ theta,
                                                  int64_t tstride, int ard, double eps, Live live,
@@ -45,6 +47,8 @@ __global__ __launch_bounds__(256, 2) void k_gram(MatB K, const double* __restric
     const int ro = 64 * (wv >> 1), co = 64 * (wv & 1);
     const double* th = theta + b * tstride;
     const double sigma = exp(th[0]);
+    double beta = 0.0;
+    if constexpr (BIAS) beta = exp(th[ard ? d + 1 : 2]);
 
     double acc[8][8];
 #pragma unroll
@@ -65,7 +69,12 @@ __global__ __launch_bounds__(256, 2) void k_gram(MatB K, const double* __restric
         for (int q = 0; q < 8; ++q) {
             const int gi = ti * 64 + R8(tr, p), gj = tj * 64 + R8(tc, q);
             double val;
-            if (gi < n && gj < n)
+            if constexpr (BIAS) {
+                if (gi < n && gj < n)
+                    val = (gi == gj) ? (sigma + beta) + eps : cov_S<FAM>(sigma, acc[p][q]) + beta;
+                else
+                    val = (gi == gj) ? 1.0 : 0.0;
+            } else if (gi < n && gj < n)
                 val = (gi == gj) ? sigma + eps
                                  : (GRAM_ABL == 1 ? sigma * acc[p][q] : cov_S<FAM>(sigma, acc[p][q]));
             else
@@ -93,8 +102,9 @@ void launch_gram(MatB K, const double* X, int64_t ldx, int n, int d, const doubl
                  hipStream_t s, bool both, MatB K2, int k2cols) {
     const int nb = np / 64, ns = (nb + 1) / 2;
     const KernelKind kk = kernel_kind_of(kind);
-    APM_FAMILY_DISPATCH(kk.family,
-                        APM_LAUNCH(k_gram<FAM>, dim3(ns * (ns + 1) / 2, nchains), dim3(256), 0, s, K,
-                                   X, ldx, n, d, theta, tstride, kk.iso ? 0 : 1, eps, live,
-                                   (int)both, K2, k2cols, nb));
+    APM_FAMILY_DISPATCH(
+        kk.family,
+        APM_BIAS_DISPATCH(kk.bias, APM_LAUNCH((k_gram<FAM, BIAS>), dim3(ns * (ns + 1) / 2, nchains),
+                                              dim3(256), 0, s, K, X, ldx, n, d, theta, tstride,
+                                              kk.iso ? 0 : 1, eps, live, (int)both, K2, k2cols, nb)));
 }

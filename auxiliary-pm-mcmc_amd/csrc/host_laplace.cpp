@@ -84,10 +84,12 @@ void predict_buffers(apm_ctx* c) {
     const int64_t np = c->np, B = c->max_batch;
     c->pxs = dalloc<double>(c, np * std::max(c->d, 1));
     c->ppart = dalloc<double>(c, B * c->nb * np);
-    c->pmean = dalloc<double>(c, 3 * B * np + B);
+    c->pmean = dalloc<double>(c, 3 * B * np + 3 * B);
     c->pvar = c->pmean + B * np;
     c->pprob = c->pvar + B * np;
     c->psig = c->pprob + B * np;
+    c->pkss = c->psig + B;
+    c->pbet = c->pkss + B;
 }
 
 void predict_block(apm_ctx* c, int count, int ms) {
@@ -95,19 +97,24 @@ void predict_block(apm_ctx* c, int count, int ms) {
     const int nb = c->nb, mb = (ms + 63) / 64;
     const int64_t np = c->np;
     launch_gram_cross(c->A, np, c->pxs, ms, mb, c->X, c->d, c->n, c->d, nb, c->theta, c->P,
-                      c->psig, c->kind, c->v.Ws, c->v.a, c->v.vstride, c->ppart, nb * np, lv, 0,
-                      count, c->stream);
+                      c->psig, c->pbet, c->kind, c->v.Ws, c->v.a, c->v.vstride, c->ppart, nb * np,
+                      lv, 0, count, c->stream);
     chol_solve_rows(c, c->A, nb, /*row_start=*/nb, /*R=*/nb + mb, /*Cb=*/nb, count);
-    launch_predict_reduce(c->lik, c->A, np, ms, mb, nb, c->psig, c->ppart, nb * np, c->pmean,
+    launch_predict_reduce(c->lik, c->A, np, ms, mb, nb, c->pkss, c->ppart, nb * np, c->pmean,
                           c->pvar, c->pprob, np, lv, count, c->stream);
 }
 
 TestInputs::TestInputs(apm_ctx* c_, int count_, const double* thetas, int64_t ldt,
                        const double* Xs_, int64_t m_, int64_t ldxs_)
-    : c(c_), count(count_), Xs(Xs_), m(m_), ldxs(ldxs_), sig((size_t)count_) {
+    : c(c_), count(count_), Xs(Xs_), m(m_), ldxs(ldxs_), sig((size_t)(3 * c_->max_batch)) {
     predict_buffers(c);
-    for (int b = 0; b < count; ++b) sig[b] = std::exp(thetas[b * ldt]);
-    HIPC(hipMemcpyAsync(c->psig, sig.data(), sizeof(double) * count, hipMemcpyHostToDevice,
+    const int B = c->max_batch;  // [s | s + beta | beta], the layout of psig / pkss / pbet
+    for (int b = 0; b < count; ++b) {
+        sig[b] = std::exp(thetas[b * ldt]);
+        sig[2 * B + b] = cov_beta(c->kind, c->P, thetas + b * ldt);
+        sig[B + b] = sig[b] + sig[2 * B + b];
+    }
+    HIPC(hipMemcpyAsync(c->psig, sig.data(), sizeof(double) * 3 * B, hipMemcpyHostToDevice,
                         c->stream));
 }
 

@@ -5,6 +5,7 @@
 //   k*_c = s exp(-1/2 sum_k ((x*_k - x_ck)/tau_k)^2)   no epsilon: kernels.pyx adds it to the
 //                                                       i == j entries of ONE point set only
 //   mu*  = k*^T a,   v = L^-1 (W^1/2 . k*),   var* = s - v^T v   (prior variance k** = s)
+//   (a biased kind, DESIGN.md §22: k*_c + beta and k** = s + beta)
 //   pi*  = Phi(mu* / sqrt(1 + var*))
 // with W, L, a of the last Newton iteration (latent_posterior_approximations.py:81-112).
 #include "apm_internal.h"
@@ -21,12 +22,15 @@
 // the partial sums of mu* on the column position only: a chain's outputs do not depend on its
 // batch nor a test point's on its block.
 // FAM (APM_FAM_*) selects the epilogue (cov_S), ard the length scales, as in k_gram.
-template <int FAM>
+// BIAS: the constant term beta = bet[b] (the host's exp, as s is) is added to every k* of a test
+// row r < ms and a training column c < n; the prior variance sig[b] that k_predict_reduce and
+// k_is_rows read is then s + beta.
+template <int FAM, bool BIAS>
 __global__ __launch_bounds__(256, 2) void k_gram_cross(
     MatB out, int64_t row0, const double* __restrict__ Xs, int ms, int mb,
     const double* __restrict__ X, int64_t ldx, int n, int d, int nb,
-    const double* __restrict__ theta, int64_t tstride, const double* __restrict__ sig, int ard,
-    const double* __restrict__ Ws, const double* __restrict__ avec, int64_t vstride,
+    const double* __restrict__ theta, int64_t tstride, const double* __restrict__ sig,
+    const double* __restrict__ bet, int ard, const double* __restrict__ Ws, const double* __restrict__ avec, int64_t vstride,
     double* __restrict__ part, int64_t pstride, Live live, int plain) {
     const int b = blockIdx.y;
     if (live.active && !live_chain(live, b)) return;
@@ -41,6 +45,8 @@ __global__ __launch_bounds__(256, 2) void k_gram_cross(
     const int ro = 64 * (wv >> 1), co = 64 * (wv & 1);
     const double* th = theta + b * tstride;
     const double sigma = sig[b];
+    double beta = 0.0;
+    if constexpr (BIAS) beta = bet[b];
 
     double acc[8][8];
 #pragma unroll
@@ -60,7 +66,10 @@ __global__ __launch_bounds__(256, 2) void k_gram_cross(
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             const int gi = ti * 64 + R8(tr, p), gj = tj * 64 + R8(tc, q);
-            acc[p][q] = (gi < ms && gj < n) ? cov_S<FAM>(sigma, acc[p][q]) : 0.0;
+            if constexpr (BIAS)
+                acc[p][q] = (gi < ms && gj < n) ? cov_S<FAM>(sigma, acc[p][q]) + beta : 0.0;
+            else
+                acc[p][q] = (gi < ms && gj < n) ? cov_S<FAM>(sigma, acc[p][q]) : 0.0;
         }
 
     if (plain) {  // apm_gram_cross: k* itself into an ms x n buffer (any ld: scalar stores)
@@ -105,15 +114,17 @@ __global__ __launch_bounds__(256, 2) void k_gram_cross(
 
 void launch_gram_cross(MatB out, int64_t row0, const double* Xs, int ms, int mb, const double* X,
                        int64_t ldx, int n, int d, int nb, const double* theta, int64_t tstride,
-                       const double* sig, int kind, const double* Ws, const double* a,
-                       int64_t vstride, double* part, int64_t pstride, Live live, int plain,
-                       int nchains, hipStream_t s) {
+                       const double* sig, const double* bet, int kind, const double* Ws,
+                       const double* a, int64_t vstride, double* part, int64_t pstride, Live live,
+                       int plain, int nchains, hipStream_t s) {
     const int nsr = (mb + 1) / 2, nsc = (nb + 1) / 2;
     const KernelKind kk = kernel_kind_of(kind);
-    APM_FAMILY_DISPATCH(kk.family,
-                        APM_LAUNCH(k_gram_cross<FAM>, dim3(nsr * nsc, nchains), dim3(256), 0, s, out,
-                                   row0, Xs, ms, mb, X, ldx, n, d, nb, theta, tstride, sig,
-                                   kk.iso ? 0 : 1, Ws, a, vstride, part, pstride, live, plain));
+    APM_FAMILY_DISPATCH(
+        kk.family,
+        APM_BIAS_DISPATCH(kk.bias, APM_LAUNCH((k_gram_cross<FAM, BIAS>), dim3(nsr * nsc, nchains),
+                                              dim3(256), 0, s, out, row0, Xs, ms, mb, X, ldx, n, d,
+                                              nb, theta, tstride, sig, bet, kk.iso ? 0 : 1, Ws, a,
+                                              vstride, part, pstride, live, plain)));
 }
 
 // One wave per (chain, test row): the squared norm of the row of V^T = (W^1/2 . k*)^T L^-T over

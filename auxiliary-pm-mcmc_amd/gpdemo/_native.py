@@ -18,6 +18,15 @@ KERNEL_ISO, KERNEL_ARD, KERNEL_PRECOMPUTED = 0, 1, 2
 KERNEL_M32_ISO, KERNEL_M32_ARD, KERNEL_M52_ISO, KERNEL_M52_ARD = 3, 4, 5, 6
 # the kinds with one length scale (theta has 2 entries; the others' has d + 1)
 _ISO_KINDS = (KERNEL_ISO, KERNEL_M32_ISO, KERNEL_M52_ISO)
+# APM_COV_BIAS: OR-ed onto one of the six device kinds, the constant term beta = exp(theta[-1])
+# (theta has one more entry)
+COV_BIAS = 16
+
+
+def theta_len(kind, d):
+    """Entries of theta that covariance kind `kind` reads at d features."""
+    return (2 if (kind & ~COV_BIAS) in _ISO_KINDS else d + 1) + (1 if kind & COV_BIAS else 0)
+
 EST_IS, EST_PRIORMC, EST_LAPLACE = 0, 1, 2
 EST_IS_EP = 3  # EST_IS with the EP fit's posterior as the importance distribution (probit)
 LIK_PROBIT, LIK_LOGIT = 0, 1
@@ -167,8 +176,7 @@ def gram(kind, K, X, theta, epsilon, device=None):
     X = _f64(X)
     theta = _f64(np.atleast_1d(theta))
     n, d = X.shape
-    need = 2 if kind in _ISO_KINDS else d + 1
-    if theta.shape[0] < need:
+    if theta.shape[0] < theta_len(kind, d):
         # kernels.pyx indexes theta[k+1] / theta[1] with bounds checking -> IndexError
         raise IndexError('Out of bounds on buffer access (axis 0)')
     out = K if (isinstance(K, np.ndarray) and K.dtype == np.float64 and K.flags.c_contiguous
@@ -189,7 +197,7 @@ def gram_cross(kind, X_test, X, theta, device=None):
     n, d = X.shape
     if Xs.ndim != 2 or Xs.shape[1] != d:
         raise ValueError('X_test has shape {0}, expected (m, {1})'.format(Xs.shape, d))
-    if theta.shape[0] < (2 if kind in _ISO_KINDS else d + 1):
+    if theta.shape[0] < theta_len(kind, d):
         raise IndexError('Out of bounds on buffer access (axis 0)')
     Ks = np.empty((Xs.shape[0], n))
     _check(lib.apm_gram_cross(_device(device), kind, _ptr(Xs), Xs.shape[0], _ptr(X), n, d, d,

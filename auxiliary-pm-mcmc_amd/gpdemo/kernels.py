@@ -17,6 +17,11 @@ With ``s = exp(theta[0])``, ``tau_k = exp(theta[k+1])`` (ARD) or ``exp(theta[1])
     Matérn 5/2            s (1 + sqrt(5) r + 5/3 r^2) exp(-sqrt(5) r)
 
 plus ``epsilon`` on the diagonal (one point set's Gram only).
+
+``bias=True`` adds a constant term to any of the six: ``K = S + beta 1 1^T + epsilon I`` with
+``beta = exp(theta[-1])`` one more, last entry of ``theta`` - a N(0, beta) prior on a constant
+offset of the latent function, integrated out. The cross-covariance gains ``beta`` as well and
+the prior variance at a test point is ``s + beta``.
 """
 from . import _native
 
@@ -59,18 +64,22 @@ def diagonal_matern52_kernel(K, X, theta, epsilon=1e-8):
 class SEKernelFunc(object):
     """``kernel_func(K, X, theta)`` for the isotropic ('iso') or ARD ('ard') SE kernel."""
 
-    def __init__(self, kind, epsilon=1e-8):
+    def __init__(self, kind, epsilon=1e-8, bias=False):
         if kind not in ('iso', 'ard'):
             raise ValueError("kind must be 'iso' or 'ard'")
         self.kind = kind
         self.epsilon = float(epsilon)
+        self.bias = bool(bias)
         self.native_kind = _native.KERNEL_ISO if kind == 'iso' else _native.KERNEL_ARD
+        if self.bias:
+            self.native_kind |= _native.COV_BIAS
 
     def __call__(self, K, X, theta):
         _native.gram(self.native_kind, K, X, theta, self.epsilon)
 
     def __repr__(self):
-        return 'SEKernelFunc({0!r}, epsilon={1!r})'.format(self.kind, self.epsilon)
+        return 'SEKernelFunc({0!r}, epsilon={1!r}{2})'.format(self.kind, self.epsilon,
+                                                             ', bias=True' if self.bias else '')
 
 
 _MATERN_KINDS = {'matern32_iso': _native.KERNEL_M32_ISO, 'matern32_ard': _native.KERNEL_M32_ARD,
@@ -83,24 +92,27 @@ class MaternKernelFunc(object):
     is what sends the estimators, ``LaplacePredictor`` and ``LaplaceGradient`` down the device
     path."""
 
-    def __init__(self, kind, epsilon=1e-8):
+    def __init__(self, kind, epsilon=1e-8, bias=False):
         if kind not in _MATERN_KINDS:
             raise ValueError('kind must be one of {0}'.format(sorted(_MATERN_KINDS)))
         self.kind = kind
         self.epsilon = float(epsilon)
-        self.native_kind = _MATERN_KINDS[kind]
+        self.bias = bool(bias)
+        self.native_kind = _MATERN_KINDS[kind] | (_native.COV_BIAS if self.bias else 0)
 
     def __call__(self, K, X, theta):
         _native.gram(self.native_kind, K, X, theta, self.epsilon)
 
     def __repr__(self):
-        return 'MaternKernelFunc({0!r}, epsilon={1!r})'.format(self.kind, self.epsilon)
+        return 'MaternKernelFunc({0!r}, epsilon={1!r}{2})'.format(
+            self.kind, self.epsilon, ', bias=True' if self.bias else '')
 
 
-def make_kernel_func(kind, epsilon=1e-8):
-    """'iso' | 'ard' (SE) or 'matern32_iso' | 'matern32_ard' | 'matern52_iso' | 'matern52_ard'."""
+def make_kernel_func(kind, epsilon=1e-8, bias=False):
+    """'iso' | 'ard' (SE) or 'matern32_iso' | 'matern32_ard' | 'matern52_iso' | 'matern52_ard';
+    bias=True adds the constant term exp(theta[-1]) (theta has one more entry)."""
     if kind in _MATERN_KINDS:
-        return MaternKernelFunc(kind, epsilon)
+        return MaternKernelFunc(kind, epsilon, bias)
     if kind in ('iso', 'ard'):
-        return SEKernelFunc(kind, epsilon)
+        return SEKernelFunc(kind, epsilon, bias)
     raise ValueError("kind must be 'iso', 'ard' or one of {0}".format(sorted(_MATERN_KINDS)))

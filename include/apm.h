@@ -80,6 +80,14 @@ extern "C" {
 #define APM_KERNEL_M32_ARD 4
 #define APM_KERNEL_M52_ISO 5
 #define APM_KERNEL_M52_ARD 6
+/* Constant (bias) term, a flag OR-ed onto one of the six kinds above (kinds 16, 17, 19 .. 22; not
+ * onto APM_KERNEL_PRECOMPUTED): K = S + beta 1 1^T + epsilon I, a N(0, beta) prior on a constant
+ * offset of the latent function, integrated out. theta gains one entry, the last one:
+ * beta = exp(theta[P - 1]) with P = apm_theta_len = the base kind's length + 1. beta is added to
+ * every pair of data points (K_ii = s + beta + epsilon), to the cross-covariance k* (no epsilon)
+ * and to the prior variance k** = s + beta; dK/dtheta_{P-1} = beta on every data pair. Accepted
+ * wherever the base kinds are; gradients have P entries. */
+#define APM_COV_BIAS 16
 
 /* estimators */
 #define APM_EST_IS 0       /* LogMarginalLikelihoodApproxPosteriorISEstimator */

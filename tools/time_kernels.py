@@ -6,8 +6,12 @@ size. Median of `reps` calls after a cold one, as tools/time_grad.py; the spread
 repetitions (max - min) is printed beside every median so that two libraries' rows can be told
 apart from run-to-run noise.
 
+The six kinds are followed by their biased twins (APM_COV_BIAS: the constant term exp(theta[-1])
+with log beta = --log-beta), whose k_grad_reduce is another instantiation.
+
 APM_LIB selects the library, so an older build can be timed with the same tool; kinds it does
-not know (apm_version() < 2: SE only) are left out. Development tool; no threshold is attached."""
+not know (apm_version() < 2: SE only; a library without APM_COV_BIAS refuses the biased kinds at
+apm_create) are left out. Development tool; no threshold is attached."""
 import argparse
 import ctypes
 import json
@@ -26,6 +30,7 @@ KINDS = [('se_iso', _native.KERNEL_ISO, True), ('se_ard', _native.KERNEL_ARD, Fa
          ('matern32_ard', _native.KERNEL_M32_ARD, False),
          ('matern52_iso', _native.KERNEL_M52_ISO, True),
          ('matern52_ard', _native.KERNEL_M52_ARD, False)]
+KINDS += [(name + '+bias', kind | _native.COV_BIAS, iso) for name, kind, iso in KINDS]
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--n', type=int, default=4096)
@@ -34,6 +39,7 @@ ap.add_argument('--batch', type=int, default=8)
 ap.add_argument('--reps', type=int, default=3)
 ap.add_argument('--tol', type=float, default=1e-14, help='Newton tolerance')
 ap.add_argument('--theta0', type=float, default=0.0, help='log signal variance of the thetas')
+ap.add_argument('--log-beta', type=float, default=1.5, help='log beta of the biased kinds')
 ap.add_argument('--kinds', default='', help='comma-separated subset of the kind names')
 ap.add_argument('--json', default='', help='also write the result rows to this file')
 a = ap.parse_args()
@@ -70,10 +76,16 @@ print('library {0} (apm_version {1}), N = {2}, D = {3}, {4} thetas, Newton toler
                                                a.tol, a.reps), flush=True)
 rows = []
 for name, kind, iso in kinds:
-    ctx = _native.Context(X, y, kind, 1e-8, 1, max_batch=a.batch, n_slots=1, n_ubufs=1)
+    try:
+        ctx = _native.Context(X, y, kind, 1e-8, 1, max_batch=a.batch, n_slots=1, n_ubufs=1)
+    except _native.NativeError as e:
+        print('{0:18s} NOT TIMED: {1}'.format(name, e), flush=True)
+        continue
     ctx.set_newton(a.tol, 1000)
     th = np.tile(np.r_[a.theta0, np.full(1 if iso else a.d, np.log(np.sqrt(a.d)))], (a.batch, 1))
-    th += np.random.RandomState(0).normal(scale=0.1, size=th.shape)
+    th += np.random.RandomState(0).normal(scale=0.1, size=th.shape)  # (the base kind's draws)
+    if kind & _native.COV_BIAS:
+        th = np.hstack([th, np.full((a.batch, 1), a.log_beta)])
     t = {'gram': [], 'grad_reduce': [], 'laplace_grad': []}
     for r in range(a.reps + 1):  # rep 0 is cold (tile lists, first launches, lazy buffers)
         ctx.prof_read(_native.PROF_GRAM, reset=True)  # (a reset drops the records of every kind)
@@ -95,7 +107,7 @@ for name, kind, iso in kinds:
             t['laplace_grad'].append(float(ms.value))
     ctx.close()
     if len(t['gram']) < a.reps:
-        print('{0:13s} NOT TIMED: status {1}, iterations {2}, launches gram {3} / k_grad_reduce '
+        print('{0:18s} NOT TIMED: status {1}, iterations {2}, launches gram {3} / k_grad_reduce '
               '{4}'.format(name, st.tolist(), nit.tolist(), n_g, n_r), flush=True)
         continue
     row = {'kind': name, 'iterations': sorted(int(i) for i in nit)}
@@ -103,7 +115,7 @@ for name, kind, iso in kinds:
         row[key + '_ms'] = float(np.median(v))
         row[key + '_spread_ms'] = float(max(v) - min(v))
     rows.append(row)
-    print('{0:13s} gram {1:.3f} ms (spread {2:.3f})  k_grad_reduce {3:.3f} ms (spread {4:.3f})  '
+    print('{0:18s} gram {1:.3f} ms (spread {2:.3f})  k_grad_reduce {3:.3f} ms (spread {4:.3f})  '
           'laplace_grad {5:.2f} ms (spread {6:.2f})  iterations {7}'
           .format(name, row['gram_ms'], row['gram_spread_ms'], row['grad_reduce_ms'],
                   row['grad_reduce_spread_ms'], row['laplace_grad_ms'],
