@@ -218,6 +218,31 @@ class _BatchedChains(object):
             prob[live], ess[live] = p, e
         return prob, ess
 
+    def loo(self):
+        """Leave-one-out predictive densities at the training points from every live chain's
+        current state ``(theta, u)`` (``apm_is_loo``): a dict with ``loo``,
+        ``lpd``, ``ess_loo`` and ``gauss`` (n_chains, n) and ``ess`` (n_chains,), NaN for failed
+        chains. For ``estimator='is'`` and ``'is_ep'`` only.
+
+        The call reads each chain's current slot and U buffer and writes nothing to the sampler's
+        state, so the trajectories are bitwise what they are without it. To compare models, call
+        it after every transition (or every few), append a chain's rows ``loo[c]`` and ``lpd[c]``
+        to per-chain lists, and give the stacked (T, n) arrays to ``gpdemo.loo.combine_loo``
+        (with ``burn`` / ``thin``): the chain-level criterion averages ``exp(-loo)`` over the
+        states, not ``loo`` itself."""
+        if self.est not in (_native.EST_IS, _native.EST_IS_EP):
+            raise ValueError("loo() needs estimator='is' or 'is_ep': the other estimators carry "
+                             'no importance samples of the posterior of f')
+        C, n = self.n_chains, self.ctx.n
+        out = {k: np.full((C, n), np.nan) for k in ('loo', 'lpd', 'ess_loo', 'gauss')}
+        out['ess'] = np.full(C, np.nan)
+        live = np.flatnonzero(~self.failed)
+        if live.size:
+            _, lo, lp, el, ga, es, _ = self.ctx.is_loo(self.slot_cur[live], self.ub_u[live])
+            out['loo'][live], out['lpd'][live], out['ess_loo'][live] = lo, lp, el
+            out['gauss'][live], out['ess'][live] = ga, es
+        return out
+
     def estimate_spread(self, n_rep=16, block=None):
         """How noisy the log-estimate is at every live chain's current theta (DESIGN.md §20,
         ``apm_is_spread``): `n_rep` independent redraws of u against the chain's current cache

@@ -10,6 +10,7 @@
 //   host_ep.cpp       the sweep loop of parallel expectation propagation (ep.hip)
 //   host_is_predict.cpp  the importance-sampling predictive's tail after an IS theta-call
 //   host_is_diag.cpp  block estimates and weight diagnostics of the IS estimate over replicates
+//   host_is_loo.cpp   leave-one-out predictive densities from the IS samples of a cached u-call
 // Everything shared has hidden visibility: the library exports the apm_* functions only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -266,6 +267,10 @@ struct __attribute__((visibility("hidden"))) apm_ctx {
     // ([seeds: max_batch][counters: APM_SPREAD_MAX_BLOCKS x max_batch])
     double* sd_out = nullptr;
     uint64_t* sd_keys = nullptr;
+    // the leave-one-out densities (apm_is_loo), allocated at its first call: log wbar (max_batch x
+    // sp) and ess (max_batch), the sample-tile partials (max_batch x 5 x np x sp/64) and the four
+    // row outputs (4 x max_batch x np)
+    double *loo_w = nullptr, *loo_ess = nullptr, *loo_part = nullptr, *loo_out = nullptr;
 };
 
 namespace apm_host __attribute__((visibility("hidden"))) {
@@ -501,6 +506,15 @@ void is_predict_tail(apm_ctx* c, int count, const double* thetas, int64_t ldt, i
 void is_diag_run(apm_ctx* c, int count, const int64_t* slots, const int64_t* ubufs,
                  const uint64_t* seeds, const uint64_t* counters, int64_t n_rep, int64_t block,
                  double* logf, double* ess, double* wmax, int64_t ldo, int* status);
+
+// ---- host_is_loo.cpp ------------------------------------------------------------------------
+// apm_u_eval's launches on the call's slots and U buffers, then the log-weights, the product with
+// the row-wise epilogue and the finish (is_loo.hip). Arguments are checked by the caller; every
+// output but status may be null: out_logf and ess (count), loo / lpd / ess_loo / gauss (count x n,
+// row stride ldo), NaN for a chain whose slot's theta-call failed.
+void is_loo_run(apm_ctx* c, int count, const int64_t* slots, const int64_t* ubufs,
+                double* out_logf, double* loo, double* lpd, double* ess_loo, double* gauss,
+                int64_t ldo, double* ess, int* status);
 
 // ---- host_ep.cpp ----------------------------------------------------------------------------
 void ep_buffers(apm_ctx* c);

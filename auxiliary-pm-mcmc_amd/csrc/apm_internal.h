@@ -541,6 +541,25 @@ void launch_is_finish(const double* pp, int64_t npr, int nst, int ms, const doub
                       double* mean, double* var, double* prob, int64_t ostride, Live live,
                       int nchains, hipStream_t s);
 
+// ---- is_loo.hip: leave-one-out predictive densities from the IS samples ------
+// logw[b * sp + s] = log of the self-normalised weight of sample s < S (k_lme's log w_s from
+// `partial`), -inf for s in [S, sp); ess[b] = k_is_weights' value; chains with status != 0 skipped
+void launch_is_logw(const double* partial, int64_t pstride, int nb, int S, int sp,
+                    const double* cst, const int64_t* slots, double* logw, double* ess,
+                    const int* status, int nchains, hipStream_t s);
+// per (chain, row block, sample tile): C_chol U as launch_ugemm forms it (wide: the f64 twin for
+// the call's wide slots too), f = f_post + acc, and per row < n the tile's five log-space sums of
+// t = log wbar - log p and t' = log wbar + log p into pp[((b 5 + q) np + row) (sp / 64) + tile],
+// q = 0: max t, 1: sum e^(t - max), 2: sum e^(2 (t - max)), 3: max t', 4: sum e^(t' - max')
+void launch_is_loo_gemm(int lik, SlotSet S, const int64_t* slots, UPool P, const int64_t* ubufs,
+                        const double* y, int n, int np, const double* logw, double* pp,
+                        const int* status, int nchains, bool wide, hipStream_t s);
+// the sample tiles in order -> loo, lpd, ess_loo, and the cavity density gauss from the slot's
+// rowq, W64, z64 and fpost64, at out[q * qstride + b * npr + row], q = 0 .. 3 (row < n)
+void launch_is_loo_finish(int lik, const double* pp, int64_t npr, int nst, int n, SlotSet S,
+                          const int64_t* slots, const double* y, double* out, int64_t qstride,
+                          const int* status, int nchains, hipStream_t s);
+
 // chol(K) retry of the chains with fail[b] == code, unblocked in LAPACK's dpotf2 order (chol.hip,
 // DESIGN.md §3.4): K's lower triangle into A, L in place, per-tile log-diagonal sums into ldet;
 // success clears fail[b]. Returns false (nothing launched) for np > 512.

@@ -393,6 +393,25 @@ int apm_is_spread(apm_ctx* c, int64_t count, const int64_t* slots, const int64_t
                         block, logf, ess, wmax, ldo, status);
 }
 
+// ---- leave-one-out predictive densities from the IS samples (host_is_loo.cpp) -----------------
+int apm_is_loo(apm_ctx* c, int64_t count, const int64_t* slots, const int64_t* ubufs,
+               double* out_logf, double* loo, double* lpd, double* ess_loo, double* gauss,
+               int64_t ldo, double* ess, int* status) {
+    if (!c) return fail(nullptr, APM_E_INVALID, "apm_is_loo: null context");
+    if (count <= 0 || count > c->max_batch)
+        return fail(c, APM_E_INVALID, "apm_is_loo: count outside [1, max_batch]");
+    if (!slots || !ubufs || !status) return fail(c, APM_E_INVALID, "apm_is_loo: bad arguments");
+    if ((loo || lpd || ess_loo || gauss) && ldo < c->n)
+        return fail(c, APM_E_INVALID, "apm_is_loo: ldo < n");
+    if (!check_idx(c, count, slots, c->n_slots, "slot") ||
+        !check_idx(c, count, ubufs, c->n_ubufs, "ubuf"))
+        return APM_E_INVALID;
+    return ctx_call(c, SKEW, [&] {
+        is_loo_run(c, (int)count, slots, ubufs, out_logf, loo, lpd, ess_loo, gauss, ldo, ess,
+                   status);
+    });
+}
+
 // ---- cache-slot lifetimes (samplers.py:563-584: an MH sampler holds the current state's cache
 // and the proposal's at once; on accept the proposal's becomes current and the old one is dropped).
 // Host bookkeeping only: a slot's contents are immutable between theta-calls into it, so a copy

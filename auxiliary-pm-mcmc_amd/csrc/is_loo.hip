@@ -1,0 +1,390 @@
+// Leave-one-out predictive densities at the training points from the importance samples
+// (DESIGN.md §23): the kernels that host_is_loo.cpp runs after the u-path of apm_u_eval.
+//
+// With the samples f_s = f_post + C_chol u_s of a chain's U buffer, their self-normalised weights
+// wbar_s (the summands of the IS estimate, ugemm.hip's log w_s) and p_si = p(y_i | f_si):
+//   loo_i     = -log sum_s wbar_s / p_si         (p(y_i | y_-i) = 1 / E[1 / p(y_i | f_i) | y])
+//   lpd_i     =  log sum_s wbar_s p_si
+//   ess_loo_i = (sum_s rho_si)^2 / sum_s rho_si^2,  rho_si = wbar_s / p_si
+// The product is the u-path's own (k_ugemm / k_ugemm64), reduced the other way round: over the
+// samples per row, once the weights are known. Every sum over s is a (max, scaled sum) pair in log
+// space: 1 / p_si reaches 1e300 for a badly fitted sample, and log wbar_s = -inf (a padded column,
+// a weight that underflowed) adds exactly nothing.
+#include "apm_internal.h"
+#include "gh_logit.h"
+#include "tile64.h"
+
+// e^(t - m), exactly 0 for t = -inf whatever m is (m = -inf too where every t is)
+__device__ __forceinline__ double loo_scaled(double t, double m) {
+    return t == -INFINITY ? 0.0 : exp(t - m);
+}
+
+// ------------------------------------------------------------------------------- log weights
+// k_is_weights' sibling: log w_s = cst + sum_i partial[i][s] as k_lme forms it (the row-block
+// entries added in ascending order), log wbar_s = (log w_s - max) - log sum_s e^(log w_s - max)
+// over the S real samples, -inf for the padded columns [S, sp); ess = 1 / sum wbar_s^2 by
+// k_is_weights' own operations in its order (its value bitwise). Failed chains drop out through
+// status, as in k_lme.
+__global__ __launch_bounds__(256) void k_is_logw(const double* __restrict__ partial,
+                                                 int64_t pstride, int nb, int S, int sp,
+                                                 const double* __restrict__ cst,
+                                                 const int64_t* __restrict__ slots,
+                                                 double* __restrict__ logw,
+                                                 double* __restrict__ ess,
+                                                 const int* __restrict__ status) {
+    const int b = blockIdx.x;
+    if (status[b] != 0) return;
+    __shared__ double red[4];
+    const double* pb = partial + b * pstride;
+    double* lw = logw + (int64_t)b * sp;
+    const double c0 = cst[slots[b]];
+    double mx = -INFINITY;
+    for (int s = threadIdx.x; s < S; s += 256) {
+        double v = c0;
+        for (int i = 0; i < nb; ++i) v += pb[(int64_t)i * sp + s];
+        lw[s] = v;
+        mx = fmax(mx, v);
+    }
+    mx = block_max_d(mx, red);
+    double se = 0.0;
+    for (int s = threadIdx.x; s < S; s += 256) se += exp(lw[s] - mx);
+    se = block_sum_d(se, red);
+    const double lse = log(se);
+    double s2 = 0.0;
+    for (int s = threadIdx.x; s < sp; s += 256) {
+        double w = 0.0, l = -INFINITY;
+        if (s < S) {
+            const double d = lw[s] - mx;
+            w = exp(d) / se;
+            l = d - lse;
+        }
+        lw[s] = l;
+        s2 = fma(w, w, s2);
+    }
+    s2 = block_sum_d(s2, red);
+    if (threadIdx.x == 0) ess[b] = 1.0 / s2;
+}
+
+void launch_is_logw(const double* partial, int64_t pstride, int nb, int S, int sp,
+                    const double* cst, const int64_t* slots, double* logw, double* ess,
+                    const int* status, int nchains, hipStream_t s) {
+    APM_LAUNCH(k_is_logw, dim3(nchains), dim3(256), 0, s, partial, pstride, nb, S, sp, cst, slots,
+               logw, ess, status);
+}
+
+// ------------------------------------------------------------------------------- the epilogue
+// On a 64 x 64 tile of f = f_post + C_chol U held as the 2 x 2 blocks of 16 x 16 of an MFMA
+// accumulator (f[bi][bj][r]: tile row 32 wr + 16 bi + ROW(lane, r), tile column 32 wc + 16 bj +
+// (lane & 15)): lp = log p(y | f) as the weights' own epilogue takes it (lik_logp_mixed), t = log
+// wbar - lp, t' = log wbar + lp, and per row over the tile's 64 sample columns
+//   m = max t,  sum e^(t - m),  sum e^(2 (t - m)),  m' = max t',  sum e^(t' - m')
+// in a fixed order: the row's maxima first (a maximum does not depend on the order), then a lane
+// adds its two column blocks, the 16 lanes of a row their sums by butterfly (xor 1, 2, 4, 8), and
+// the two column-waves meet in LDS, where the pairs are rescaled to their common maximum. One
+// store per (row < n, quantity) at pp[(q npr + row) nst + sb]: no atomics.
+struct LooEpi {
+    double v[5][64][2];
+};
+#define LOO_ROW32(l, r) (((l) >> 4) * 4 + (r))  // v_mfma_f32_16x16x4_f32's C/D row
+
+template <int LIK, bool F64MAP>
+__device__ __forceinline__ void loo_epilogue(const double (&f)[2][2][4], int row0, int n,
+                                             const double* __restrict__ y,
+                                             const double* __restrict__ lwt,
+                                             double* __restrict__ pp, int64_t npr, int nst, int sb,
+                                             LooEpi& ep) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wr = w >> 1, wc = w & 1;
+    const int r16 = lane & 15;
+    const double lw0 = lwt[32 * wc + r16], lw1 = lwt[32 * wc + 16 + r16];
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int rl = 32 * wr + 16 * bi + (F64MAP ? F64_CROW(lane, r) : LOO_ROW32(lane, r));
+            const double yr = row0 + rl < n ? y[row0 + rl] : 1.0;
+            const double lp0 = lik_logp_mixed<LIK>(yr * f[bi][0][r]);
+            const double lp1 = lik_logp_mixed<LIK>(yr * f[bi][1][r]);
+            // a sample without weight has no t: -inf whatever its lp is
+            const double t0 = lw0 == -INFINITY ? lw0 : lw0 - lp0;
+            const double t1 = lw1 == -INFINITY ? lw1 : lw1 - lp1;
+            const double u0 = lw0 == -INFINITY ? lw0 : lw0 + lp0;
+            const double u1 = lw1 == -INFINITY ? lw1 : lw1 + lp1;
+            double m = fmax(t0, t1), mu = fmax(u0, u1);
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) {
+                m = fmax(m, __shfl_xor(m, o, 64));
+                mu = fmax(mu, __shfl_xor(mu, o, 64));
+            }
+            const double e0 = loo_scaled(t0, m), e1 = loo_scaled(t1, m);
+            double q0 = e0 + e1;
+            double q1 = e0 * e0 + e1 * e1;
+            double q2 = loo_scaled(u0, mu) + loo_scaled(u1, mu);
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) {
+                q0 += __shfl_xor(q0, o, 64);
+                q1 += __shfl_xor(q1, o, 64);
+                q2 += __shfl_xor(q2, o, 64);
+            }
+            if (r16 == 0) {
+                ep.v[0][rl][wc] = m;
+                ep.v[1][rl][wc] = q0;
+                ep.v[2][rl][wc] = q1;
+                ep.v[3][rl][wc] = mu;
+                ep.v[4][rl][wc] = q2;
+            }
+        }
+    __syncthreads();
+    const int rl = threadIdx.x;
+    if (rl < 64 && row0 + rl < n) {
+        const double m = fmax(ep.v[0][rl][0], ep.v[0][rl][1]);
+        const double a0 = loo_scaled(ep.v[0][rl][0], m), a1 = loo_scaled(ep.v[0][rl][1], m);
+        const double mu = fmax(ep.v[3][rl][0], ep.v[3][rl][1]);
+        const double c0 = loo_scaled(ep.v[3][rl][0], mu), c1 = loo_scaled(ep.v[3][rl][1], mu);
+        const int64_t o = (int64_t)(row0 + rl) * nst + sb, qs = npr * nst;
+        pp[o] = m;
+        pp[o + qs] = ep.v[1][rl][0] * a0 + ep.v[1][rl][1] * a1;
+        pp[o + 2 * qs] = ep.v[2][rl][0] * (a0 * a0) + ep.v[2][rl][1] * (a1 * a1);
+        pp[o + 3 * qs] = mu;
+        pp[o + 4 * qs] = ep.v[4][rl][0] * c0 + ep.v[4][rl][1] * c1;
+    }
+}
+
+// ------------------------------------------------------------------------------- the GEMM
+// One 64 x 64 tile (row block i, sample block sb) of C_chol U per workgroup on
+// v_mfma_f32_16x16x4_f32 from the slot's fp32 factor and the U buffer's fp32 mirror, to the depth
+// (i + 1) 64: k_ugemm's staging (U through two LDS buffers, the A fragments straight from global,
+// the next slice loaded while the current one is multiplied), its XCD-aware order (chain-major,
+// heaviest row block first, sample block fastest) and its accumulation order, so f_s is bitwise
+// the f_s the weights were formed at. The main loop is this kernel's own copy: k_ugemm stays as
+// it is. pp: [chain][quantity 0..4][row < npr][sample tile < nst].
+template <int LIK>
+__global__ __launch_bounds__(256) void k_is_loo_gemm(SlotSet S, const int64_t* __restrict__ slots,
+                                                     UPool P, const int64_t* __restrict__ ubufs,
+                                                     const double* __restrict__ y, int n, int np,
+                                                     const double* __restrict__ logw,
+                                                     double* __restrict__ pp,
+                                                     const int* __restrict__ status, int nsb,
+                                                     int nchains) {
+    const int nb = np / 64;
+    const long total = (long)nb * nsb * nchains;
+    const long slot_id = blockIdx.x, xcd = slot_id & 7, q = total >> 3, rem = total & 7;
+    const long item = nchains < 8 ? slot_id
+                      : (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (slot_id >> 3);
+    const int b = (int)(item / ((long)nb * nsb));
+    const int rest = (int)(item % ((long)nb * nsb));
+    if (status[b] != 0) return;
+    const int i = nb - 1 - rest / nsb;
+    const int sb = rest % nsb;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wr = w >> 1, wc = w & 1;
+    const int r16 = lane & 15, kq = lane >> 4;
+    __shared__ float Ut[2][64][65];
+    __shared__ LooEpi ep;
+
+    const int64_t slot = slots[b];
+    if (S.wide[slot]) return;  // k_is_loo_gemm64
+    const float* L = S.L + slot * S.lstride;
+    const float* U = P.base32 + ubufs[b] * P.stride;
+    const int sp = P.sp;
+    const int kend = (i + 1) * 64;
+
+    f4_t acc[2][2];
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj) acc[bi][bj] = f4_t{0.f, 0.f, 0.f, 0.f};
+
+    f4_t un[4];
+    f4_t an[2][4];
+    auto gload = [&](int kk) {
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int e = tid + h * 256;  // 4-element piece, 16 per U row
+            un[h] = *reinterpret_cast<const f4_t*>(U + (int64_t)(kk + e / 16) * sp + sb * 64 +
+                                                   (e % 16) * 4);
+        }
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi) {
+            const float* p = L + (int64_t)(i * 64 + 32 * wr + 16 * bi + r16) * np + kk + kq * 16;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) an[bi][t] = *reinterpret_cast<const f4_t*>(p + 4 * t);
+        }
+    };
+    gload(0);
+    for (int kk = 0, cur = 0; kk < kend; kk += 64, cur ^= 1) {
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int e = tid + h * 256;
+            const int r = e / 16, c4 = (e % 16) * 4;
+            Ut[cur][r][c4] = un[h][0];
+            Ut[cur][r][c4 + 1] = un[h][1];
+            Ut[cur][r][c4 + 2] = un[h][2];
+            Ut[cur][r][c4 + 3] = un[h][3];
+        }
+        float a[2][16];
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+            for (int t = 0; t < 16; ++t) a[bi][t] = an[bi][t >> 2][t & 3];
+        __syncthreads();
+        if (kk + 64 < kend) gload(kk + 64);
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            float bv[2];
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj) bv[bj] = Ut[cur][kq * 16 + t][32 * wc + 16 * bj + r16];
+#pragma unroll
+            for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+                for (int bj = 0; bj < 2; ++bj)
+                    acc[bi][bj] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[bi][t], bv[bj],
+                                                                       acc[bi][bj], 0, 0, 0);
+        }
+    }
+
+    const double* fp = S.fpost64 + slot * S.vstride;
+    double f[2][2][4];
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double fr = fp[i * 64 + 32 * wr + 16 * bi + LOO_ROW32(lane, r)];
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj) f[bi][bj][r] = fr + (double)acc[bi][bj][r];
+        }
+    loo_epilogue<LIK, false>(f, i * 64, n, y, logw + (int64_t)b * sp + sb * 64,
+                             pp + (int64_t)b * 5 * np * nsb, np, nsb, sb, ep);
+}
+
+// The same product and epilogue on the f64 MFMA for the call's wide slots, from the slot's fp64
+// factor and the fp64 U buffer, staged plainly as k_ugemm64 is (its accumulation order).
+template <int LIK>
+__global__ __launch_bounds__(256) void k_is_loo_gemm64(SlotSet S,
+                                                       const int64_t* __restrict__ slots, UPool P,
+                                                       const int64_t* __restrict__ ubufs,
+                                                       const double* __restrict__ y, int n, int np,
+                                                       const double* __restrict__ logw,
+                                                       double* __restrict__ pp,
+                                                       const int* __restrict__ status, int nsb) {
+    const int b = blockIdx.y;
+    if (status[b] != 0) return;
+    const int64_t slot = slots[b];
+    if (!S.wide[slot]) return;
+    const int i = (int)blockIdx.x / nsb, sb = (int)blockIdx.x % nsb;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wr = w >> 1, wc = w & 1;
+    const int r16 = lane & 15, kq = lane >> 4;
+    __shared__ double La[64][17];
+    __shared__ double Ub[16][65];
+    __shared__ LooEpi ep;
+    const double* L = S.L64[slot];
+    if (!L) return;  // (as k_ugemm64; a slot read by a u-call has its buffer attached)
+    const double* U = P.base + ubufs[b] * P.stride;
+    const int sp = P.sp;
+    d4_t acc[2][2];
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj) acc[bi][bj] = d4_t{0.0, 0.0, 0.0, 0.0};
+    const int kend = (i + 1) * 64;
+    for (int kk = 0; kk < kend; kk += 16) {
+        for (int e = tid; e < 64 * 16; e += 256) {
+            const int r = e >> 4, c = e & 15;
+            La[r][c] = L[(int64_t)(i * 64 + r) * np + kk + c];
+            Ub[e >> 6][e & 63] = U[(int64_t)(kk + (e >> 6)) * sp + sb * 64 + (e & 63)];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+#pragma unroll
+            for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+                for (int bj = 0; bj < 2; ++bj)
+                    acc[bi][bj] = __builtin_amdgcn_mfma_f64_16x16x4f64(
+                        La[32 * wr + 16 * bi + r16][4 * t + kq],
+                        Ub[4 * t + kq][32 * wc + 16 * bj + r16], acc[bi][bj], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    const double* fp = S.fpost64 + slot * S.vstride;
+    double f[2][2][4];
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double fr = fp[i * 64 + 32 * wr + 16 * bi + F64_CROW(lane, r)];
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj) f[bi][bj][r] = fr + acc[bi][bj][r];
+        }
+    loo_epilogue<LIK, true>(f, i * 64, n, y, logw + (int64_t)b * sp + sb * 64,
+                            pp + (int64_t)b * 5 * np * nsb, np, nsb, sb, ep);
+}
+
+void launch_is_loo_gemm(int lik, SlotSet S, const int64_t* slots, UPool P, const int64_t* ubufs,
+                        const double* y, int n, int np, const double* logw, double* pp,
+                        const int* status, int nchains, bool wide, hipStream_t s) {
+    const int nb = np / 64, nsb = P.sp / 64;
+    const long total = (long)nb * nsb * nchains;
+    APM_LIK_DISPATCH(lik, APM_LAUNCH(k_is_loo_gemm<LIK>, dim3((unsigned)total), dim3(256), 0, s, S,
+                                     slots, P, ubufs, y, n, np, logw, pp, status, nsb, nchains));
+    if (wide)
+        APM_LIK_DISPATCH(lik, APM_LAUNCH(k_is_loo_gemm64<LIK>, dim3((unsigned)(nb * nsb), nchains),
+                                         dim3(256), 0, s, S, slots, P, ubufs, y, n, np, logw, pp,
+                                         status, nsb));
+}
+
+// ------------------------------------------------------------------------------- finish
+// Per (chain, row i < n): the sample tiles' pairs merged in ascending order into
+//   loo = -(m + log s),  lpd = m' + log s',  ess_loo = s^2 / s2,
+// and the Gaussian (cavity) leave-one-out density of the slot's N(f_post, C), site i removed:
+//   tau = 1 / C_ii - W_i,  nu = f_post_i / C_ii - z_i,  C_ii = rowq_i,
+//   gauss = log int p(y_i | f) N(f | nu / tau, 1 / tau) df
+// (probit: log Phi(y m / sqrt(1 + v)); logit: the log of the Gauss-Hermite average, gh_logit.h);
+// a computed tau <= 0 gives NaN for that point's gauss only. out: [quantity 0..3][chain][npr].
+template <int LIK>
+__global__ __launch_bounds__(256) void k_is_loo_finish(const double* __restrict__ pp, int64_t npr,
+                                                       int nst, int n, SlotSet S,
+                                                       const int64_t* __restrict__ slots,
+                                                       const double* __restrict__ y,
+                                                       double* __restrict__ out, int64_t qstride,
+                                                       const int* __restrict__ status) {
+    const int b = blockIdx.y;
+    if (status[b] != 0) return;
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= n) return;
+    const int64_t qs = npr * nst;
+    const double* p = pp + (int64_t)b * 5 * qs + (int64_t)r * nst;
+    double m = -INFINITY, s = 0.0, s2 = 0.0, mu = -INFINITY, su = 0.0;
+    for (int t = 0; t < nst; ++t) {
+        const double mt = p[t], nm = fmax(m, mt);
+        const double a = loo_scaled(m, nm), c = loo_scaled(mt, nm);
+        s = s * a + p[t + qs] * c;
+        s2 = s2 * (a * a) + p[t + 2 * qs] * (c * c);
+        m = nm;
+        const double ut = p[t + 3 * qs], nu = fmax(mu, ut);
+        su = su * loo_scaled(mu, nu) + p[t + 4 * qs] * loo_scaled(ut, nu);
+        mu = nu;
+    }
+    double* o = out + b * npr + r;
+    o[0] = -(m + log(s));
+    o[qstride] = mu + log(su);
+    o[2 * qstride] = s * s / s2;
+
+    const int64_t so = slots[b] * S.vstride + r;
+    const double cii = S.rowq[so];
+    const double tau = 1.0 / cii - S.W64[so];
+    const double nu = S.fpost64[so] / cii - S.z64[so];
+    double g = NAN;
+    if (tau > 0.0) {
+        const double mc = y[r] * (nu / tau), vc = 1.0 / tau;
+        if constexpr (LIK == APM_LIK_LOGIT) g = log(gh_logit_avg(mc, vc));
+        else g = log_ndtr_d(mc / sqrt(1.0 + vc));
+    }
+    o[3 * qstride] = g;
+}
+
+void launch_is_loo_finish(int lik, const double* pp, int64_t npr, int nst, int n, SlotSet S,
+                          const int64_t* slots, const double* y, double* out, int64_t qstride,
+                          const int* status, int nchains, hipStream_t s) {
+    APM_LIK_DISPATCH(lik, APM_LAUNCH(k_is_loo_finish<LIK>, dim3((n + 255) / 256, nchains),
+                                     dim3(256), 0, s, pp, npr, nst, n, S, slots, y, out, qstride,
+                                     status));
+}

@@ -77,6 +77,7 @@ _SIGS = {
     'apm_u_eval': (_i, [_p, _i64, _p, _p, _p, _p]),
     'apm_u_eval_diag': (_i, [_p, _i64, _p, _p, _i64, _p, _p, _p, _i64, _p]),
     'apm_is_spread': (_i, [_p, _i64, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _i64, _p]),
+    'apm_is_loo': (_i, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p]),
     'apm_slot_read': (_i, [_p, _i64, _p, _i64, _p, _p, _p]),
     'apm_cache_acquire': (_i, [_p, _p]),
     'apm_cache_copy': (_i, [_p, _i64]),
@@ -577,6 +578,27 @@ class Context(object):
                                       n_rep, block, _ptr(logf), _ptr(ess), _ptr(wmax),
                                       n_rep * nblk, _ptr(st)), self._h)
         return logf, ess, wmax, st
+
+    def is_loo(self, slots, ubufs):
+        """Leave-one-out predictive densities at the training points from the importance samples
+        of the cached u-call of :meth:`u_eval`: ``(logf, loo, lpd, ess_loo, gauss, ess, status)``,
+        logf (u_eval's value bitwise) and ess (count,), the others (count, n): the exact
+        ``log p(y_i | y_-i, theta)`` estimate, the in-sample density, the ESS of the LOO ratio and
+        the Gaussian (cavity) LOO of the slot's approximation; NaN for a chain whose slot's last
+        theta-call failed (include/apm.h apm_is_loo). Slots and U buffers are only read."""
+        sl = np.ascontiguousarray(slots, dtype=np.int64)
+        ub = np.ascontiguousarray(ubufs, dtype=np.int64)
+        if sl.ndim != 1 or ub.shape != sl.shape or not 1 <= sl.shape[0] <= self.max_batch:
+            raise ValueError('one U buffer per slot, between 1 and max_batch = {0} chains'
+                             .format(self.max_batch))
+        count, n = sl.shape[0], self.n
+        logf, ess = np.full(count, np.nan), np.full(count, np.nan)
+        loo, lpd, ess_loo, gauss = (np.full((count, n), np.nan) for _ in range(4))
+        st = np.zeros(count, dtype=np.int32)
+        _check(self.lib.apm_is_loo(self._h, count, _ptr(sl), _ptr(ub), _ptr(logf), _ptr(loo),
+                                   _ptr(lpd), _ptr(ess_loo), _ptr(gauss), n, _ptr(ess), _ptr(st)),
+               self._h)
+        return logf, loo, lpd, ess_loo, gauss, ess, st
 
     def slot_read(self, slot):
         L = np.zeros((self.n, self.n))

@@ -332,6 +332,38 @@ int apm_u_eval_diag(apm_ctx *ctx, int64_t count, const int64_t *slots, const int
 int apm_is_spread(apm_ctx *ctx, int64_t count, const int64_t *slots, const int64_t *ubufs,
                   const uint64_t *seeds, const uint64_t *counters, int64_t n_rep, int64_t block,
                   double *logf, double *ess, double *wmax, int64_t ldo, int *status);
+/* ---- leave-one-out predictive densities from the IS samples (no reference counterpart;
+ * DESIGN.md §23) -------------------------------------------------------------------------------
+ * For one chain, with slot state (f_post, W, z = C^-1 f_post, the factor C_chol and its squared row
+ * norms C_ii) and a U buffer of S = n_imp real columns: f_si = f_post_i + (C_chol U)_is are the
+ * importance samples, wbar_s their self-normalised weights (log w_s the summand of the estimate
+ * exactly as apm_u_eval forms it; padded columns weigh exactly 0) and p_si = p(y_i | f_si) the
+ * context's likelihood, the same function of the same f_si as in the weights. Per training point
+ * i < n:
+ *   loo_i     = -log sum_s wbar_s / p_si     (log p(y_i | y_-i): 1 / E[1 / p(y_i | f_i) | y])
+ *   lpd_i     =  log sum_s wbar_s p_si       (the in-sample density; lpd_i >= loo_i)
+ *   ess_loo_i = (sum_s rho_si)^2 / sum_s rho_si^2, rho_si = wbar_s / p_si   (in [1, n_imp])
+ *   gauss_i   = log int p(y_i | f) N(f | nu / tau, 1 / tau) df,
+ *               tau = 1 / C_ii - W_i, nu = f_post_i / C_ii - z_i
+ * and per chain ess = 1 / sum_s wbar_s^2. gauss is the Gaussian (cavity) leave-one-out density of
+ * the slot's N(f_post, C) with site i removed (EP's own cavity for an APM_EST_IS_EP slot; probit:
+ * log Phi(y_i m / sqrt(1 + v)), logit: the log of the Gauss-Hermite average of apm_predict); a
+ * computed tau <= 0 gives NaN for that point's gauss only. All sums over s are formed in log
+ * space. Averaged over the states (theta, u) of a pseudo-marginal chain, exp(-loo_i) and
+ * exp(lpd_i) estimate E[1 / p(y_i | f_i) | y] and E[p(y_i | f_i) | y]: no Gaussian approximation
+ * of p(f | theta, y) is left in them.
+ * apm_u_eval (the same checks, launches and status: out_logf is bitwise its value) followed by
+ * the tail; chain i's rows are at [i ldo], n values each. Any output pointer except status may be
+ * NULL. APM_E_INVALID, with nothing written, for count outside [1, max_batch], null slots / ubufs
+ * / status, indices out of range and ldo < n with any row output non-NULL. A chain whose slot's
+ * last theta-call failed gets apm_u_eval's status and NaN in every output. Works for slots written
+ * by APM_EST_IS, APM_EST_IS_EP and APM_EST_PRIORMC (W = z = 0: loo is the prior-proposal
+ * estimate, gauss the prior predictive) under both likelihoods. A chain's outputs do not depend on
+ * its position in the batch nor on the other chains. Slots and U buffers are only read.
+ * apm_version() is unchanged: detect the entry point by its symbol. */
+int apm_is_loo(apm_ctx *ctx, int64_t count, const int64_t *slots, const int64_t *ubufs,
+               double *out_logf, double *loo, double *lpd, double *ess_loo, double *gauss,
+               int64_t ldo, double *ess, int *status);
 /* cache-slot lifetimes (samplers.py:563-584: an MH sampler keeps the current state's cache and the
  * proposal's alive at once). acquire: a free slot, one owner (APM_E_NOMEM when all are owned);
  * copy: one more owner of the same (immutable) state - the handle copy of the reference's tuple;
