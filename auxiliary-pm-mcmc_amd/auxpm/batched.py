@@ -218,7 +218,7 @@ class _BatchedChains(object):
             prob[live], ess[live] = p, e
         return prob, ess
 
-    def loo(self):
+    def loo(self, psis=False):
         """Leave-one-out predictive densities at the training points from every live chain's
         current state ``(theta, u)`` (``apm_is_loo``): a dict with ``loo``,
         ``lpd``, ``ess_loo`` and ``gauss`` (n_chains, n) and ``ess`` (n_chains,), NaN for failed
@@ -229,18 +229,30 @@ class _BatchedChains(object):
         it after every transition (or every few), append a chain's rows ``loo[c]`` and ``lpd[c]``
         to per-chain lists, and give the stacked (T, n) arrays to ``gpdemo.loo.combine_loo``
         (with ``burn`` / ``thin``): the chain-level criterion averages ``exp(-loo)`` over the
-        states, not ``loo`` itself."""
+        states, not ``loo`` itself.
+
+        With ``psis=True`` the dict gains ``loo_psis`` and ``khat`` (n_chains, n) and ``khat_w``
+        (n_chains,) from ``apm_is_loo_psis``: the Pareto-smoothed densities, the
+        Pareto shape of each point's importance ratios and that of the weights. Give
+        ``combine_loo`` the stacked ``khat`` rows too; it reports the points whose mean shape
+        exceeds 0.7. That call only reads as well."""
         if self.est not in (_native.EST_IS, _native.EST_IS_EP):
             raise ValueError("loo() needs estimator='is' or 'is_ep': the other estimators carry "
                              'no importance samples of the posterior of f')
         C, n = self.n_chains, self.ctx.n
         out = {k: np.full((C, n), np.nan) for k in ('loo', 'lpd', 'ess_loo', 'gauss')}
         out['ess'] = np.full(C, np.nan)
+        if psis:
+            out.update(loo_psis=np.full((C, n), np.nan), khat=np.full((C, n), np.nan),
+                       khat_w=np.full(C, np.nan))
         live = np.flatnonzero(~self.failed)
         if live.size:
             _, lo, lp, el, ga, es, _ = self.ctx.is_loo(self.slot_cur[live], self.ub_u[live])
             out['loo'][live], out['lpd'][live], out['ess_loo'][live] = lo, lp, el
             out['gauss'][live], out['ess'][live] = ga, es
+            if psis:
+                _, ps, kh, kw, _, _ = self.ctx.is_loo_psis(self.slot_cur[live], self.ub_u[live])
+                out['loo_psis'][live], out['khat'][live], out['khat_w'][live] = ps, kh, kw
         return out
 
     def estimate_spread(self, n_rep=16, block=None):

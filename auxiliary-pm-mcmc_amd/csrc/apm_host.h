@@ -11,6 +11,7 @@
 //   host_is_predict.cpp  the importance-sampling predictive's tail after an IS theta-call
 //   host_is_diag.cpp  block estimates and weight diagnostics of the IS estimate over replicates
 //   host_is_loo.cpp   leave-one-out predictive densities from the IS samples of a cached u-call
+//   host_is_psis.cpp  their Pareto-smoothed form and the Pareto k-hat of the ratios' tails
 // Everything shared has hidden visibility: the library exports the apm_* functions only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -271,6 +272,11 @@ struct __attribute__((visibility("hidden"))) apm_ctx {
     // sp) and ess (max_batch), the sample-tile partials (max_batch x 5 x np x sp/64) and the four
     // row outputs (4 x max_batch x np)
     double *loo_w = nullptr, *loo_ess = nullptr, *loo_part = nullptr, *loo_out = nullptr;
+    // the Pareto-smoothed densities (apm_is_loo_psis), one allocation at its first call (psis_t is
+    // its base and the sign that it exists): the log ratios (max_batch x np x sp), log wbar
+    // (max_batch x sp) and k_is_logw's ess (max_batch), and the outputs (loo_psis and khat:
+    // 2 x max_batch x np; khat_w: max_batch)
+    double *psis_w = nullptr, *psis_t = nullptr, *psis_out = nullptr;
 };
 
 namespace apm_host __attribute__((visibility("hidden"))) {
@@ -515,6 +521,16 @@ void is_diag_run(apm_ctx* c, int count, const int64_t* slots, const int64_t* ubu
 void is_loo_run(apm_ctx* c, int count, const int64_t* slots, const int64_t* ubufs,
                 double* out_logf, double* loo, double* lpd, double* ess_loo, double* gauss,
                 int64_t ldo, double* ess, int* status);
+
+// ---- host_is_psis.cpp -----------------------------------------------------------------------
+// apm_u_eval's launches on the call's slots and U buffers, then the log-weights, the product with
+// the storing epilogue and the row fits (is_psis.hip). Arguments are checked by the caller; every
+// output but status may be null: out_logf and khat_w (count), loo_psis / khat (count x n, row
+// stride ldo), logratio (count x n n_imp, row stride ldr), NaN for a chain whose slot's theta-call
+// failed.
+void is_psis_run(apm_ctx* c, int count, const int64_t* slots, const int64_t* ubufs,
+                 double* out_logf, double* loo_psis, double* khat, int64_t ldo, double* khat_w,
+                 double* logratio, int64_t ldr, int* status);
 
 // ---- host_ep.cpp ----------------------------------------------------------------------------
 void ep_buffers(apm_ctx* c);

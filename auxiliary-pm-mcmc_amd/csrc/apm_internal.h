@@ -560,6 +560,19 @@ void launch_is_loo_finish(int lik, const double* pp, int64_t npr, int nst, int n
                           const int64_t* slots, const double* y, double* out, int64_t qstride,
                           const int* status, int nchains, hipStream_t s);
 
+// ---- is_psis.hip: Pareto-smoothed leave-one-out densities and k-hat ----------
+// launch_is_loo_gemm's product with a storing epilogue: T[(b np + row) sp + s] = log wbar_s -
+// log p(y_row | f_row,s) for row < n (-inf where log wbar_s is), rows [n, np) left alone
+void launch_psis_gemm(int lik, SlotSet S, const int64_t* slots, UPool P, const int64_t* ubufs,
+                      const double* y, int n, int np, const double* logw, double* T,
+                      const int* status, int nchains, bool wide, hipStream_t s);
+// per (chain, row < n) of T (chain stride tstride, row stride sp, the first S columns): the tail
+// fit and the smoothed sum into out[b npr + row] (loo_psis) and out[qstride + b npr + row] (khat);
+// per chain the fit on logw[b sp ..] into khat_w[b]. S <= APM_PSIS_MAX_SAMPLES.
+void launch_psis_rows(const double* T, int64_t tstride, int sp, const double* logw, int S, int n,
+                      double* out, int64_t npr, int64_t qstride, double* khat_w,
+                      const int* status, int nchains, hipStream_t s);
+
 // chol(K) retry of the chains with fail[b] == code, unblocked in LAPACK's dpotf2 order (chol.hip,
 // DESIGN.md §3.4): K's lower triangle into A, L in place, per-tile log-diagonal sums into ldet;
 // success clears fail[b]. Returns false (nothing launched) for np > 512.

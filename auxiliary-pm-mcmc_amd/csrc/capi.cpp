@@ -412,6 +412,30 @@ int apm_is_loo(apm_ctx* c, int64_t count, const int64_t* slots, const int64_t* u
     });
 }
 
+// ---- their Pareto-smoothed form and the Pareto k-hat diagnostics (host_is_psis.cpp) ------------
+int apm_is_loo_psis(apm_ctx* c, int64_t count, const int64_t* slots, const int64_t* ubufs,
+                    double* out_logf, double* loo_psis, double* khat, int64_t ldo, double* khat_w,
+                    double* logratio, int64_t ldr, int* status) {
+    if (!c) return fail(nullptr, APM_E_INVALID, "apm_is_loo_psis: null context");
+    if (count <= 0 || count > c->max_batch)
+        return fail(c, APM_E_INVALID, "apm_is_loo_psis: count outside [1, max_batch]");
+    if (!slots || !ubufs || !status)
+        return fail(c, APM_E_INVALID, "apm_is_loo_psis: bad arguments");
+    if (c->S > APM_PSIS_MAX_SAMPLES)
+        return fail(c, APM_E_INVALID, "apm_is_loo_psis: n_imp above APM_PSIS_MAX_SAMPLES");
+    if ((loo_psis || khat) && ldo < c->n)
+        return fail(c, APM_E_INVALID, "apm_is_loo_psis: ldo < n");
+    if (logratio && ldr < (int64_t)c->n * c->S)
+        return fail(c, APM_E_INVALID, "apm_is_loo_psis: ldr < n*n_imp");
+    if (!check_idx(c, count, slots, c->n_slots, "slot") ||
+        !check_idx(c, count, ubufs, c->n_ubufs, "ubuf"))
+        return APM_E_INVALID;
+    return ctx_call(c, SKEW, [&] {
+        is_psis_run(c, (int)count, slots, ubufs, out_logf, loo_psis, khat, ldo, khat_w, logratio,
+                    ldr, status);
+    });
+}
+
 // ---- cache-slot lifetimes (samplers.py:563-584: an MH sampler holds the current state's cache
 // and the proposal's at once; on accept the proposal's becomes current and the old one is dropped).
 // Host bookkeeping only: a slot's contents are immutable between theta-calls into it, so a copy

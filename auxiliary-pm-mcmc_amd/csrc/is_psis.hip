@@ -1,0 +1,354 @@
+// Pareto-smoothed leave-one-out densities and the Pareto shape k-hat of the importance ratios
+// (DESIGN.md §24): the kernels that host_is_psis.cpp runs after the u-path of apm_u_eval and
+// k_is_logw.
+//
+// §23's product f = f_post + C_chol U once more, with an epilogue that stores every log ratio
+//   t_si = log wbar_s - log p(y_i | f_si)
+// instead of reducing it (k_psis_gemm, its f64 twin), and one workgroup per (chain, row) that sorts
+// the row in LDS, fits the generalised Pareto distribution to its upper tail (Zhang & Stephens
+// 2009 with the priors of the `loo` package) and sums the row with the tail replaced by the fitted
+// quantiles (k_psis_rows; include/apm.h has the steps). The same fit on the row log wbar gives the
+// tail shape of the weights themselves.
+#include <cfloat>
+
+#include "apm_internal.h"
+#include "tile64.h"
+
+#define PSIS_ROW32(l, r) (((l) >> 4) * 4 + (r))  // v_mfma_f32_16x16x4_f32's C/D row
+
+// ------------------------------------------------------------------------------- the epilogue
+// On a 64 x 64 tile of f held as is_loo.hip's loo_epilogue takes it: lp = lik_logp_mixed(y f),
+// t = log wbar - lp (-inf for a sample without weight) stored at T[row sp + column] for the rows
+// < n. The 16 lanes of a row write 16 consecutive doubles.
+template <int LIK, bool F64MAP>
+__device__ __forceinline__ void psis_epilogue(const double (&f)[2][2][4], int row0, int n,
+                                              const double* __restrict__ y,
+                                              const double* __restrict__ lwt,
+                                              double* __restrict__ T, int sp) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wr = w >> 1, wc = w & 1;
+    const int r16 = lane & 15;
+    const double lw0 = lwt[32 * wc + r16], lw1 = lwt[32 * wc + 16 + r16];
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int rl = 32 * wr + 16 * bi + (F64MAP ? F64_CROW(lane, r) : PSIS_ROW32(lane, r));
+            if (row0 + rl >= n) continue;
+            const double yr = y[row0 + rl];
+            const double lp0 = lik_logp_mixed<LIK>(yr * f[bi][0][r]);
+            const double lp1 = lik_logp_mixed<LIK>(yr * f[bi][1][r]);
+            double* o = T + (int64_t)(row0 + rl) * sp + 32 * wc + r16;
+            o[0] = lw0 == -INFINITY ? lw0 : lw0 - lp0;
+            o[16] = lw1 == -INFINITY ? lw1 : lw1 - lp1;
+        }
+}
+
+// ------------------------------------------------------------------------------- the GEMM
+// k_is_loo_gemm's tile (k_ugemm's staging, XCD-aware order and accumulation order: f_s bitwise the
+// f_s the weights were formed at) with the storing epilogue. The main loop is this kernel's own
+// copy: k_ugemm and k_is_loo_gemm stay as they are. T: [chain][row < np][sp].
+template <int LIK>
+__global__ __launch_bounds__(256) void k_psis_gemm(SlotSet S, const int64_t* __restrict__ slots,
+                                                   UPool P, const int64_t* __restrict__ ubufs,
+                                                   const double* __restrict__ y, int n, int np,
+                                                   const double* __restrict__ logw,
+                                                   double* __restrict__ T,
+                                                   const int* __restrict__ status, int nsb,
+                                                   int nchains) {
+    const int nb = np / 64;
+    const long total = (long)nb * nsb * nchains;
+    const long slot_id = blockIdx.x, xcd = slot_id & 7, q = total >> 3, rem = total & 7;
+    const long item = nchains < 8 ? slot_id
+                      : (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (slot_id >> 3);
+    const int b = (int)(item / ((long)nb * nsb));
+    const int rest = (int)(item % ((long)nb * nsb));
+    if (status[b] != 0) return;
+    const int i = nb - 1 - rest / nsb;
+    const int sb = rest % nsb;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wr = w >> 1, wc = w & 1;
+    const int r16 = lane & 15, kq = lane >> 4;
+    __shared__ float Ut[2][64][65];
+
+    const int64_t slot = slots[b];
+    if (S.wide[slot]) return;  // k_psis_gemm64
+    const float* L = S.L + slot * S.lstride;
+    const float* U = P.base32 + ubufs[b] * P.stride;
+    const int sp = P.sp;
+    const int kend = (i + 1) * 64;
+
+    f4_t acc[2][2];
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj) acc[bi][bj] = f4_t{0.f, 0.f, 0.f, 0.f};
+
+    f4_t un[4];
+    f4_t an[2][4];
+    auto gload = [&](int kk) {
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int e = tid + h * 256;  // 4-element piece, 16 per U row
+            un[h] = *reinterpret_cast<const f4_t*>(U + (int64_t)(kk + e / 16) * sp + sb * 64 +
+                                                   (e % 16) * 4);
+        }
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi) {
+            const float* p = L + (int64_t)(i * 64 + 32 * wr + 16 * bi + r16) * np + kk + kq * 16;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) an[bi][t] = *reinterpret_cast<const f4_t*>(p + 4 * t);
+        }
+    };
+    gload(0);
+    for (int kk = 0, cur = 0; kk < kend; kk += 64, cur ^= 1) {
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int e = tid + h * 256;
+            const int r = e / 16, c4 = (e % 16) * 4;
+            Ut[cur][r][c4] = un[h][0];
+            Ut[cur][r][c4 + 1] = un[h][1];
+            Ut[cur][r][c4 + 2] = un[h][2];
+            Ut[cur][r][c4 + 3] = un[h][3];
+        }
+        float a[2][16];
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+            for (int t = 0; t < 16; ++t) a[bi][t] = an[bi][t >> 2][t & 3];
+        __syncthreads();
+        if (kk + 64 < kend) gload(kk + 64);
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            float bv[2];
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj) bv[bj] = Ut[cur][kq * 16 + t][32 * wc + 16 * bj + r16];
+#pragma unroll
+            for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+                for (int bj = 0; bj < 2; ++bj)
+                    acc[bi][bj] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[bi][t], bv[bj],
+                                                                       acc[bi][bj], 0, 0, 0);
+        }
+    }
+
+    const double* fp = S.fpost64 + slot * S.vstride;
+    double f[2][2][4];
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double fr = fp[i * 64 + 32 * wr + 16 * bi + PSIS_ROW32(lane, r)];
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj) f[bi][bj][r] = fr + (double)acc[bi][bj][r];
+        }
+    psis_epilogue<LIK, false>(f, i * 64, n, y, logw + (int64_t)b * sp + sb * 64,
+                              T + (int64_t)b * np * sp + sb * 64, sp);
+}
+
+// The same product and epilogue on the f64 MFMA for the call's wide slots (k_is_loo_gemm64's
+// staging and accumulation order, which are k_ugemm64's).
+template <int LIK>
+__global__ __launch_bounds__(256) void k_psis_gemm64(SlotSet S, const int64_t* __restrict__ slots,
+                                                     UPool P, const int64_t* __restrict__ ubufs,
+                                                     const double* __restrict__ y, int n, int np,
+                                                     const double* __restrict__ logw,
+                                                     double* __restrict__ T,
+                                                     const int* __restrict__ status, int nsb) {
+    const int b = blockIdx.y;
+    if (status[b] != 0) return;
+    const int64_t slot = slots[b];
+    if (!S.wide[slot]) return;
+    const int i = (int)blockIdx.x / nsb, sb = (int)blockIdx.x % nsb;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wr = w >> 1, wc = w & 1;
+    const int r16 = lane & 15, kq = lane >> 4;
+    __shared__ double La[64][17];
+    __shared__ double Ub[16][65];
+    const double* L = S.L64[slot];
+    if (!L) return;  // (as k_ugemm64; a slot read by a u-call has its buffer attached)
+    const double* U = P.base + ubufs[b] * P.stride;
+    const int sp = P.sp;
+    d4_t acc[2][2];
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj) acc[bi][bj] = d4_t{0.0, 0.0, 0.0, 0.0};
+    const int kend = (i + 1) * 64;
+    for (int kk = 0; kk < kend; kk += 16) {
+        for (int e = tid; e < 64 * 16; e += 256) {
+            const int r = e >> 4, c = e & 15;
+            La[r][c] = L[(int64_t)(i * 64 + r) * np + kk + c];
+            Ub[e >> 6][e & 63] = U[(int64_t)(kk + (e >> 6)) * sp + sb * 64 + (e & 63)];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+#pragma unroll
+            for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+                for (int bj = 0; bj < 2; ++bj)
+                    acc[bi][bj] = __builtin_amdgcn_mfma_f64_16x16x4f64(
+                        La[32 * wr + 16 * bi + r16][4 * t + kq],
+                        Ub[4 * t + kq][32 * wc + 16 * bj + r16], acc[bi][bj], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    const double* fp = S.fpost64 + slot * S.vstride;
+    double f[2][2][4];
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double fr = fp[i * 64 + 32 * wr + 16 * bi + F64_CROW(lane, r)];
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj) f[bi][bj][r] = fr + acc[bi][bj][r];
+        }
+    psis_epilogue<LIK, true>(f, i * 64, n, y, logw + (int64_t)b * sp + sb * 64,
+                             T + (int64_t)b * np * sp + sb * 64, sp);
+}
+
+void launch_psis_gemm(int lik, SlotSet S, const int64_t* slots, UPool P, const int64_t* ubufs,
+                      const double* y, int n, int np, const double* logw, double* T,
+                      const int* status, int nchains, bool wide, hipStream_t s) {
+    const int nb = np / 64, nsb = P.sp / 64;
+    const long total = (long)nb * nsb * nchains;
+    APM_LIK_DISPATCH(lik, APM_LAUNCH(k_psis_gemm<LIK>, dim3((unsigned)total), dim3(256), 0, s, S,
+                                     slots, P, ubufs, y, n, np, logw, T, status, nsb, nchains));
+    if (wide)
+        APM_LIK_DISPATCH(lik, APM_LAUNCH(k_psis_gemm64<LIK>, dim3((unsigned)(nb * nsb), nchains),
+                                         dim3(256), 0, s, S, slots, P, ubufs, y, n, np, logw, T,
+                                         status, nsb));
+}
+
+// ------------------------------------------------------------------------------- the rows
+// The largest tail: M <= ceil(3 sqrt(APM_PSIS_MAX_SAMPLES)) = 192, so the fit's grid has
+// m = 30 + floor(sqrt(M)) <= 43 points.
+#define PSIS_MAX_TAIL 192
+#define PSIS_MAX_GRID 64
+
+// One workgroup of 256 threads per (chain, row): blockIdx.x < n is a row of T, blockIdx.x == n the
+// chain's row log wbar (khat_w; its sum is not kept). LDS (dynamic): the row padded with -inf to P,
+// the power of two >= S, then the tail's excesses x (PSIS_MAX_TAIL), the grid's b_j, L_j and
+// b_j omega_j (PSIS_MAX_GRID each) and the block reductions' four words.
+//
+// Every sum has a shape that depends on (S, P, M) alone: a thread adds its elements in ascending
+// order with stride 256 (the grid: a lane with stride 64), a wave by butterfly, the four waves in
+// order (block_sum_d); the grid's row j belongs to wave j mod 4. So a row's result does not depend
+// on where it runs. Every branch below is taken by the whole workgroup.
+__global__ __launch_bounds__(256) void k_psis_rows(const double* __restrict__ T, int64_t tstride,
+                                                   int sp, const double* __restrict__ logw, int S,
+                                                   int P, int n, double* __restrict__ out,
+                                                   int64_t npr, int64_t qstride,
+                                                   double* __restrict__ khat_w,
+                                                   const int* __restrict__ status) {
+    const int b = blockIdx.y;
+    if (status[b] != 0) return;
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const double* row = r < n ? T + b * tstride + (int64_t)r * sp : logw + (int64_t)b * sp;
+    extern __shared__ double psis_lds[];
+    double* a = psis_lds;
+    double* xs = a + P;
+    double* gb = xs + PSIS_MAX_TAIL;
+    double* gl = gb + PSIS_MAX_GRID;
+    double* gw = gl + PSIS_MAX_GRID;
+    double* red = gw + PSIS_MAX_GRID;
+
+    // 1. the finite entries, their maximum, the shifted row and its raw sum
+    double mx = -INFINITY, cnt = 0.0;
+    for (int s = tid; s < P; s += 256) {
+        const double v = s < S ? row[s] : -INFINITY;
+        a[s] = v;
+        mx = fmax(mx, v);
+        cnt += v != -INFINITY ? 1.0 : 0.0;
+    }
+    mx = block_max_d(mx, red);
+    const int Sf = (int)block_sum_d(cnt, red);
+    double raw = 0.0;
+    for (int s = tid; s < P; s += 256) {
+        const double v = a[s] == -INFINITY ? a[s] : a[s] - mx;
+        a[s] = v;
+        raw += v == -INFINITY ? 0.0 : exp(v);
+    }
+    raw = block_sum_d(raw, red);  // (its barriers also publish a[])
+    int M = (int)ceil(3.0 * sqrt((double)Sf));  // ceil(3 sqrt(S')), made exact in integers
+    while (M > 0 && (M - 1) * (M - 1) >= 9 * Sf) --M;
+    while (M * M < 9 * Sf) ++M;
+    M = min(Sf / 5, M);
+
+    double khat = NAN, res = -(mx + log(raw));
+    if (M >= 5) {
+        // bitonic sort, ascending: -inf first, the tail in a[P - M .. P)
+        for (int k = 2; k <= P; k <<= 1)
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                for (int e = tid; e < P / 2; e += 256) {
+                    const int lo = ((e & ~(j - 1)) << 1) | (e & (j - 1)), hi = lo | j;
+                    const double u = a[lo], v = a[hi];
+                    if ((u > v) == ((lo & k) == 0)) {
+                        a[lo] = v;
+                        a[hi] = u;
+                    }
+                }
+                __syncthreads();
+            }
+        // 3. the excesses over the cut
+        const double ec = exp(fmax(a[P - M - 1], log(DBL_MIN)));
+        if (tid < M) xs[tid] = exp(a[P - M + tid]) - ec;
+        __syncthreads();
+        const double x1 = xs[0], xM = xs[M - 1];
+        if (x1 > 0.0 && xM > x1) {
+            // 4. the profile likelihood on the grid b_j
+            int m = 30;
+            while ((m - 29) * (m - 29) <= M) ++m;  // 30 + floor(sqrt(M))
+            const double xq = xs[(M + 2) / 4 - 1];
+            for (int j = w; j < m; j += 4) {
+                const double bj = 1.0 / xM + (1.0 - sqrt((double)m / (j + 0.5))) / (3.0 * xq);
+                double sum = 0.0;
+                for (int z = lane; z < M; z += 64) sum += log1p(-bj * xs[z]);
+                const double kj = wave_sum_d(sum) / M;
+                if (lane == 0) {
+                    gb[j] = bj;
+                    gl[j] = M * (log(-bj / kj) - kj - 1.0);
+                }
+            }
+            __syncthreads();
+            if (tid < m) {
+                double den = 0.0;
+                for (int l = 0; l < m; ++l) den += exp(gl[l] - gl[tid]);
+                gw[tid] = gb[tid] * (1.0 / den);
+            }
+            __syncthreads();
+            double bh = 0.0;
+            for (int j = 0; j < m; ++j) bh += gw[j];
+            const double k = block_sum_d(tid < M ? log1p(-bh * xs[tid]) : 0.0, red) / M;
+            const double sigma = -k / bh;
+            khat = (M * k + 5.0) / (M + 10.0);
+            if (isfinite(khat) && isfinite(sigma)) {
+                // 5. the tail's quantiles, capped at the largest raw ratio; 6. the sum
+                double q = 0.0;
+                if (tid < M) {
+                    const double l1 = log1p(-(tid + 0.5) / M);
+                    q = khat == 0.0 ? -sigma * l1 : sigma * expm1(-khat * l1) / khat;
+                    q = fmin(q + ec, 1.0);
+                }
+                for (int s = P - Sf + tid; s < P - M; s += 256) q += exp(a[s]);
+                res = -(mx + log(block_sum_d(q, red)));
+            }
+        }
+    }
+    if (tid == 0) {
+        if (r < n) {
+            out[b * npr + r] = res;
+            out[qstride + b * npr + r] = khat;
+        } else {
+            khat_w[b] = khat;
+        }
+    }
+}
+
+void launch_psis_rows(const double* T, int64_t tstride, int sp, const double* logw, int S, int n,
+                      double* out, int64_t npr, int64_t qstride, double* khat_w,
+                      const int* status, int nchains, hipStream_t s) {
+    int P = 2;
+    while (P < S) P <<= 1;
+    const size_t lds = sizeof(double) * (P + PSIS_MAX_TAIL + 3 * PSIS_MAX_GRID + 4);
+    APM_LAUNCH(k_psis_rows, dim3(n + 1, nchains), dim3(256), lds, s, T, tstride, sp, logw, S, P, n,
+               out, npr, qstride, khat_w, status);
+}

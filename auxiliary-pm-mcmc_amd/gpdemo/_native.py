@@ -40,6 +40,7 @@ PROF_CHOL_UPDATE32_OUTER, PROF_CHOL_UPDATE_OUTER, PROF_DF_TIMEOUTS = 5, 6, 7
 PROF_POST32_OUTER, PROF_POST64_RERUNS, PROF_TRSV_TIMEOUTS = 8, 9, 10
 PROF_ICM_CHECKS, PROF_GUARD, PROF_GRAD_REDUCE, PROF_EP_SITES, PROF_NKINDS = 11, 12, 13, 14, 15
 SPREAD_MAX_BLOCKS = 4096  # APM_SPREAD_MAX_BLOCKS: n_rep * nblk of one apm_is_spread call
+PSIS_MAX_SAMPLES = 4096  # APM_PSIS_MAX_SAMPLES: the largest n_imp apm_is_loo_psis sorts
 
 
 class NativeUnavailableError(RuntimeError):
@@ -78,6 +79,7 @@ _SIGS = {
     'apm_u_eval_diag': (_i, [_p, _i64, _p, _p, _i64, _p, _p, _p, _i64, _p]),
     'apm_is_spread': (_i, [_p, _i64, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _i64, _p]),
     'apm_is_loo': (_i, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p]),
+    'apm_is_loo_psis': (_i, [_p, _i64, _p, _p, _p, _p, _p, _i64, _p, _p, _i64, _p]),
     'apm_slot_read': (_i, [_p, _i64, _p, _i64, _p, _p, _p]),
     'apm_cache_acquire': (_i, [_p, _p]),
     'apm_cache_copy': (_i, [_p, _i64]),
@@ -599,6 +601,34 @@ class Context(object):
                                    _ptr(lpd), _ptr(ess_loo), _ptr(gauss), n, _ptr(ess), _ptr(st)),
                self._h)
         return logf, loo, lpd, ess_loo, gauss, ess, st
+
+    def is_loo_psis(self, slots, ubufs, want_logratio=False):
+        """Pareto-smoothed leave-one-out densities and the Pareto shape k-hat of the importance
+        ratios' upper tails, from the importance samples of the cached u-call of :meth:`u_eval`:
+        ``(logf, loo_psis, khat, khat_w, logratio, status)``, logf (u_eval's value bitwise) and
+        khat_w (the tail shape of the weights themselves) (count,), loo_psis and khat (count, n);
+        khat is NaN where the tail is too short to fit (fewer than 25 samples) or degenerate, and
+        loo_psis is then the raw value. With `want_logratio` the log ratios ``log wbar_s - log
+        p(y_i | f_si)`` come back as (count, n, n_imp), else None. NaN for a chain whose slot's
+        last theta-call failed (include/apm.h apm_is_loo_psis). Slots and U buffers are only
+        read."""
+        sl = np.ascontiguousarray(slots, dtype=np.int64)
+        ub = np.ascontiguousarray(ubufs, dtype=np.int64)
+        if sl.ndim != 1 or ub.shape != sl.shape or not 1 <= sl.shape[0] <= self.max_batch:
+            raise ValueError('one U buffer per slot, between 1 and max_batch = {0} chains'
+                             .format(self.max_batch))
+        if self.n_imp > PSIS_MAX_SAMPLES:
+            raise ValueError('n_imp = {0} above {1} (APM_PSIS_MAX_SAMPLES)'
+                             .format(self.n_imp, PSIS_MAX_SAMPLES))
+        count, n = sl.shape[0], self.n
+        logf, khat_w = np.full(count, np.nan), np.full(count, np.nan)
+        loo_psis, khat = np.full((count, n), np.nan), np.full((count, n), np.nan)
+        lr = np.full((count, n, self.n_imp), np.nan) if want_logratio else None
+        st = np.zeros(count, dtype=np.int32)
+        _check(self.lib.apm_is_loo_psis(self._h, count, _ptr(sl), _ptr(ub), _ptr(logf),
+                                        _ptr(loo_psis), _ptr(khat), n, _ptr(khat_w), _ptr(lr),
+                                        n * self.n_imp, _ptr(st)), self._h)
+        return logf, loo_psis, khat, khat_w, lr, st
 
     def slot_read(self, slot):
         L = np.zeros((self.n, self.n))

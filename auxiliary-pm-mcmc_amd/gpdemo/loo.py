@@ -27,7 +27,7 @@ from .predict import _keep
 __all__ = ['ISLeaveOneOut', 'combine_loo']
 
 
-def combine_loo(loo, lpd, burn=0, thin=1):
+def combine_loo(loo, lpd, burn=0, thin=1, khat=None):
     """The chain-level criterion from per-state rows ``loo`` and ``lpd`` (T, n), kept samples
     ``burn::thin``. The identity averages ``1 / p`` over the states, so
 
@@ -35,7 +35,13 @@ def combine_loo(loo, lpd, burn=0, thin=1):
 
     (both by logsumexp). Returns a dict with ``elpd_loo = sum_i loo_i``, its standard error
     ``se = sqrt(n var_i loo_i)``, ``p_loo = sum_i lpd_i - elpd_loo`` (the effective number of
-    parameters) and the pointwise arrays ``loo`` and ``lpd`` (n,)."""
+    parameters) and the pointwise arrays ``loo`` and ``lpd`` (n,).
+
+    ``loo`` may as well be the Pareto-smoothed rows ``loo_psis``, which have the same form. With
+    their per-state shapes ``khat`` (T, n) the dict gains ``khat`` (n,), the per-point mean over
+    the kept states (NaN entries, states whose tail could not be fitted, are ignored; NaN where
+    no state has a value), and ``n_bad``, the number of points whose mean exceeds 0.7: their
+    ``loo`` is not to be trusted (Vehtari et al. 2024)."""
     lo, lp = _keep(loo, burn, thin), _keep(lpd, burn, thin)
     if lo.shape != lp.shape:
         raise ValueError('loo has shape {0}, lpd {1}'.format(lo.shape, lp.shape))
@@ -43,8 +49,18 @@ def combine_loo(loo, lpd, burn=0, thin=1):
     loo_i = -(logsumexp(-lo, axis=0) - np.log(T))
     lpd_i = logsumexp(lp, axis=0) - np.log(T)
     elpd = float(loo_i.sum())
-    return dict(elpd_loo=elpd, se=float(np.sqrt(n * np.var(loo_i))),
-                p_loo=float(lpd_i.sum()) - elpd, loo=loo_i, lpd=lpd_i)
+    out = dict(elpd_loo=elpd, se=float(np.sqrt(n * np.var(loo_i))),
+               p_loo=float(lpd_i.sum()) - elpd, loo=loo_i, lpd=lpd_i)
+    if khat is not None:
+        kh = _keep(khat, burn, thin)
+        if kh.shape != lo.shape:
+            raise ValueError('khat has shape {0}, loo {1}'.format(kh.shape, lo.shape))
+        seen = np.isfinite(kh)
+        cnt = seen.sum(axis=0)
+        mean = np.where(seen, kh, 0.0).sum(axis=0) / np.maximum(cnt, 1)
+        out['khat'] = np.where(cnt > 0, mean, np.nan)
+        out['n_bad'] = int((out['khat'] > 0.7).sum())
+    return out
 
 
 class ISLeaveOneOut(object):
@@ -107,13 +123,19 @@ class ISLeaveOneOut(object):
             raise_for_ep_status(status, self.max_sweeps)
         _raise_for_status(status, ctx, self.max_iters)
 
-    def __call__(self, thetas, us=None, seeds=None, on_error='raise'):
+    def __call__(self, thetas, us=None, seeds=None, on_error='raise', psis=False):
         """For thetas (T, P) or (P,): a dict with ``loo``, ``lpd``, ``ess_loo`` and ``gauss``
         (T, n), ``ess`` and ``logf`` (T,) and ``status`` (T,). The draws are either ``us``, host
         arrays (n, n_imp) per theta, or ``seeds``, one Philox seed per theta for the device's own
         normals (``apm_u_normal``, counter 0) - exactly one of the two. Each batch runs the
         theta-call and then ``apm_is_loo`` on the slots it wrote. A theta whose fit fails raises
-        the estimators' exception, or gives NaN rows with ``on_error='nan'``."""
+        the estimators' exception, or gives NaN rows with ``on_error='nan'``.
+
+        With ``psis=True`` each batch also runs ``apm_is_loo_psis`` and the dict
+        gains ``loo_psis`` and ``khat`` (T, n), the Pareto-smoothed densities and the Pareto shape
+        of each point's ratios (above 0.7: distrust ``loo`` at that point; NaN: the tail was too
+        short to fit and ``loo_psis`` is ``loo``), and ``khat_w`` (T,), the shape of the weights
+        themselves. The other entries are bitwise what they are without it."""
         if on_error not in ('raise', 'nan'):
             raise ValueError("on_error must be 'raise' or 'nan'")
         if (us is None) == (seeds is None):
@@ -134,6 +156,9 @@ class ISLeaveOneOut(object):
         ctx = self._context()
         out = {k: np.full((T, n), np.nan) for k in ('loo', 'lpd', 'ess_loo', 'gauss')}
         out.update(ess=np.full(T, np.nan), logf=np.full(T, np.nan))
+        if psis:
+            out.update(loo_psis=np.full((T, n), np.nan), khat=np.full((T, n), np.nan),
+                       khat_w=np.full(T, np.nan))
         st = np.zeros(T, dtype=np.int32)
         nops = np.zeros(T, dtype=np.int64)
         for t0 in range(0, T, self.max_batch):
@@ -148,6 +173,9 @@ class ISLeaveOneOut(object):
             _, st[sl], nops[sl] = ctx.theta_eval(self._est, th[sl], idx, idx)
             (out['logf'][sl], out['loo'][sl], out['lpd'][sl], out['ess_loo'][sl],
              out['gauss'][sl], out['ess'][sl], _) = ctx.is_loo(idx, idx)
+            if psis:
+                _, out['loo_psis'][sl], out['khat'][sl], out['khat_w'][sl], _, _ = \
+                    ctx.is_loo_psis(idx, idx)
         self.status, self.n_cubic_ops = st, nops
         out['status'] = st
         if on_error == 'raise':

@@ -364,6 +364,47 @@ int apm_is_spread(apm_ctx *ctx, int64_t count, const int64_t *slots, const int64
 int apm_is_loo(apm_ctx *ctx, int64_t count, const int64_t *slots, const int64_t *ubufs,
                double *out_logf, double *loo, double *lpd, double *ess_loo, double *gauss,
                int64_t ldo, double *ess, int *status);
+/* ---- Pareto-smoothed leave-one-out densities and the Pareto k-hat of the importance ratios (PSIS:
+ * Vehtari, Simpson, Gelman, Yao, Gabry; no reference counterpart) -----------------
+ * ess_loo_i is blind to a ratio whose variance is infinite; the shape k-hat of the ratios' upper
+ * tail is not. Per chain and per training point i < n, with t_s = log wbar_s - log p(y_i | f_si),
+ * exactly apm_is_loo's t. Padded columns, and real columns whose log wbar_s = -inf, have no t; S'
+ * is the number of finite t_s.
+ *  1. M = min(floor(0.2 S'), ceil(3 sqrt(S'))) and mx = max_s t_s; work with t_s - mx, sorted
+ *     ascending t_(1) <= .. <= t_(S').
+ *  2. If M < 5: khat_i = NaN and loo_psis_i = -(mx + log sum_s e^(t_s - mx)), the raw value.
+ *  3. cut = max(t_(S'-M), log DBL_MIN), e_c = e^cut, x_z = e^(t_(S'-M+z)) - e_c for z = 1..M,
+ *     ascending. If x_1 <= 0 or x_M <= x_1: the same fallback as in 2.
+ *  4. The generalised-Pareto fit of Zhang & Stephens (2009) with the `loo` package's priors:
+ *     m = 30 + floor(sqrt(M)), q = x_(floor(M/4 + 0.5)) (1-based); for j = 1..m
+ *       b_j = 1 / x_M + (1 - sqrt(m / (j - 0.5))) / (3 q),  k_j = (1/M) sum_z log1p(-b_j x_z),
+ *       L_j = M (log(-b_j / k_j) - k_j - 1),  omega_j = 1 / sum_l e^(L_l - L_j);
+ *     b = sum_j b_j omega_j, k = (1/M) sum_z log1p(-b x_z), sigma = -k / b and
+ *     khat = (M k + 5) / (M + 10) (prior_k = 10 pulling towards 0.5). A non-finite khat or sigma
+ *     gives the fallback, with khat_i as computed.
+ *  5. p_z = (z - 0.5) / M, q_z = sigma expm1(-khat log1p(-p_z)) / khat (-sigma log1p(-p_z) when
+ *     khat == 0), r_z = min(q_z + e_c, 1): the cap is truncation at the largest raw ratio.
+ *  6. loo_psis_i = -(mx + log(sum_{z <= S'-M} e^(t_(z)) + sum_z r_z)). Only the sum is needed, so
+ *     no rank-to-sample map is formed and ties cannot matter.
+ * loo_psis keeps the form -log sum_s r_si, so it drops into the same average over a chain's states
+ * as loo (1 / E[1 / p]). Per chain, steps 1-4 on the row log wbar_s give khat_w, the tail shape of
+ * the importance weights: a diagnostic only (the pseudo-marginal estimate itself is never
+ * smoothed, which would bias it). k-hat above 0.7 marks a value not to be trusted.
+ * apm_u_eval (the same checks, launches and status: out_logf is bitwise its value) followed by
+ * the tail; chain i's rows loo_psis and khat are at [i ldo], n values each, khat_w has count
+ * entries. logratio, if given, receives the t_si themselves, chain i's at [i ldr + r n_imp + s] for
+ * row r < n and the real columns s < n_imp (ldr >= n n_imp), for a caller who pools states and
+ * smooths offline. Any output pointer except status may be NULL. APM_E_INVALID, with nothing
+ * written, for apm_is_loo's own conditions, for n_imp > APM_PSIS_MAX_SAMPLES and for
+ * ldr < n n_imp with logratio non-NULL. A chain whose slot's last theta-call failed gets
+ * apm_u_eval's status and NaN in every output. Works for slots written by APM_EST_IS,
+ * APM_EST_IS_EP and APM_EST_PRIORMC under both likelihoods. A chain's outputs do not depend on its
+ * position in the batch nor on the other chains. Slots and U buffers are only read; apm_is_loo's
+ * results are not disturbed. apm_version() is unchanged: detect the entry point by its symbol. */
+#define APM_PSIS_MAX_SAMPLES 4096
+int apm_is_loo_psis(apm_ctx *ctx, int64_t count, const int64_t *slots, const int64_t *ubufs,
+                    double *out_logf, double *loo_psis, double *khat, int64_t ldo,
+                    double *khat_w, double *logratio, int64_t ldr, int *status);
 /* cache-slot lifetimes (samplers.py:563-584: an MH sampler keeps the current state's cache and the
  * proposal's alive at once). acquire: a free slot, one owner (APM_E_NOMEM when all are owned);
  * copy: one more owner of the same (immutable) state - the handle copy of the reference's tuple;
