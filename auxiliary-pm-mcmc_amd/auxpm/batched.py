@@ -84,7 +84,7 @@ class _BatchedChains(object):
 
     def __init__(self, X, y, n_chains, n_imp, prior, kernel='ard', epsilon=1e-8,
                  max_slice_iters=1000, seed=0, estimator='is', device=None, first_chain=0,
-                 likelihood='probit', ep_settings=None, bias=False):
+                 likelihood='probit', ep_settings=None, bias=False, linear=False):
         _native.likelihood_code(likelihood)  # ('probit' | 'logit'; ValueError otherwise)
         self.likelihood = likelihood
         self.n_chains = int(n_chains)
@@ -99,6 +99,13 @@ class _BatchedChains(object):
         self.bias = bool(bias)
         if self.bias:
             kind |= _native.COV_BIAS
+        # linear=True ('iso' and 'ard' only): the linear term exp(theta[-1]) x x^T, one more entry
+        # again (the constant term's is then theta[-2]), with the same default prior
+        self.linear = bool(linear)
+        if self.linear:
+            if (kind & ~_native.COV_BIAS) not in (_native.KERNEL_ISO, _native.KERNEL_ARD):
+                raise ValueError("linear=True needs kernel 'iso' or 'ard'")
+            kind |= _native.COV_LINEAR
         C = self.n_chains
         self.ctx = _native.Context(X, y, kind, epsilon, n_imp, max_batch=C, n_slots=2 * C,
                                    n_ubufs=3 * C, device=device, likelihood=likelihood)
@@ -493,11 +500,11 @@ class BatchedAPMEllSSPlusRandDirSliceSampler(_BatchedChains):
 
     def __init__(self, X, y, n_chains, n_imp, prior, kernel='ard', epsilon=1e-8, w=1.,
                  max_steps_out=0, max_slice_iters=1000, seed=0, estimator='is', device=None,
-                 first_chain=0, likelihood='probit', ep_settings=None, bias=False):
+                 first_chain=0, likelihood='probit', ep_settings=None, bias=False, linear=False):
         super(BatchedAPMEllSSPlusRandDirSliceSampler, self).__init__(
             X, y, n_chains, n_imp, prior, kernel, epsilon, max_slice_iters, seed, estimator,
             device, first_chain, likelihood=likelihood, ep_settings=ep_settings,
-            bias=bias)
+            bias=bias, linear=linear)
         self.w = float(w)
         self.max_steps_out = int(max_steps_out)
         C = self.n_chains
@@ -866,11 +873,11 @@ class BatchedAPMEllSSPlusMHSampler(_BatchedMHMixin, _BatchedChains):
 
     def __init__(self, X, y, n_chains, n_imp, prior, prop_scales, kernel='ard', epsilon=1e-8,
                  metropolis=False, max_slice_iters=1000, seed=0, estimator='is', device=None,
-                 first_chain=0, likelihood='probit', ep_settings=None, bias=False):
+                 first_chain=0, likelihood='probit', ep_settings=None, bias=False, linear=False):
         super(BatchedAPMEllSSPlusMHSampler, self).__init__(
             X, y, n_chains, n_imp, prior, kernel, epsilon, max_slice_iters, seed, estimator,
             device, first_chain, likelihood=likelihood, ep_settings=ep_settings,
-            bias=bias)
+            bias=bias, linear=linear)
         self._init_mh(prop_scales, metropolis)
 
     def _mh_theta(self):
@@ -903,11 +910,11 @@ class BatchedPMMHSampler(_BatchedMHMixin, _BatchedChains):
 
     def __init__(self, X, y, n_chains, n_imp, prior, prop_scales, kernel='iso', epsilon=1e-8,
                  metropolis=False, seed=0, estimator='is', device=None, first_chain=0,
-                 likelihood='probit', ep_settings=None, bias=False):
+                 likelihood='probit', ep_settings=None, bias=False, linear=False):
         super(BatchedPMMHSampler, self).__init__(
             X, y, n_chains, n_imp, prior, kernel, epsilon, 1000, seed, estimator, device,
             first_chain, likelihood=likelihood, ep_settings=ep_settings,
-            bias=bias)
+            bias=bias, linear=linear)
         self._init_mh(prop_scales, metropolis)
 
     def set_estimator(self, estimator):
@@ -973,11 +980,11 @@ class BatchedAPMMetIndPlusSeqSliceSampler(BatchedAPMEllSSPlusRandDirSliceSampler
 
     def __init__(self, X, y, n_chains, n_imp, prior, ws, kernel='ard', epsilon=1e-8,
                  max_steps_out=0, max_slice_iters=1000, seed=0, estimator='is', device=None,
-                 first_chain=0, likelihood='probit', ep_settings=None, bias=False):
+                 first_chain=0, likelihood='probit', ep_settings=None, bias=False, linear=False):
         super(BatchedAPMMetIndPlusSeqSliceSampler, self).__init__(
             X, y, n_chains, n_imp, prior, kernel, epsilon, 1., max_steps_out, max_slice_iters,
             seed, estimator, device, first_chain, likelihood=likelihood, ep_settings=ep_settings,
-            bias=bias)
+            bias=bias, linear=linear)
         self.ws = np.array(np.broadcast_to(np.asarray(ws, dtype=np.float64), (self.P,)))
 
     def _u_update(self, chains=None):
@@ -1014,11 +1021,11 @@ class BatchedAPMEllSSPlusEllSSSampler(BatchedAPMEllSSPlusRandDirSliceSampler):
 
     def __init__(self, X, y, n_chains, n_imp, theta_prior_std, kernel='ard', epsilon=1e-8,
                  max_slice_iters=1000, seed=0, estimator='is', device=None, first_chain=0,
-                 likelihood='probit', ep_settings=None, bias=False):
+                 likelihood='probit', ep_settings=None, bias=False, linear=False):
         super(BatchedAPMEllSSPlusEllSSSampler, self).__init__(
             X, y, n_chains, n_imp, {}, kernel, epsilon, 1., 0, max_slice_iters, seed, estimator,
             device, first_chain, likelihood=likelihood, ep_settings=ep_settings,
-            bias=bias)
+            bias=bias, linear=linear)
         self.theta_prior_std = np.array(np.broadcast_to(
             np.asarray(theta_prior_std, dtype=np.float64), (self.P,)))
         C = self.n_chains

@@ -245,9 +245,15 @@ struct __attribute__((visibility("hidden"))) apm_ctx {
     // (np x d), the mu* partials (max_batch x nb x np), the three outputs (max_batch x np each) and
     // behind them, as the host computes them (max_batch each): the chains' s = exp(theta_0) (psig,
     // the cross-covariance's), their prior variance k** = s + beta (pkss: s itself without the
-    // constant term) and beta = exp(theta_{P-1}) (pbet: 0 without it)
+    // constant term) and beta = exp(theta_{P-1}) (pbet: 0 without it). A kind with the linear term
+    // (DESIGN.md §25): lambda = exp(theta_{P-1}) in plam (beta is then theta_{P-2}'s) and the
+    // staged test rows' squared norms in pxn (np), k** = pkss[b] + plam[b] pxn[r]; both stay
+    // null for every other kind, and no kernel launched for one reads them
     double *pxs = nullptr, *ppart = nullptr, *pmean = nullptr, *pvar = nullptr, *pprob = nullptr;
-    double *psig = nullptr, *pkss = nullptr, *pbet = nullptr;
+    double *psig = nullptr, *pkss = nullptr, *pbet = nullptr, *plam = nullptr, *pxn = nullptr;
+    // max_i |x_i|^2 and sum_i |x_i|^2 of the training inputs (apm_create; the range flags of a
+    // kind with the linear term: K_ii = s + beta + lambda |x_i|^2 + eps differs by row)
+    double x2max = 0.0, x2sum = 0.0;
     // the gradient path (apm_laplace_grad), allocated at its first call: six vectors per chain
     // (dS, g, s2, t = K s2, u = -R t, q; max_batch x np each), the super-tile partials
     // (max_batch x ns (ns + 1) / 2 x P) and the gradients (max_batch x P)
@@ -371,7 +377,13 @@ const double* upload_thetas(apm_ctx* c, int64_t count, const double* thetas, int
 // beta = exp(theta_{P-1}) of a biased kind's theta (P entries), 0 for every other kind: with it
 // K_ii = exp(theta_0) + beta + eps and k** = exp(theta_0) + beta
 inline double cov_beta(int kind, int P, const double* theta) {
-    return kernel_kind_of(kind).bias ? std::exp(theta[P - 1]) : 0.0;
+    const KernelKind kk = kernel_kind_of(kind);
+    return kk.bias ? std::exp(theta[P - 1 - kk.linear]) : 0.0;
+}
+// lambda = exp(theta_{P-1}) of a kind with the linear term (beta is then theta_{P-2}'s), 0 for
+// every other kind: K_ii = exp(theta_0) + beta + lambda |x_i|^2 + eps
+inline double cov_lambda(int kind, int P, const double* theta) {
+    return kernel_kind_of(kind).linear ? std::exp(theta[P - 1]) : 0.0;
 }
 // the identity-padded copy of a host K (n x n, row stride ldk) -> chain 0's K, both triangles
 // (k_full), staged in Kp, which the caller keeps until its next sync; returns max |K_ii|
@@ -464,8 +476,9 @@ void predict_buffers(apm_ctx* c);
 void predict_block(apm_ctx* c, int count, int ms);
 // One call's test inputs Xs (m x d, row stride ldxs), a block of at most np rows at a time: the
 // constructor uploads the chains' s = exp(theta_0), s + beta and beta to psig / pkss / pbet
-// (predict_buffers() first; cov_beta), upload()
-// packs rows [r0, r0 + ms) and sends them to pxs (returns ms), rows_back() enqueues the copy of
+// (predict_buffers() first; cov_beta) and, for a kind with the linear term, lambda to plam; upload()
+// packs rows [r0, r0 + ms) and sends them to pxs (returns ms; with the linear term their squared
+// norms, features in order, go to pxn: once per block, the same for every chain), rows_back() enqueues the copy of
 // the block's pmean / pvar / pprob rows to the caller's arrays (count x m, row stride ldo, any of
 // them null). The two users copy back differently on purpose: the Laplace / EP predictive every
 // row with one 2-D copy per output (only_ok null; rows of failed chains hold stale values, which

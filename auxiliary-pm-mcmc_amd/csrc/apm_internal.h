@@ -218,29 +218,41 @@ void launch_refine(int mode, const double* Ws, const double* Kb, double* x, cons
 // exp(theta_1) for every k (iso); dK/dtheta_{k+1} = G ((x_ik - x_jk)/tau_k)^2 (gradient.hip).
 // APM_COV_BIAS (16) OR-ed onto one of the six: K = S + beta 1 1^T + eps I on the data pairs, beta =
 // exp of theta's last entry; dK/dtheta_{P-1} = beta on every data pair.
+// APM_COV_LINEAR (64) OR-ed onto an SE kind, with or without the bias: K = S [+ beta] + lambda x x^T
+// + eps I on the data pairs (the raw inputs' dot products), lambda = exp of theta's last entry and
+// beta = exp of the one before it; dK/dtheta_{P-1} = lambda x_i . x_j.
 enum { APM_FAM_SE = 0, APM_FAM_M32 = 1, APM_FAM_M52 = 2 };
 struct KernelKind {
     int family;  // APM_FAM_*, -1: not built on the device
     int iso;     // one length scale (theta has 2 entries) instead of d (d + 1 entries)
-    int bias;    // the constant term: one more theta entry, the last
+    int bias;    // the constant term: one more theta entry (the last, or the one before lambda's)
+    int linear;  // the linear term (SE only): one more theta entry, the last
     bool on_device() const { return family >= 0; }
-    int64_t theta_len(int64_t d) const { return family < 0 ? 0 : (iso ? 2 : d + 1) + bias; }
+    int64_t theta_len(int64_t d) const {
+        return family < 0 ? 0 : (iso ? 2 : d + 1) + bias + linear;
+    }
 };
 inline KernelKind kernel_kind_of(int kind) {
-    const int bias = (kind & 16) ? 1 : 0;  // APM_COV_BIAS
+    const int bias = (kind & 16) ? 1 : 0;    // APM_COV_BIAS
+    const int linear = (kind & 64) ? 1 : 0;  // APM_COV_LINEAR
+    switch (kind & ~(16 | 64)) {
+        case 0: return KernelKind{APM_FAM_SE, 1, bias, linear};  // APM_KERNEL_ISO
+        case 1: return KernelKind{APM_FAM_SE, 0, bias, linear};  // APM_KERNEL_ARD
+        default: break;
+    }
+    if (linear) return KernelKind{-1, 0, 0, 0};  // (a Matern kind has no linear instantiation)
     switch (kind & ~16) {
-        case 0: return KernelKind{APM_FAM_SE, 1, bias};   // APM_KERNEL_ISO
-        case 1: return KernelKind{APM_FAM_SE, 0, bias};   // APM_KERNEL_ARD
-        case 3: return KernelKind{APM_FAM_M32, 1, bias};  // APM_KERNEL_M32_ISO
-        case 4: return KernelKind{APM_FAM_M32, 0, bias};  // APM_KERNEL_M32_ARD
-        case 5: return KernelKind{APM_FAM_M52, 1, bias};  // APM_KERNEL_M52_ISO
-        case 6: return KernelKind{APM_FAM_M52, 0, bias};  // APM_KERNEL_M52_ARD
-        // APM_KERNEL_PRECOMPUTED (with or without the flag) and unknown values
-        default: return KernelKind{-1, 0, 0};
+        case 3: return KernelKind{APM_FAM_M32, 1, bias, 0};  // APM_KERNEL_M32_ISO
+        case 4: return KernelKind{APM_FAM_M32, 0, bias, 0};  // APM_KERNEL_M32_ARD
+        case 5: return KernelKind{APM_FAM_M52, 1, bias, 0};  // APM_KERNEL_M52_ISO
+        case 6: return KernelKind{APM_FAM_M52, 0, bias, 0};  // APM_KERNEL_M52_ARD
+        // APM_KERNEL_PRECOMPUTED (with or without a flag) and unknown values
+        default: return KernelKind{-1, 0, 0, 0};
     }
 }
-// the launchers' dispatch on the family and the constant term (template parameters of k_gram,
-// k_gram_cross and k_grad_reduce: their epilogues differ, everything else is shared)
+// the launchers' dispatch on the family, the constant and the linear term (template parameters of
+// k_gram, k_gram_cross and k_grad_reduce: their epilogues differ, everything else is shared). The
+// linear term exists for the SE family only: inside a Matern case LIN is false whatever the flag.
 #define APM_FAMILY_DISPATCH(family, ...)                                           \
     switch (family) {                                                              \
         case APM_FAM_M32: { constexpr int FAM = APM_FAM_M32; __VA_ARGS__; } break; \
@@ -250,6 +262,9 @@ inline KernelKind kernel_kind_of(int kind) {
 #define APM_BIAS_DISPATCH(bias, ...)                        \
     if (bias) { constexpr bool BIAS = true; __VA_ARGS__; }  \
     else { constexpr bool BIAS = false; __VA_ARGS__; }
+#define APM_LINEAR_DISPATCH(linear, ...)                                       \
+    if (linear) { constexpr bool LIN = FAM == APM_FAM_SE; __VA_ARGS__; }       \
+    else { constexpr bool LIN = false; __VA_ARGS__; }
 #ifdef __HIPCC__
 // the covariance function of the pair's scaled squared distance r2, family FAM
 template <int FAM>
@@ -297,22 +312,23 @@ void launch_gram(MatB K, const double* X, int64_t ldx, int n, int d, const doubl
 // plain != 0 (apm_gram_cross): out.base[r * out.ld + c] <- k*_rc for r < ms, c < n, one chain,
 // nothing else is touched (Ws, a, part, live may be null).
 // A biased kind adds bet[b] = exp(theta_{P-1}), the host's as sig[b] is, to every k*_rc with
-// r < ms, c < n (bet is not read otherwise and may be null).
+// r < ms, c < n (bet is not read otherwise and may be null). A kind with the linear term adds
+// lam[b] xs_r . x_c (lam[b] the host's exp of theta's last entry; not read otherwise, may be null).
 void launch_gram_cross(MatB out, int64_t row0, const double* Xs, int ms, int mb, const double* X,
                        int64_t ldx, int n, int d, int nb, const double* theta, int64_t tstride,
-                       const double* sig, const double* bet, int kind, const double* Ws,
-                       const double* a,
-                       int64_t vstride, double* part, int64_t pstride, Live live, int plain,
-                       int nchains, hipStream_t s);
+                       const double* sig, const double* bet, const double* lam, int kind,
+                       const double* Ws, const double* a, int64_t vstride, double* part,
+                       int64_t pstride, Live live, int plain, int nchains, hipStream_t s);
 // per chain and test row r < ms: mean = sum_tj part[tj][r] (in order), var = sig[b] - |row r of V^T|^2
 // over columns [0, 64 nb) of A's rows [row0, ..), prob = Phi(mean / sqrt(1 + var)); each output
 // out[b * ostride + r]. Nothing is clamped. sig[b] is the prior variance k** here (and in
-// launch_is_rows): s, or s + beta of a biased kind.
+// launch_is_rows): s, or s + beta of a biased kind. lam != null (a kind with the linear term):
+// k** = sig[b] + lam[b] xsn[r], xsn the test rows' squared norms; a null lam reads neither.
 // lik (APM_LIK_*): the logit's prob is the Gauss-Hermite average of sigma (gh_table.h)
 void launch_predict_reduce(int lik, MatB A, int64_t row0, int ms, int mb, int nb,
-                           const double* sig, const double* part, int64_t pstride, double* mean,
-                           double* var, double* prob, int64_t ostride, Live live, int nchains,
-                           hipStream_t s);
+                           const double* sig, const double* lam, const double* xsn,
+                           const double* part, int64_t pstride, double* mean, double* var,
+                           double* prob, int64_t ostride, Live live, int nchains, hipStream_t s);
 
 // ---- gradient.hip: gradient of the Laplace LML w.r.t. theta ---------------
 // per chain and row r < 64 nb: dS = K_rr - |row np + r of A over columns [0, 64 nb)|^2,
@@ -334,7 +350,9 @@ void launch_grad_q(const double* s2, const double* u, double* q, int64_t gstride
 // off the diagonal, exp(theta_0) on it; t over the ns (ns + 1) / 2 lower super-tiles, ns =
 // ceil(nb / 2). launch_grad_sum adds them in tile order into grad[b * P + j]. A biased kind's K
 // tiles hold S + beta: its SE instantiation forms S from the pair's own r^2, its Matern ones take
-// K - beta; both write beta sum_ik M_ik as entry P - 1.
+// K - beta; both write beta sum_ik M_ik as entry P - 1. A kind with the linear term (SE only) takes
+// the biased SE route, writes beta's entry at P - 2 and lambda sum_ik M_ik x_i . x_k as entry
+// P - 1 from a kernel of its own (k_grad_lin).
 void launch_grad_reduce(MatB K, MatB Rn, const double* X, int64_t ldx, int n, int d, int nb,
                         const double* theta, int64_t tstride, int kind, const double* a,
                         int64_t vstride, const double* q, const double* g, int64_t gstride,
@@ -526,6 +544,7 @@ void launch_is_ut(UPool P, const int64_t* ubufs, int np, double* Ut, Live live, 
 // [0, 64 nb): vstar = sig[b] - |p_r|^2, cvec = sum_tj part[tj][r] in order (0 for r >= ms), each at
 // out[b * ostride + r], and p_r^T J into columns [64 nb, 128 nb) of the same row
 void launch_is_rows(MatB A, int64_t row0, int ms, int mb, int nb, const double* sig,
+                    const double* lam, const double* xsn,
                     const double* part, int64_t pstride, double* vstar, double* cvec,
                     int64_t ostride, Live live, int nchains, hipStream_t s);
 // per (chain, row tile < mb, sample tile < sp / 64): the h-rows (A's rows [row0, ..), columns

@@ -292,14 +292,25 @@ int apm_theta_eval(apm_ctx* c, int est, int64_t count, const double* thetas, int
         // fp16x3 Newton updates need |L_ij| <= sqrt(1 + K_ii) < 65504 (chol32_update.hip): per chain;
         // the posterior bottom block's operands |L'_ij| <= sqrt(1 + n K_ii) (postcov.hip).
         // K_ii = s + beta + eps; "theta_0 < 19" is the bound s < e^19 on K_ii, which a constant
-        // term shares (beta = 0 leaves every flag what it was)
+        // term shares (beta = 0 leaves every flag what it was). With the linear term K_ii differs
+        // by row: the bounds take its largest value, s + beta + lambda max|x|^2 + eps, and the
+        // ICM threshold its sum, trace(K); without the flag every expression is
+        // what it was
+        const bool lin = kernel_kind_of(c->kind).linear != 0;
         for (int64_t b = 0; b < count; ++b) {
             const double beta = cov_beta(c->kind, c->P, th + b * c->P);
-            const double sb = std::exp(th[b * c->P]) + beta, kii = sb + c->eps;
-            pin_h3(c)[b] = c->h3 && (beta == 0.0 ? th[b * c->P] < 19.0 : std::log(sb) < 19.0);
+            double sb = std::exp(th[b * c->P]) + beta;
+            double tr = 0.0;
+            if (lin) {
+                const double lam = cov_lambda(c->kind, c->P, th + b * c->P);
+                tr = c->n * (sb + c->eps) + lam * c->x2sum;
+                sb += lam * c->x2max;
+            }
+            const double kii = sb + c->eps;
+            pin_h3(c)[b] = c->h3 && (beta == 0.0 && !lin ? th[b * c->P] < 19.0 : std::log(sb) < 19.0);
             pin_inv(c)[b] = 1.0 + sb + c->eps < 32768.0;
             pin_h3post(c)[b] = c->h3 && 1.0 + c->n * kii < 4e8;
-            pin_icm(c)[b] = c->n * kii / std::max(c->icm_q, 1.0);
+            pin_icm(c)[b] = (lin ? tr : c->n * kii) / std::max(c->icm_q, 1.0);
         }
         upload_h3(c, (int)count);
         if (est != APM_EST_LAPLACE) upload_idx(c, (int)count, slots, ubufs);
@@ -537,23 +548,24 @@ int apm_gram_cross(int device, int kind, const double* Xs, int64_t m, const doub
         return fail(nullptr, APM_E_INVALID, "apm_gram_cross: bad arguments");
     const int64_t P = kernel_kind_of(kind).theta_len(d);
     if (n_theta < P) return fail(nullptr, APM_E_INVALID, "apm_gram_cross: theta too short");
-    double* dev = nullptr;  // [X: n x d][Xs: m x d][theta: P][s][beta][Ks: m x n]
+    double* dev = nullptr;  // [X: n x d][Xs: m x d][theta: P][s][beta][lambda][Ks: m x n]
     try {
         HIPC(hipSetDevice(device));
-        std::vector<double> h((size_t)((n + m) * d + P + 2));  // (+ s = exp(theta_0), beta)
+        std::vector<double> h((size_t)((n + m) * d + P + 3));  // (+ s = exp(theta_0), beta, lambda)
         for (int64_t i = 0; i < n + m; ++i)  // both point sets take the row stride ldx
             for (int64_t k = 0; k < d; ++k)
                 h[i * d + k] = i < n ? X[i * ldx + k] : Xs[(i - n) * ldx + k];
         for (int64_t p = 0; p < P; ++p) h[(n + m) * d + p] = theta[p];
         h[(n + m) * d + P] = std::exp(theta[0]);
         h[(n + m) * d + P + 1] = cov_beta(kind, (int)P, theta);
+        h[(n + m) * d + P + 2] = cov_lambda(kind, (int)P, theta);
         HIPC(hipMalloc(reinterpret_cast<void**>(&dev), sizeof(double) * (h.size() + m * n)));
         HIPC(hipMemcpy(dev, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
         double* dK = dev + h.size();
         launch_gram_cross(MatB{dK, n, 0}, 0, dev + n * d, (int)m, (int)((m + 63) / 64), dev, d,
                           (int)n, (int)d, (int)((n + 63) / 64), dev + (n + m) * d, 0,
-                          dev + (n + m) * d + P, dev + (n + m) * d + P + 1, kind, nullptr, nullptr,
-                          0, nullptr, 0,
+                          dev + (n + m) * d + P, dev + (n + m) * d + P + 1,
+                          dev + (n + m) * d + P + 2, kind, nullptr, nullptr, 0, nullptr, 0,
                           Live{nullptr, nullptr}, 1, 1, nullptr);
         HIPC(hipMemcpy2D(Ks, sizeof(double) * ldk, dK, sizeof(double) * n, sizeof(double) * n, m,
                          hipMemcpyDeviceToHost));

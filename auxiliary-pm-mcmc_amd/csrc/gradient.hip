@@ -12,6 +12,8 @@
 //   dK/dtheta_{k+1} = G_ik ((x_ik - x_jk)/tau_k)^2 (ARD), the sum over k of these (iso); G = S for
 //   the SE family, cov_G (apm_internal.h) for Matern 3/2 and 5/2
 //   dK/dtheta_{P-1} = beta on every data pair (a biased kind, K = S + beta 1 1^T + epsilon I)
+//   dK/dtheta_{P-1} = lambda x_i . x_k on every data pair (a kind with the linear term, DESIGN.md
+//   §25; beta's entry is then P - 2)
 // with W, L, a of the last Newton iteration (latent_posterior_approximations.py:81-106).
 #include "apm_internal.h"
 #include "pair_tile.h"
@@ -150,7 +152,12 @@ void launch_grad_q(const double* s2, const double* u, double* q, int64_t gstride
 // on every pair, the diagonal included): the pairs in the order the stage visits them (SE: a
 // row's 8 pairs, then the 8 row sums; Matern: one running sum over the two runs' rows), the
 // wave's butterfly, the 4 waves in order; it is entry P - 1 of the partials.
-template <int FAM, bool BIAS>
+//
+// LIN (the linear term, DESIGN.md §25, SE only): K's lower tiles hold S [+ beta] + lambda x x^T,
+// so the instantiation takes the biased SE route, S from the lane's own r^2 with K not read, which
+// keeps theta_0's weight exact; beta's entry moves to P - 2. lambda's own entry P - 1 is not
+// written here: k_grad_lin below does.
+template <int FAM, bool BIAS, bool LIN>
 __global__ __launch_bounds__(256, FAM == APM_FAM_SE ? 1 : 2) void k_grad_reduce(
     MatB K, MatB Rn, const double* __restrict__ X, int64_t ldx, int n, int d, int nb,
     const double* __restrict__ theta, int64_t tstride, int ard, const double* __restrict__ avec,
@@ -174,7 +181,7 @@ __global__ __launch_bounds__(256, FAM == APM_FAM_SE ? 1 : 2) void k_grad_reduce(
 
     double w[8][8];
     double s0 = 0.0, sb = 0.0;
-    if constexpr (FAM != APM_FAM_SE || BIAS) {  // first pass: w <- the pairs' r^2
+    if constexpr (FAM != APM_FAM_SE || BIAS || LIN) {  // first pass: w <- the pairs' r^2
 #pragma unroll
         for (int p = 0; p < 8; ++p)
 #pragma unroll
@@ -190,7 +197,7 @@ __global__ __launch_bounds__(256, FAM == APM_FAM_SE ? 1 : 2) void k_grad_reduce(
         const double* ab = avec + b * vstride;
         const double* qb = qvec + b * gstride;
         const double* gb = gvec + b * gstride;
-        if constexpr (BIAS && FAM == APM_FAM_SE) {
+        if constexpr ((BIAS || LIN) && FAM == APM_FAM_SE) {
             // the stage below without K: S = G from the lane's own r^2, and beta's sum beside
             // theta_0's (a row's 8 pairs in order, then the 8 row sums in order)
             double ak[8], qk[8], gk[8];
@@ -222,10 +229,10 @@ __global__ __launch_bounds__(256, FAM == APM_FAM_SE ? 1 : 2) void k_grad_reduce(
                     const bool in = gi < n && gj <= gi;  // (gj <= gi < n)
                     w[p][q] = in ? cnt * (m * sv) : 0.0;
                     sp += w[p][q];
-                    spb += in ? cnt * m : 0.0;
+                    if constexpr (BIAS) spb += in ? cnt * m : 0.0;
                 }
                 s0 += sp;
-                sb += spb;
+                if constexpr (BIAS) sb += spb;
             }
         } else if constexpr (FAM == APM_FAM_SE) {
             double ak[8], qk[8], gk[8];
@@ -290,7 +297,7 @@ __global__ __launch_bounds__(256, FAM == APM_FAM_SE ? 1 : 2) void k_grad_reduce(
             // and shares them and spills up to 114 registers).
             int trs = tr, tcs = tc;
             double beta = 0.0;
-            if constexpr (BIAS) beta = exp(th[P - 1]);
+            if constexpr (BIAS) beta = exp(th[P - 1 - (LIN ? 1 : 0)]);
             const double* Kt = K.base + b * K.cstride + tj * 64;
             const double* Rt = Rn.base + b * Rn.cstride + tj * 64;
             double sp[8];
@@ -338,7 +345,7 @@ __global__ __launch_bounds__(256, FAM == APM_FAM_SE ? 1 : 2) void k_grad_reduce(
 #pragma unroll
             for (int p = 0; p < 8; ++p) s0 += sp[p];
         }
-    } else if constexpr (FAM == APM_FAM_SE && !BIAS) {  // (a two-pass w is zero already)
+    } else if constexpr (FAM == APM_FAM_SE && !BIAS && !LIN) {  // (a two-pass w is zero already)
 #pragma unroll
         for (int p = 0; p < 8; ++p)
 #pragma unroll
@@ -391,8 +398,92 @@ __global__ __launch_bounds__(256, FAM == APM_FAM_SE ? 1 : 2) void k_grad_reduce(
         pb[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
         if (ard == 0) pb[1] = iso;
         if constexpr (BIAS)
-            pb[P - 1] = exp(th[P - 1]) * (((red[0][1] + red[1][1]) + red[2][1]) + red[3][1]);
+            pb[P - 1 - (LIN ? 1 : 0)] = exp(th[P - 1 - (LIN ? 1 : 0)]) *
+                                        (((red[0][1] + red[1][1]) + red[2][1]) + red[3][1]);
     }
+}
+
+// lambda's entry of the gradient (the linear term): part[b][t][P - 1] <-
+// lambda sum c M_ik (x_i . x_k) over the data pairs of lower super-tile t, a kernel of its own
+// beside k_grad_reduce with its tiling, its M and its order of sums. The first sweep stages the
+// unscaled inputs (pair_stage<true>) and accumulates the pairs' dot products in the lane's 8x8
+// block, features in order; the stage then streams the lower tiles of Rn once more and forms M as
+// k_grad_reduce does (K is not read): a row's 8 pairs in order, the 8 row sums in order, the
+// wave's butterfly, the 4 waves in order; k_grad_sum adds the super-tiles in order. Nothing of
+// k_grad_reduce's 64 live weights has to make room for the 64 dot products this way, and its
+// non-linear instantiations stay what they were.
+__global__ __launch_bounds__(256, 2) void k_grad_lin(
+    MatB Rn, const double* __restrict__ X, int64_t ldx, int n, int d, int nb,
+    const double* __restrict__ theta, int64_t tstride, const double* __restrict__ avec,
+    int64_t vstride, const double* __restrict__ qvec, const double* __restrict__ gvec,
+    int64_t gstride, double* __restrict__ part, int64_t pstride, int P, Live live) {
+    const int b = blockIdx.y;
+    if (!live_chain(live, b)) return;
+    const int t = blockIdx.x;
+    int si, sj;  // the lower super-tile, si >= sj
+    lower_tri_index(t, si, sj);
+
+    __shared__ PairTile lds;
+    __shared__ double red[4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tr = lane >> 3, tc = lane & 7;
+    const int ti = 2 * si + (wv >> 1), tj = 2 * sj + (wv & 1);
+    const bool mine = ti < nb && tj <= ti;  // (wave-uniform)
+    const int ro = 64 * (wv >> 1), co = 64 * (wv & 1);
+    const double* th = theta + b * tstride;
+
+    double w[8][8];
+#pragma unroll
+    for (int p = 0; p < 8; ++p)
+#pragma unroll
+        for (int q = 0; q < 8; ++q) w[p][q] = 0.0;
+    for (int k0 = 0; k0 < d; k0 += GK) {
+        const int kc = min(GK, d - k0);
+        pair_stage<true>(lds, th, 0, k0, kc, X, ldx, n, si * 128, X, ldx, n, sj * 128);
+        if (mine) pair_dot_chunk(lds, kc, ro, tr, co, tc, w);
+    }
+    double sl = 0.0;
+    if (mine) {
+        const double* ab = avec + b * vstride;
+        const double* qb = qvec + b * gstride;
+        const double* gb = gvec + b * gstride;
+        double ak[8], qk[8], gk[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int gj = tj * 64 + R8(tc, q);
+            ak[q] = ab[gj];
+            qk[q] = qb[gj];
+            gk[q] = gb[gj];
+        }
+        const double* Rt = Rn.base + b * Rn.cstride + tj * 64 + 4 * tc;
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+            const int gi = ti * 64 + R8(tr, p);
+            const double* rr = Rt + (int64_t)gi * Rn.ld;
+            const d2_t r0 = *reinterpret_cast<const d2_t*>(rr);
+            const d2_t r1 = *reinterpret_cast<const d2_t*>(rr + 2);
+            const d2_t r2 = *reinterpret_cast<const d2_t*>(rr + 32);
+            const d2_t r3 = *reinterpret_cast<const d2_t*>(rr + 34);
+            const double rv[8] = {r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, r3.x, r3.y};
+            const double ai = ab[gi], qi = qb[gi], gg = gb[gi];
+            double sp = 0.0;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int gj = tj * 64 + R8(tc, q);
+                const double m = 0.5 * (fma(ai, ak[q], rv[q]) + fma(qi, gk[q], gg * qk[q]));
+                const double cnt = (gi > gj) ? 2.0 : 1.0;
+                const bool in = gi < n && gj <= gi;  // (gj <= gi < n)
+                sp += in ? cnt * (m * w[p][q]) : 0.0;
+            }
+            sl += sp;
+        }
+    }
+    sl = wave_sum_d(sl);
+    if (lane == 0) red[wv] = sl;
+    __syncthreads();
+    if (tid == 0)
+        part[b * pstride + (int64_t)t * P + P - 1] =
+            exp(th[P - 1]) * (((red[0] + red[1]) + red[2]) + red[3]);
 }
 
 void launch_grad_reduce(MatB K, MatB Rn, const double* X, int64_t ldx, int n, int d, int nb,
@@ -404,11 +495,16 @@ void launch_grad_reduce(MatB K, MatB Rn, const double* X, int64_t ldx, int n, in
     const KernelKind kk = kernel_kind_of(kind);
     APM_FAMILY_DISPATCH(
         kk.family,
-        APM_BIAS_DISPATCH(kk.bias,
-                          APM_LAUNCH((k_grad_reduce<FAM, BIAS>), dim3(ns * (ns + 1) / 2, nchains),
-                                     dim3(256), 0, s, K, Rn, X, ldx, n, d, nb, theta, tstride,
-                                     kk.iso ? 0 : 1, a, vstride, q, g, gstride, part, pstride, P,
-                                     live)));
+        APM_BIAS_DISPATCH(
+            kk.bias,
+            APM_LINEAR_DISPATCH(kk.linear, APM_LAUNCH((k_grad_reduce<FAM, BIAS, LIN>),
+                                                      dim3(ns * (ns + 1) / 2, nchains), dim3(256),
+                                                      0, s, K, Rn, X, ldx, n, d, nb, theta, tstride,
+                                                      kk.iso ? 0 : 1, a, vstride, q, g, gstride,
+                                                      part, pstride, P, live))));
+    if (kk.linear)
+        APM_LAUNCH(k_grad_lin, dim3(ns * (ns + 1) / 2, nchains), dim3(256), 0, s, Rn, X, ldx, n, d,
+                   nb, theta, tstride, a, vstride, q, g, gstride, part, pstride, P, live);
 }
 
 // grad[b][p] = the nst super-tile partials of (chain b, parameter p) added in tile order

@@ -29,7 +29,16 @@
 // ard: theta[1 + k] scales feature k (ARD), else theta[1] scales every feature (iso).
 // BIAS: the constant term: beta = exp of theta's last entry is added to cov_S for
 // the data pairs only, K_ii = (s + beta) + eps; a padded row or column never sees it.
-template <int FAM, bool BIAS>
+// LIN: the linear term (the SE family only): lambda = exp of theta's last entry
+// (beta is then the one before it). A sweep of its own over the feature chunks stages the unscaled
+// inputs into the same LDS image and sums x_i . x_j in the lane's 8x8 block by one fma per feature,
+// k in order (pair_dot_chunk). There is no room for a second 8x8 block, and adding the features
+// onto cov_S [+ beta] one by one would round d times at the size of K instead of once; so the
+// dot products are parked in the lane's own entries of the K tile, which it overwrites below,
+// while the block serves the distance sweep, and the epilogue reads them back:
+// K_ij = fma(lambda, x_i . x_j, cov_S [+ beta]), K_ii = fma(lambda, |x_i|^2, s [+ beta]) + eps.
+// The identity padding is selected as before: a padded row or column never sees lambda.
+template <int FAM, bool BIAS, bool LIN>
 __global__ __launch_bounds__(256, 2) void k_gram(MatB K, const double* __restrict__ X, int64_t ldx,
                                                  int n, int d, const double* __restrict__ theta,
                                                  int64_t tstride, int ard, double eps, Live live,
@@ -49,6 +58,8 @@ __global__ __launch_bounds__(256, 2) void k_gram(MatB K, const double* __restric
     const double sigma = exp(th[0]);
     double beta = 0.0;
     if constexpr (BIAS) beta = exp(th[ard ? d + 1 : 2]);
+    double lam = 0.0;
+    if constexpr (LIN) lam = exp(th[(ard ? d + 1 : 2) + (BIAS ? 1 : 0)]);
 
     double acc[8][8];
 #pragma unroll
@@ -56,6 +67,21 @@ __global__ __launch_bounds__(256, 2) void k_gram(MatB K, const double* __restric
 #pragma unroll
         for (int q = 0; q < 8; ++q) acc[p][q] = 0.0;
 
+    double* Kb = K.base + b * K.cstride;
+    if constexpr (LIN) {
+        for (int k0 = 0; k0 < d; k0 += GK) {
+            const int kc = min(GK, d - k0);
+            pair_stage<true>(lds, th, ard, k0, kc, X, ldx, n, si * 128, X, ldx, n, sj * 128);
+            if (mine) pair_dot_chunk(lds, kc, ro, tr, co, tc, acc);
+        }
+        if (mine) {
+            pair_store_tile(Kb + (int64_t)ti * 64 * K.ld + tj * 64, K.ld, tr, tc, acc);
+#pragma unroll
+            for (int p = 0; p < 8; ++p)
+#pragma unroll
+                for (int q = 0; q < 8; ++q) acc[p][q] = 0.0;
+        }
+    }
     for (int k0 = 0; k0 < d; k0 += GK) {
         const int kc = min(GK, d - k0);
         pair_stage(lds, th, ard, k0, kc, X, ldx, n, si * 128, X, ldx, n, sj * 128);
@@ -64,12 +90,21 @@ __global__ __launch_bounds__(256, 2) void k_gram(MatB K, const double* __restric
     if (!mine) return;  // (after the last barrier)
 
 #pragma unroll
-    for (int p = 0; p < 8; ++p)
+    for (int p = 0; p < 8; ++p) {
+        double dt[8];  // (LIN: the row's parked dot products)
+        if constexpr (LIN)
+            pair_load_row(Kb + ((int64_t)ti * 64 + R8(tr, p)) * K.ld + tj * 64 + 4 * tc, dt);
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             const int gi = ti * 64 + R8(tr, p), gj = tj * 64 + R8(tc, q);
             double val;
-            if constexpr (BIAS) {
+            if constexpr (LIN) {
+                if (gi < n && gj < n)
+                    val = (gi == gj) ? fma(lam, dt[q], sigma + beta) + eps
+                                     : fma(lam, dt[q], cov_S<FAM>(sigma, acc[p][q]) + beta);
+                else
+                    val = (gi == gj) ? 1.0 : 0.0;
+            } else if constexpr (BIAS) {
                 if (gi < n && gj < n)
                     val = (gi == gj) ? (sigma + beta) + eps : cov_S<FAM>(sigma, acc[p][q]) + beta;
                 else
@@ -81,7 +116,7 @@ __global__ __launch_bounds__(256, 2) void k_gram(MatB K, const double* __restric
                 val = (gi == gj) ? 1.0 : 0.0;
             acc[p][q] = val;
         }
-    double* Kb = K.base + b * K.cstride;
+    }
     if (GRAM_ABL == 2 && acc[0][0] != -1.0) return;
     pair_store_tile(Kb + (int64_t)ti * 64 * K.ld + tj * 64, K.ld, tr, tc, acc);
     if (K2.base && tj < k2cols)
@@ -104,7 +139,10 @@ void launch_gram(MatB K, const double* X, int64_t ldx, int n, int d, const doubl
     const KernelKind kk = kernel_kind_of(kind);
     APM_FAMILY_DISPATCH(
         kk.family,
-        APM_BIAS_DISPATCH(kk.bias, APM_LAUNCH((k_gram<FAM, BIAS>), dim3(ns * (ns + 1) / 2, nchains),
-                                              dim3(256), 0, s, K, X, ldx, n, d, theta, tstride,
-                                              kk.iso ? 0 : 1, eps, live, (int)both, K2, k2cols, nb)));
+        APM_BIAS_DISPATCH(
+            kk.bias,
+            APM_LINEAR_DISPATCH(kk.linear,
+                                APM_LAUNCH((k_gram<FAM, BIAS, LIN>), dim3(ns * (ns + 1) / 2, nchains),
+                                           dim3(256), 0, s, K, X, ldx, n, d, theta, tstride,
+                                           kk.iso ? 0 : 1, eps, live, (int)both, K2, k2cols, nb))));
 }

@@ -207,6 +207,12 @@ void init_ctx(apm_ctx* c, int device, int kind, const double* X, int64_t n, int6
         for (int64_t i = 0; i < n; ++i)
             for (int64_t k = 0; k < d; ++k) Xc[i * d + k] = X[i * ldx + k];
         HIPC(hipMemcpy(c->X, Xc.data(), sizeof(double) * n * d, hipMemcpyHostToDevice));
+        for (int64_t i = 0; i < n; ++i) {  // (the range flags of a kind with the linear term)
+            double s = 0.0;
+            for (int64_t k = 0; k < d; ++k) s += Xc[i * d + k] * Xc[i * d + k];
+            c->x2max = std::max(c->x2max, s);
+            c->x2sum += s;
+        }
     }
     c->y = dalloc<double>(c, np);
     std::vector<double> yp((size_t)np, 0.0);

@@ -89,10 +89,11 @@ void is_predict_tail(apm_ctx* c, int count, const double* thetas, int64_t ldt, i
     for (int64_t r0 = 0; r0 < m; r0 += np) {
         const int ms = in.upload(r0), mb = (ms + 63) / 64;
         launch_gram_cross(c->A, np, c->pxs, ms, mb, c->X, c->d, c->n, c->d, nb, c->theta, c->P,
-                          c->psig, c->pbet, c->kind, c->is_ones, c->v.a, vs, c->ppart,
+                          c->psig, c->pbet, c->plam, c->kind, c->is_ones, c->v.a, vs, c->ppart,
                           (int64_t)nb * np, lv, 0, count, s);
         chol_solve_rows(c, TL, nb, /*row_start=*/nb, /*R=*/nb + mb, /*Cb=*/nb, count);
-        launch_is_rows(c->A, np, ms, mb, nb, c->pkss, c->ppart, (int64_t)nb * np, c->is_vstar,
+        launch_is_rows(c->A, np, ms, mb, nb, c->pkss, c->plam, c->pxn, c->ppart, (int64_t)nb * np,
+                       c->is_vstar,
                        c->is_c, np, lv, count, s);
         chol_solve_rows(c, TR, nb, /*row_start=*/nb, /*R=*/nb + mb, /*Cb=*/nb, count, so);
         launch_is_pred_gemm(c->lik, c->A, np, np, np, mb, c->is_ut, c->sp, c->is_w, c->is_vstar,

@@ -82,14 +82,17 @@ int laplace_then_live(apm_ctx* c, int count, double* lml, int* status, int64_t* 
 void predict_buffers(apm_ctx* c) {
     if (c->pxs) return;
     const int64_t np = c->np, B = c->max_batch;
-    c->pxs = dalloc<double>(c, np * std::max(c->d, 1));
+    const bool lin = kernel_kind_of(c->kind).linear != 0;
+    c->pxs = dalloc<double>(c, np * std::max(c->d, 1) + (lin ? np : 0));
+    if (lin) c->pxn = c->pxs + np * std::max(c->d, 1);
     c->ppart = dalloc<double>(c, B * c->nb * np);
-    c->pmean = dalloc<double>(c, 3 * B * np + 3 * B);
+    c->pmean = dalloc<double>(c, 3 * B * np + (lin ? 4 : 3) * B);
     c->pvar = c->pmean + B * np;
     c->pprob = c->pvar + B * np;
     c->psig = c->pprob + B * np;
     c->pkss = c->psig + B;
     c->pbet = c->pkss + B;
+    if (lin) c->plam = c->pbet + B;
 }
 
 void predict_block(apm_ctx* c, int count, int ms) {
@@ -97,34 +100,46 @@ void predict_block(apm_ctx* c, int count, int ms) {
     const int nb = c->nb, mb = (ms + 63) / 64;
     const int64_t np = c->np;
     launch_gram_cross(c->A, np, c->pxs, ms, mb, c->X, c->d, c->n, c->d, nb, c->theta, c->P,
-                      c->psig, c->pbet, c->kind, c->v.Ws, c->v.a, c->v.vstride, c->ppart, nb * np,
-                      lv, 0, count, c->stream);
+                      c->psig, c->pbet, c->plam, c->kind, c->v.Ws, c->v.a, c->v.vstride, c->ppart,
+                      nb * np, lv, 0, count, c->stream);
     chol_solve_rows(c, c->A, nb, /*row_start=*/nb, /*R=*/nb + mb, /*Cb=*/nb, count);
-    launch_predict_reduce(c->lik, c->A, np, ms, mb, nb, c->pkss, c->ppart, nb * np, c->pmean,
-                          c->pvar, c->pprob, np, lv, count, c->stream);
+    launch_predict_reduce(c->lik, c->A, np, ms, mb, nb, c->pkss, c->plam, c->pxn, c->ppart,
+                          nb * np, c->pmean, c->pvar, c->pprob, np, lv, count, c->stream);
 }
 
 TestInputs::TestInputs(apm_ctx* c_, int count_, const double* thetas, int64_t ldt,
                        const double* Xs_, int64_t m_, int64_t ldxs_)
-    : c(c_), count(count_), Xs(Xs_), m(m_), ldxs(ldxs_), sig((size_t)(3 * c_->max_batch)) {
+    : c(c_), count(count_), Xs(Xs_), m(m_), ldxs(ldxs_), sig((size_t)(4 * c_->max_batch)) {
     predict_buffers(c);
-    const int B = c->max_batch;  // [s | s + beta | beta], the layout of psig / pkss / pbet
+    // [s | s + beta | beta | lambda], the layout of psig / pkss / pbet / plam (the last one for a
+    // kind with the linear term only)
+    const int B = c->max_batch;
     for (int b = 0; b < count; ++b) {
         sig[b] = std::exp(thetas[b * ldt]);
         sig[2 * B + b] = cov_beta(c->kind, c->P, thetas + b * ldt);
         sig[B + b] = sig[b] + sig[2 * B + b];
+        sig[3 * B + b] = cov_lambda(c->kind, c->P, thetas + b * ldt);
     }
-    HIPC(hipMemcpyAsync(c->psig, sig.data(), sizeof(double) * 3 * B, hipMemcpyHostToDevice,
-                        c->stream));
+    HIPC(hipMemcpyAsync(c->psig, sig.data(), sizeof(double) * (c->plam ? 4 : 3) * B,
+                        hipMemcpyHostToDevice, c->stream));
 }
 
 int TestInputs::upload(int64_t r0) {
     const int ms = (int)std::min<int64_t>(c->np, m - r0);
-    xs.resize((size_t)ms * c->d);
+    xs.resize((size_t)ms * c->d + (c->pxn ? ms : 0));
     for (int i = 0; i < ms; ++i)
         for (int k = 0; k < c->d; ++k) xs[(size_t)i * c->d + k] = Xs[(r0 + i) * ldxs + k];
     HIPC(hipMemcpyAsync(c->pxs, xs.data(), sizeof(double) * ms * c->d, hipMemcpyHostToDevice,
                         c->stream));
+    if (c->pxn) {  // |x*_i|^2, features in order
+        double* xn = xs.data() + (size_t)ms * c->d;
+        for (int i = 0; i < ms; ++i) {
+            double s = 0.0;
+            for (int k = 0; k < c->d; ++k) s = std::fma(xs[(size_t)i * c->d + k], xs[(size_t)i * c->d + k], s);
+            xn[i] = s;
+        }
+        HIPC(hipMemcpyAsync(c->pxn, xn, sizeof(double) * ms, hipMemcpyHostToDevice, c->stream));
+    }
     return ms;
 }
 

@@ -97,6 +97,8 @@ void launch_is_ut(UPool P, const int64_t* ubufs, int np, double* Ut, Live live, 
 // (the right-hand side of the solve against L'). Rows >= ms are exact zeros (k_gram_cross).
 __global__ __launch_bounds__(256) void k_is_rows(MatB A, int64_t row0, int ms, int mb, int nb,
                                                  const double* __restrict__ sig,
+                                                 const double* __restrict__ lam,
+                                                 const double* __restrict__ xsn,
                                                  const double* __restrict__ part, int64_t pstride,
                                                  double* __restrict__ vstar,
                                                  double* __restrict__ cvec, int64_t ostride,
@@ -111,15 +113,17 @@ __global__ __launch_bounds__(256) void k_is_rows(MatB A, int64_t row0, int ms, i
         *reinterpret_cast<d2_t*>(row + np + (np - 2 - c)) = d2_t{v.y, v.x};
     });
     if (lane != 0) return;
-    vstar[b * ostride + r] = sig[b] - s;
+    // (lam: null unless the kind has the linear term; rows >= ms keep sig[b])
+    vstar[b * ostride + r] = ((lam && r < ms) ? fma(lam[b], xsn[r], sig[b]) : sig[b]) - s;
     cvec[b * ostride + r] = r < ms ? sum_tile_partials(part + b * pstride + r, nb, 64 * mb) : 0.0;
 }
 
 void launch_is_rows(MatB A, int64_t row0, int ms, int mb, int nb, const double* sig,
-                    const double* part, int64_t pstride, double* vstar, double* cvec,
-                    int64_t ostride, Live live, int nchains, hipStream_t s) {
-    APM_LAUNCH(k_is_rows, dim3(16 * mb, nchains), dim3(256), 0, s, A, row0, ms, mb, nb, sig, part,
-               pstride, vstar, cvec, ostride, live);
+                    const double* lam, const double* xsn, const double* part, int64_t pstride,
+                    double* vstar, double* cvec, int64_t ostride, Live live, int nchains,
+                    hipStream_t s) {
+    APM_LAUNCH(k_is_rows, dim3(16 * mb, nchains), dim3(256), 0, s, A, row0, ms, mb, nb, sig, lam,
+               xsn, part, pstride, vstar, cvec, ostride, live);
 }
 
 // ------------------------------------------------------------------------------- the link

@@ -26,7 +26,9 @@ struct PairTile {
 // Features [k0, k0 + kc) of rows [i0, i0 + 128) of Xi and of rows [j0, j0 + 128) of Xj -> LDS,
 // pre-scaled; zeros for rows beyond ni (nj) and features beyond kc. The first barrier ends the
 // reads of the previous chunk, the last one publishes this one. ard: th[1 + k] scales feature k,
-// else th[1] every feature.
+// else th[1] every feature. RAW: the features as they are (the linear term's dot products are on
+// the unscaled inputs): th, ard and itau are not touched.
+template <bool RAW = false>
 __device__ __forceinline__ void pair_stage(PairTile& s, const double* __restrict__ th, int ard,
                                            int k0, int kc, const double* __restrict__ Xi,
                                            int64_t ldi, int ni, int i0,
@@ -34,12 +36,14 @@ __device__ __forceinline__ void pair_stage(PairTile& s, const double* __restrict
                                            int j0) {
     const int tid = threadIdx.x;
     __syncthreads();
-    if (tid < kc) s.itau[tid] = exp(-th[ard ? 1 + k0 + tid : 1]);
-    __syncthreads();
+    if constexpr (!RAW) {
+        if (tid < kc) s.itau[tid] = exp(-th[ard ? 1 + k0 + tid : 1]);
+        __syncthreads();
+    }
     for (int e = tid; e < 128 * GK; e += 256) {
         const int r = e / GK, k = e % GK;  // consecutive lanes: consecutive features of a row
         const int gi = i0 + r, gj = j0 + r;
-        const double sc = (k < kc) ? s.itau[k] : 0.0;
+        const double sc = RAW ? 1.0 : ((k < kc) ? s.itau[k] : 0.0);
         s.xi[k][r] = (k < kc && gi < ni) ? Xi[(int64_t)gi * ldi + k0 + k] * sc : 0.0;
         s.xj[k][r] = (k < kc && gj < nj) ? Xj[(int64_t)gj * ldj + k0 + k] * sc : 0.0;
     }
@@ -81,6 +85,31 @@ __device__ __forceinline__ void pair_r2_chunk(const PairTile& s, int kc, int ro,
             for (int q = 0; q < 8; ++q) acc[p][q] = fma(df[q], df[q], acc[p][q]);
         }
     }
+}
+
+// acc[p][q] += the staged (RAW) chunk's share of x_i . x_j of pair (row R8(tr, p), column
+// R8(tc, q)): one fma per feature, k in order. The product inside an fma is exact, so (i, j) and
+// (j, i) of a diagonal tile get the same bits.
+__device__ __forceinline__ void pair_dot_chunk(const PairTile& s, int kc, int ro, int tr, int co,
+                                               int tc, double (&acc)[8][8]) {
+    for (int k = 0; k < kc; ++k) {
+        double a[8], c[8];
+        pair_operands(s, k, ro, tr, co, tc, a, c);
+#pragma unroll
+        for (int p = 0; p < 8; ++p)
+#pragma unroll
+            for (int q = 0; q < 8; ++q) acc[p][q] = fma(a[p], c[q], acc[p][q]);
+    }
+}
+
+// pair_store_row's inverse: the lane's 8 values of one row back from src
+__device__ __forceinline__ void pair_load_row(const double* src, double (&v)[8]) {
+    const d2_t v0 = *reinterpret_cast<const d2_t*>(src);
+    const d2_t v1 = *reinterpret_cast<const d2_t*>(src + 2);
+    const d2_t v2 = *reinterpret_cast<const d2_t*>(src + 32);
+    const d2_t v3 = *reinterpret_cast<const d2_t*>(src + 34);
+    v[0] = v0.x, v[1] = v0.y, v[2] = v1.x, v[3] = v1.y;
+    v[4] = v2.x, v[5] = v2.y, v[6] = v3.x, v[7] = v3.y;
 }
 
 // A lane's 8 values of one row (columns R8(g, 0..7) of the tile) as four 16-byte stores; dst: the

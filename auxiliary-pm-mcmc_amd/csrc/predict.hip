@@ -25,12 +25,19 @@
 // BIAS: the constant term beta = bet[b] (the host's exp, as s is) is added to every k* of a test
 // row r < ms and a training column c < n; the prior variance sig[b] that k_predict_reduce and
 // k_is_rows read is then s + beta.
-template <int FAM, bool BIAS>
+// LIN: the linear term: lambda = lam[b] (the host's exp, as s and beta are) times
+// the dot product of the raw inputs is added to every k* of a test row r < ms and a training
+// column c < n as k_gram does it: a sweep of its own sums the dot products (pair_dot_chunk), they
+// are parked in the lane's own entries of the output, which it overwrites below, and the epilogue
+// takes fma(lambda, x*_r . x_c, cov_S [+ beta]). The prior variance then differs by test row,
+// k** = sig[b] + lam[b] |x*_r|^2 (k_predict_reduce, k_is_rows).
+template <int FAM, bool BIAS, bool LIN>
 __global__ __launch_bounds__(256, 2) void k_gram_cross(
     MatB out, int64_t row0, const double* __restrict__ Xs, int ms, int mb,
     const double* __restrict__ X, int64_t ldx, int n, int d, int nb,
     const double* __restrict__ theta, int64_t tstride, const double* __restrict__ sig,
-    const double* __restrict__ bet, int ard, const double* __restrict__ Ws, const double* __restrict__ avec, int64_t vstride,
+    const double* __restrict__ bet, const double* __restrict__ lamv, int ard,
+    const double* __restrict__ Ws, const double* __restrict__ avec, int64_t vstride,
     double* __restrict__ part, int64_t pstride, Live live, int plain) {
     const int b = blockIdx.y;
     if (live.active && !live_chain(live, b)) return;
@@ -47,6 +54,8 @@ __global__ __launch_bounds__(256, 2) void k_gram_cross(
     const double sigma = sig[b];
     double beta = 0.0;
     if constexpr (BIAS) beta = bet[b];
+    double lam = 0.0;
+    if constexpr (LIN) lam = lamv[b];
 
     double acc[8][8];
 #pragma unroll
@@ -54,6 +63,31 @@ __global__ __launch_bounds__(256, 2) void k_gram_cross(
 #pragma unroll
         for (int q = 0; q < 8; ++q) acc[p][q] = 0.0;
 
+    if constexpr (LIN) {
+        for (int k0 = 0; k0 < d; k0 += GK) {
+            const int kc = min(GK, d - k0);
+            pair_stage<true>(lds, th, ard, k0, kc, Xs, d, ms, si * 128, X, ldx, n, sj * 128);
+            if (mine) pair_dot_chunk(lds, kc, ro, tr, co, tc, acc);
+        }
+        if (mine) {  // park the dot products where this lane's own results go
+#pragma unroll
+            for (int p = 0; p < 8; ++p) {
+                if (plain) {
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) {
+                        const int gi = ti * 64 + R8(tr, p), gj = tj * 64 + R8(tc, q);
+                        if (gi < ms && gj < n) out.base[(int64_t)gi * out.ld + gj] = acc[p][q];
+                    }
+                } else {
+                    pair_store_row(out.base + b * out.cstride +
+                                       (row0 + ti * 64 + R8(tr, p)) * out.ld + tj * 64 + 4 * tc,
+                                   acc[p]);
+                }
+#pragma unroll
+                for (int q = 0; q < 8; ++q) acc[p][q] = 0.0;
+            }
+        }
+    }
     for (int k0 = 0; k0 < d; k0 += GK) {
         const int kc = min(GK, d - k0);
         pair_stage(lds, th, ard, k0, kc, Xs, d, ms, si * 128, X, ldx, n, sj * 128);
@@ -62,15 +96,34 @@ __global__ __launch_bounds__(256, 2) void k_gram_cross(
     if (!mine) return;  // (after the last barrier)
 
 #pragma unroll
-    for (int p = 0; p < 8; ++p)
+    for (int p = 0; p < 8; ++p) {
+        double dt[8];  // (LIN: the row's parked dot products)
+        if constexpr (LIN) {
+            if (plain) {
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const int gi = ti * 64 + R8(tr, p), gj = tj * 64 + R8(tc, q);
+                    dt[q] = (gi < ms && gj < n) ? out.base[(int64_t)gi * out.ld + gj] : 0.0;
+                }
+            } else {
+                pair_load_row(out.base + b * out.cstride +
+                                  (row0 + ti * 64 + R8(tr, p)) * out.ld + tj * 64 + 4 * tc,
+                              dt);
+            }
+        }
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             const int gi = ti * 64 + R8(tr, p), gj = tj * 64 + R8(tc, q);
-            if constexpr (BIAS)
+            if constexpr (LIN)
+                acc[p][q] = (gi < ms && gj < n)
+                                ? fma(lam, dt[q], cov_S<FAM>(sigma, acc[p][q]) + beta)
+                                : 0.0;
+            else if constexpr (BIAS)
                 acc[p][q] = (gi < ms && gj < n) ? cov_S<FAM>(sigma, acc[p][q]) + beta : 0.0;
             else
                 acc[p][q] = (gi < ms && gj < n) ? cov_S<FAM>(sigma, acc[p][q]) : 0.0;
         }
+    }
 
     if (plain) {  // apm_gram_cross: k* itself into an ms x n buffer (any ld: scalar stores)
 #pragma unroll
@@ -114,17 +167,20 @@ __global__ __launch_bounds__(256, 2) void k_gram_cross(
 
 void launch_gram_cross(MatB out, int64_t row0, const double* Xs, int ms, int mb, const double* X,
                        int64_t ldx, int n, int d, int nb, const double* theta, int64_t tstride,
-                       const double* sig, const double* bet, int kind, const double* Ws,
-                       const double* a, int64_t vstride, double* part, int64_t pstride, Live live,
-                       int plain, int nchains, hipStream_t s) {
+                       const double* sig, const double* bet, const double* lam, int kind,
+                       const double* Ws, const double* a, int64_t vstride, double* part,
+                       int64_t pstride, Live live, int plain, int nchains, hipStream_t s) {
     const int nsr = (mb + 1) / 2, nsc = (nb + 1) / 2;
     const KernelKind kk = kernel_kind_of(kind);
     APM_FAMILY_DISPATCH(
         kk.family,
-        APM_BIAS_DISPATCH(kk.bias, APM_LAUNCH((k_gram_cross<FAM, BIAS>), dim3(nsr * nsc, nchains),
-                                              dim3(256), 0, s, out, row0, Xs, ms, mb, X, ldx, n, d,
-                                              nb, theta, tstride, sig, bet, kk.iso ? 0 : 1, Ws, a,
-                                              vstride, part, pstride, live, plain)));
+        APM_BIAS_DISPATCH(
+            kk.bias,
+            APM_LINEAR_DISPATCH(kk.linear,
+                                APM_LAUNCH((k_gram_cross<FAM, BIAS, LIN>), dim3(nsr * nsc, nchains),
+                                           dim3(256), 0, s, out, row0, Xs, ms, mb, X, ldx, n, d, nb,
+                                           theta, tstride, sig, bet, lam, kk.iso ? 0 : 1, Ws, a,
+                                           vstride, part, pstride, live, plain))));
 }
 
 // One wave per (chain, test row): the squared norm of the row of V^T = (W^1/2 . k*)^T L^-T over
@@ -142,6 +198,7 @@ void launch_gram_cross(MatB out, int64_t row0, const double* Xs, int ms, int mb,
 template <int LIK>
 __global__ __launch_bounds__(256) void k_predict_reduce(
     MatB A, int64_t row0, int ms, int mb, int nb, const double* __restrict__ sig,
+    const double* __restrict__ lam, const double* __restrict__ xsn,
     const double* __restrict__ part, int64_t pstride, double* __restrict__ mean,
     double* __restrict__ var, double* __restrict__ prob, int64_t ostride, Live live) {
     const int b = blockIdx.y;
@@ -151,7 +208,8 @@ __global__ __launch_bounds__(256) void k_predict_reduce(
     // (every lane has the norm, mu* and v; the logit's wave stays whole)
     const double s = row_sqnorm_d2(A.base + b * A.cstride + (row0 + r) * A.ld, 64 * nb, lane);
     const double mu = sum_tile_partials(part + b * pstride + r, nb, 64 * mb);
-    const double v = sig[b] - s;
+    // (lam: null unless the kind has the linear term; xsn is then not read either)
+    const double v = (lam ? fma(lam[b], xsn[r], sig[b]) : sig[b]) - s;
     if constexpr (LIK == APM_LIK_LOGIT) {
         const double sd = v > 0.0 ? sqrt(2.0 * v) : 0.0;
         double acc = 0.0;
@@ -175,10 +233,10 @@ __global__ __launch_bounds__(256) void k_predict_reduce(
 }
 
 void launch_predict_reduce(int lik, MatB A, int64_t row0, int ms, int mb, int nb,
-                           const double* sig, const double* part, int64_t pstride, double* mean,
-                           double* var, double* prob, int64_t ostride, Live live, int nchains,
-                           hipStream_t s) {
+                           const double* sig, const double* lam, const double* xsn,
+                           const double* part, int64_t pstride, double* mean, double* var,
+                           double* prob, int64_t ostride, Live live, int nchains, hipStream_t s) {
     APM_LIK_DISPATCH(lik, APM_LAUNCH(k_predict_reduce<LIK>, dim3((ms + 3) / 4, nchains), dim3(256),
-                                     0, s, A, row0, ms, mb, nb, sig, part, pstride, mean, var,
-                                     prob, ostride, live));
+                                     0, s, A, row0, ms, mb, nb, sig, lam, xsn, part, pstride, mean,
+                                     var, prob, ostride, live));
 }

@@ -21,11 +21,15 @@ _ISO_KINDS = (KERNEL_ISO, KERNEL_M32_ISO, KERNEL_M52_ISO)
 # APM_COV_BIAS: OR-ed onto one of the six device kinds, the constant term beta = exp(theta[-1])
 # (theta has one more entry)
 COV_BIAS = 16
+# APM_COV_LINEAR: OR-ed onto KERNEL_ISO or KERNEL_ARD (with or without COV_BIAS), the linear term
+# lambda x x^T with lambda = exp(theta[-1]); beta is then exp(theta[-2])
+COV_LINEAR = 64
 
 
 def theta_len(kind, d):
     """Entries of theta that covariance kind `kind` reads at d features."""
-    return (2 if (kind & ~COV_BIAS) in _ISO_KINDS else d + 1) + (1 if kind & COV_BIAS else 0)
+    return ((2 if (kind & ~(COV_BIAS | COV_LINEAR)) in _ISO_KINDS else d + 1)
+            + (1 if kind & COV_BIAS else 0) + (1 if kind & COV_LINEAR else 0))
 
 EST_IS, EST_PRIORMC, EST_LAPLACE = 0, 1, 2
 EST_IS_EP = 3  # EST_IS with the EP fit's posterior as the importance distribution (probit)

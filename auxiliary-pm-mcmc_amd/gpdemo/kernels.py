@@ -22,6 +22,12 @@ plus ``epsilon`` on the diagonal (one point set's Gram only).
 ``beta = exp(theta[-1])`` one more, last entry of ``theta`` - a N(0, beta) prior on a constant
 offset of the latent function, integrated out. The cross-covariance gains ``beta`` as well and
 the prior variance at a test point is ``s + beta``.
+
+``linear=True`` ('iso' and 'ard' only, with or without ``bias``) adds the linear term
+``lambda X X^T`` on the raw (unscaled) inputs, ``lambda = exp(theta[-1])`` one more, last entry -
+a N(0, lambda I) prior on the weights of a linear function of the inputs, integrated out; with
+both, ``beta = exp(theta[-2])``. The cross-covariance gains ``lambda x* . x`` and the prior
+variance at a test point is ``s [+ beta] + lambda |x*|^2``.
 """
 from . import _native
 
@@ -64,22 +70,26 @@ def diagonal_matern52_kernel(K, X, theta, epsilon=1e-8):
 class SEKernelFunc(object):
     """``kernel_func(K, X, theta)`` for the isotropic ('iso') or ARD ('ard') SE kernel."""
 
-    def __init__(self, kind, epsilon=1e-8, bias=False):
+    def __init__(self, kind, epsilon=1e-8, bias=False, linear=False):
         if kind not in ('iso', 'ard'):
             raise ValueError("kind must be 'iso' or 'ard'")
         self.kind = kind
         self.epsilon = float(epsilon)
         self.bias = bool(bias)
+        self.linear = bool(linear)
         self.native_kind = _native.KERNEL_ISO if kind == 'iso' else _native.KERNEL_ARD
         if self.bias:
             self.native_kind |= _native.COV_BIAS
+        if self.linear:
+            self.native_kind |= _native.COV_LINEAR
 
     def __call__(self, K, X, theta):
         _native.gram(self.native_kind, K, X, theta, self.epsilon)
 
     def __repr__(self):
-        return 'SEKernelFunc({0!r}, epsilon={1!r}{2})'.format(self.kind, self.epsilon,
-                                                             ', bias=True' if self.bias else '')
+        return 'SEKernelFunc({0!r}, epsilon={1!r}{2}{3})'.format(
+            self.kind, self.epsilon, ', bias=True' if self.bias else '',
+            ', linear=True' if self.linear else '')
 
 
 _MATERN_KINDS = {'matern32_iso': _native.KERNEL_M32_ISO, 'matern32_ard': _native.KERNEL_M32_ARD,
@@ -108,11 +118,15 @@ class MaternKernelFunc(object):
             self.kind, self.epsilon, ', bias=True' if self.bias else '')
 
 
-def make_kernel_func(kind, epsilon=1e-8, bias=False):
+def make_kernel_func(kind, epsilon=1e-8, bias=False, linear=False):
     """'iso' | 'ard' (SE) or 'matern32_iso' | 'matern32_ard' | 'matern52_iso' | 'matern52_ard';
-    bias=True adds the constant term exp(theta[-1]) (theta has one more entry)."""
+    bias=True adds the constant term exp(theta[-1]) (theta has one more entry); linear=True
+    ('iso' and 'ard' only) the linear term exp(theta[-1]) x x^T (one more entry again, the last;
+    the constant term's is then theta[-2])."""
+    if linear and kind not in ('iso', 'ard'):
+        raise ValueError("linear=True needs kind 'iso' or 'ard'")
     if kind in _MATERN_KINDS:
         return MaternKernelFunc(kind, epsilon, bias)
     if kind in ('iso', 'ard'):
-        return SEKernelFunc(kind, epsilon, bias)
+        return SEKernelFunc(kind, epsilon, bias, linear)
     raise ValueError("kind must be 'iso', 'ard' or one of {0}".format(sorted(_MATERN_KINDS)))

@@ -88,6 +88,17 @@ extern "C" {
  * and to the prior variance k** = s + beta; dK/dtheta_{P-1} = beta on every data pair. Accepted
  * wherever the base kinds are; gradients have P entries. */
 #define APM_COV_BIAS 16
+/* Linear (dot-product) term, a flag OR-ed onto APM_KERNEL_ISO or APM_KERNEL_ARD, with or without
+ * APM_COV_BIAS (kinds 64, 65, 80, 81; refused on a Matern kind and on APM_KERNEL_PRECOMPUTED):
+ * K = S [+ beta 1 1^T] + lambda X X^T + epsilon I, a N(0, lambda I) prior on the weights of a
+ * linear function of the raw (unscaled) inputs, integrated out. theta gains one entry, the last
+ * one: lambda = exp(theta[P - 1]) with P = apm_theta_len = the base kind's length [+ 1] + 1; with
+ * both flags beta = exp(theta[P - 2]). K_ii = s [+ beta] + lambda |x_i|^2 + epsilon, the
+ * cross-covariance gains lambda x*_i . x_j (no epsilon) and the prior variance at a test point is
+ * s [+ beta] + lambda |x*_i|^2; dK/dtheta_{P-1} = lambda x_i . x_j on every data pair. Accepted
+ * wherever the base kinds are; gradients have P entries. A caller detects the feature by this
+ * macro (apm_version() is unchanged). */
+#define APM_COV_LINEAR 64
 
 /* estimators */
 #define APM_EST_IS 0       /* LogMarginalLikelihoodApproxPosteriorISEstimator */
