@@ -12,7 +12,7 @@
 // a weight that underflowed) adds exactly nothing.
 #include "apm_internal.h"
 #include "gh_logit.h"
-#include "tile64.h"
+#include "ugemm_tile.h"
 
 // e^(t - m), exactly 0 for t = -inf whatever m is (m = -inf too where every t is)
 __device__ __forceinline__ double loo_scaled(double t, double m) {
@@ -85,7 +85,6 @@ void launch_is_logw(const double* partial, int64_t pstride, int nb, int S, int s
 struct LooEpi {
     double v[5][64][2];
 };
-#define LOO_ROW32(l, r) (((l) >> 4) * 4 + (r))  // v_mfma_f32_16x16x4_f32's C/D row
 
 template <int LIK, bool F64MAP>
 __device__ __forceinline__ void loo_epilogue(const double (&f)[2][2][4], int row0, int n,
@@ -100,7 +99,7 @@ __device__ __forceinline__ void loo_epilogue(const double (&f)[2][2][4], int row
     for (int bi = 0; bi < 2; ++bi)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int rl = 32 * wr + 16 * bi + (F64MAP ? F64_CROW(lane, r) : LOO_ROW32(lane, r));
+            const int rl = 32 * wr + 16 * bi + (F64MAP ? F64_CROW(lane, r) : F32_CROW(lane, r));
             const double yr = row0 + rl < n ? y[row0 + rl] : 1.0;
             const double lp0 = lik_logp_mixed<LIK>(yr * f[bi][0][r]);
             const double lp1 = lik_logp_mixed<LIK>(yr * f[bi][1][r]);
@@ -150,13 +149,10 @@ __device__ __forceinline__ void loo_epilogue(const double (&f)[2][2][4], int row
 }
 
 // ------------------------------------------------------------------------------- the GEMM
-// One 64 x 64 tile (row block i, sample block sb) of C_chol U per workgroup on
-// v_mfma_f32_16x16x4_f32 from the slot's fp32 factor and the U buffer's fp32 mirror, to the depth
-// (i + 1) 64: k_ugemm's staging (U through two LDS buffers, the A fragments straight from global,
-// the next slice loaded while the current one is multiplied), its XCD-aware order (chain-major,
-// heaviest row block first, sample block fastest) and its accumulation order, so f_s is bitwise
-// the f_s the weights were formed at. The main loop is this kernel's own copy: k_ugemm stays as
-// it is. pp: [chain][quantity 0..4][row < npr][sample tile < nst].
+// One 64 x 64 tile (row block i, sample block sb) of C_chol U per workgroup, from the slot's fp32
+// factor and the U buffer's fp32 mirror: ugemm_tile.h's work-item order and product, which are
+// k_ugemm's, so f_s is bitwise the f_s the weights were formed at.
+// pp: [chain][quantity 0..4][row < npr][sample tile < nst].
 template <int LIK>
 __global__ __launch_bounds__(256) void k_is_loo_gemm(SlotSet S, const int64_t* __restrict__ slots,
                                                      UPool P, const int64_t* __restrict__ ubufs,
@@ -165,98 +161,26 @@ __global__ __launch_bounds__(256) void k_is_loo_gemm(SlotSet S, const int64_t* _
                                                      double* __restrict__ pp,
                                                      const int* __restrict__ status, int nsb,
                                                      int nchains) {
-    const int nb = np / 64;
-    const long total = (long)nb * nsb * nchains;
-    const long slot_id = blockIdx.x, xcd = slot_id & 7, q = total >> 3, rem = total & 7;
-    const long item = nchains < 8 ? slot_id
-                      : (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (slot_id >> 3);
-    const int b = (int)(item / ((long)nb * nsb));
-    const int rest = (int)(item % ((long)nb * nsb));
+    int b, i, sb;
+    ugemm_item(np / 64, nsb, nchains, b, i, sb);
     if (status[b] != 0) return;
-    const int i = nb - 1 - rest / nsb;
-    const int sb = rest % nsb;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wr = w >> 1, wc = w & 1;
-    const int r16 = lane & 15, kq = lane >> 4;
     __shared__ float Ut[2][64][65];
     __shared__ LooEpi ep;
 
     const int64_t slot = slots[b];
     if (S.wide[slot]) return;  // k_is_loo_gemm64
-    const float* L = S.L + slot * S.lstride;
-    const float* U = P.base32 + ubufs[b] * P.stride;
     const int sp = P.sp;
-    const int kend = (i + 1) * 64;
-
     f4_t acc[2][2];
-#pragma unroll
-    for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-        for (int bj = 0; bj < 2; ++bj) acc[bi][bj] = f4_t{0.f, 0.f, 0.f, 0.f};
+    ugemm_tile32(acc, S.L + slot * S.lstride, P.base32 + ubufs[b] * P.stride, np, sp, i, sb, Ut);
 
-    f4_t un[4];
-    f4_t an[2][4];
-    auto gload = [&](int kk) {
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            const int e = tid + h * 256;  // 4-element piece, 16 per U row
-            un[h] = *reinterpret_cast<const f4_t*>(U + (int64_t)(kk + e / 16) * sp + sb * 64 +
-                                                   (e % 16) * 4);
-        }
-#pragma unroll
-        for (int bi = 0; bi < 2; ++bi) {
-            const float* p = L + (int64_t)(i * 64 + 32 * wr + 16 * bi + r16) * np + kk + kq * 16;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) an[bi][t] = *reinterpret_cast<const f4_t*>(p + 4 * t);
-        }
-    };
-    gload(0);
-    for (int kk = 0, cur = 0; kk < kend; kk += 64, cur ^= 1) {
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            const int e = tid + h * 256;
-            const int r = e / 16, c4 = (e % 16) * 4;
-            Ut[cur][r][c4] = un[h][0];
-            Ut[cur][r][c4 + 1] = un[h][1];
-            Ut[cur][r][c4 + 2] = un[h][2];
-            Ut[cur][r][c4 + 3] = un[h][3];
-        }
-        float a[2][16];
-#pragma unroll
-        for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-            for (int t = 0; t < 16; ++t) a[bi][t] = an[bi][t >> 2][t & 3];
-        __syncthreads();
-        if (kk + 64 < kend) gload(kk + 64);
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            float bv[2];
-#pragma unroll
-            for (int bj = 0; bj < 2; ++bj) bv[bj] = Ut[cur][kq * 16 + t][32 * wc + 16 * bj + r16];
-#pragma unroll
-            for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-                for (int bj = 0; bj < 2; ++bj)
-                    acc[bi][bj] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[bi][t], bv[bj],
-                                                                       acc[bi][bj], 0, 0, 0);
-        }
-    }
-
-    const double* fp = S.fpost64 + slot * S.vstride;
     double f[2][2][4];
-#pragma unroll
-    for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const double fr = fp[i * 64 + 32 * wr + 16 * bi + LOO_ROW32(lane, r)];
-#pragma unroll
-            for (int bj = 0; bj < 2; ++bj) f[bi][bj][r] = fr + (double)acc[bi][bj][r];
-        }
+    ugemm_add_fpost<false>(f, acc, S.fpost64 + slot * S.vstride, i);
     loo_epilogue<LIK, false>(f, i * 64, n, y, logw + (int64_t)b * sp + sb * 64,
                              pp + (int64_t)b * 5 * np * nsb, np, nsb, sb, ep);
 }
 
-// The same product and epilogue on the f64 MFMA for the call's wide slots, from the slot's fp64
-// factor and the fp64 U buffer, staged plainly as k_ugemm64 is (its accumulation order).
+// The same on the f64 MFMA for the call's wide slots, from the slot's fp64 factor and the fp64 U
+// buffer: k_ugemm64's product (ugemm_tile64).
 template <int LIK>
 __global__ __launch_bounds__(256) void k_is_loo_gemm64(SlotSet S,
                                                        const int64_t* __restrict__ slots, UPool P,
@@ -270,50 +194,16 @@ __global__ __launch_bounds__(256) void k_is_loo_gemm64(SlotSet S,
     const int64_t slot = slots[b];
     if (!S.wide[slot]) return;
     const int i = (int)blockIdx.x / nsb, sb = (int)blockIdx.x % nsb;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wr = w >> 1, wc = w & 1;
-    const int r16 = lane & 15, kq = lane >> 4;
     __shared__ double La[64][17];
     __shared__ double Ub[16][65];
     __shared__ LooEpi ep;
     const double* L = S.L64[slot];
     if (!L) return;  // (as k_ugemm64; a slot read by a u-call has its buffer attached)
-    const double* U = P.base + ubufs[b] * P.stride;
     const int sp = P.sp;
     d4_t acc[2][2];
-#pragma unroll
-    for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-        for (int bj = 0; bj < 2; ++bj) acc[bi][bj] = d4_t{0.0, 0.0, 0.0, 0.0};
-    const int kend = (i + 1) * 64;
-    for (int kk = 0; kk < kend; kk += 16) {
-        for (int e = tid; e < 64 * 16; e += 256) {
-            const int r = e >> 4, c = e & 15;
-            La[r][c] = L[(int64_t)(i * 64 + r) * np + kk + c];
-            Ub[e >> 6][e & 63] = U[(int64_t)(kk + (e >> 6)) * sp + sb * 64 + (e & 63)];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-#pragma unroll
-            for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-                for (int bj = 0; bj < 2; ++bj)
-                    acc[bi][bj] = __builtin_amdgcn_mfma_f64_16x16x4f64(
-                        La[32 * wr + 16 * bi + r16][4 * t + kq],
-                        Ub[4 * t + kq][32 * wc + 16 * bj + r16], acc[bi][bj], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    const double* fp = S.fpost64 + slot * S.vstride;
+    ugemm_tile64(acc, L, P.base + ubufs[b] * P.stride, np, sp, i, sb, La, Ub);
     double f[2][2][4];
-#pragma unroll
-    for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const double fr = fp[i * 64 + 32 * wr + 16 * bi + F64_CROW(lane, r)];
-#pragma unroll
-            for (int bj = 0; bj < 2; ++bj) f[bi][bj][r] = fr + acc[bi][bj][r];
-        }
+    ugemm_add_fpost<true>(f, acc, S.fpost64 + slot * S.vstride, i);
     loo_epilogue<LIK, true>(f, i * 64, n, y, logw + (int64_t)b * sp + sb * 64,
                             pp + (int64_t)b * 5 * np * nsb, np, nsb, sb, ep);
 }

@@ -11,6 +11,7 @@
 // vanishing gradient in f_s at the Laplace mode - as in the reference's own evaluation. The large
 // terms (1/2 W f^2, z f, the -x^2/2 of log Phi) are formed and summed in fp64.
 #include "apm_internal.h"
+#include "ugemm_tile.h"
 
 // ------------------------------------------------------------------------------- U buffers
 __global__ __launch_bounds__(256) void k_u_convert(const double* __restrict__ U, int64_t ldu,
@@ -130,10 +131,6 @@ void launch_u_combine(UPool P, const int64_t* dst, const int64_t* a, const int64
 }
 
 // ------------------------------------------------------------------------------- L . U + epilogue
-// v_mfma_f32_16x16x4_f32: A lane l -> A[l&15][k=l>>4], B lane l -> B[k=l>>4][l&15],
-// C/D lane l, reg r -> (row = (l>>4)*4 + r, col = l&15)
-#define UP 65  // LDS row pitch (floats) of the staged U tile: conflict-free B-fragment reads
-
 // one entry of the per-sample sum: log p(y | f) + 1/2 W f^2 - z f, the large terms in fp64
 // (probit: log Phi(y f), logit: log sigma(y f))
 template <int LIK>
@@ -143,7 +140,13 @@ __device__ __forceinline__ double is_term(double f, double y, double W, double z
 
 // One 64 x 64 output tile (row block i, sample block sb) per workgroup, waves 32 x 32 (a 64 x 128
 // tile that read L once per two sample blocks was measured slower from 8 chains up: half the
-// workgroups, 2 instead of 4 per CU - DESIGN.md §5).
+// workgroups, 2 instead of 4 per CU - DESIGN.md §5). The work-item order is ugemm_tile.h's, shared
+// with the LOO and PSIS kernels. The product below is the text of ugemm_tile.h's ugemm_tile32 and
+// must stay so - those kernels need f_s bitwise as the weights are formed at it here: a change to
+// the staging or the accumulation order is made in both places. It is written out because
+// through the call this kernel measured 0.8 % slower from 21 chains up, outside its run-to-run
+// spread of 0.3 % (the same instructions in the main loop but for the order of
+// five, the loop 12 bytes earlier in the code; the cause is not isolated).
 template <int LIK>
 __global__ __launch_bounds__(256) void k_ugemm(SlotSet S, const int64_t* __restrict__ slots,
                                                UPool P, const int64_t* __restrict__ ubufs,
@@ -151,29 +154,13 @@ __global__ __launch_bounds__(256) void k_ugemm(SlotSet S, const int64_t* __restr
                                                double* __restrict__ partial, int64_t pstride,
                                                const int* __restrict__ status, int nsb,
                                                int nchains) {
-    // XCD-aware order (as k_chol_update's xcd_remap): dispatch slot s runs on XCD s % 8, and
-    // consecutive work items land on the same XCD. Items run chain-major, then row block
-    // (heaviest, i.e. longest K range, first; consecutive row blocks read nearly the same rows
-    // of U), then sample block fastest - so the nsb
-    // workgroups that share row block i's slice of L run together on one XCD and read it once
-    // from its L2, and a chain's U stays within one XCD's L2 / the Infinity Cache.
-    constexpr int NSW = 1;
-    const int nb = np / 64;
-    const int nsg = nsb / NSW;  // sample groups
-    const long total = (long)nb * nsg * nchains;
-    const long slot_id = blockIdx.x, xcd = slot_id & 7, q = total >> 3, rem = total & 7;
-    const long item = nchains < 8 ? slot_id  // too few chains to fill 8 XCDs evenly: plain order
-                      : (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (slot_id >> 3);
-    const int b = (int)(item / ((long)nb * nsg));
-    const int rest = (int)(item % ((long)nb * nsg));
+    int b, i, sb;
+    ugemm_item(np / 64, nsb, nchains, b, i, sb);
     if (status[b] != 0) return;
-    const int i = nb - 1 - rest / nsg;
-    const int sb = (rest % nsg) * NSW;  // first sample block
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wr = w >> 1, wc = w & 1;
     const int r16 = lane & 15, kq = lane >> 4;
-    constexpr int SW = 64 * NSW;  // samples per workgroup
-    __shared__ float Ut[2][64][SW + 1];
-    __shared__ double csum[2][SW];
+    __shared__ float Ut[2][64][65];
+    __shared__ double csum[2][64];
 
     const int64_t slot = slots[b];
     if (S.wide[slot]) return;  // k_ugemm64
@@ -182,25 +169,20 @@ __global__ __launch_bounds__(256) void k_ugemm(SlotSet S, const int64_t* __restr
     const int sp = P.sp;
     const int kend = (i + 1) * 64;
 
-    f4_t acc[2][2 * NSW];
+    f4_t acc[2][2];
 #pragma unroll
     for (int bi = 0; bi < 2; ++bi)
 #pragma unroll
-        for (int bj = 0; bj < 2 * NSW; ++bj) acc[bi][bj] = f4_t{0.f, 0.f, 0.f, 0.f};
+        for (int bj = 0; bj < 2; ++bj) acc[bi][bj] = f4_t{0.f, 0.f, 0.f, 0.f};
 
-    // U[kk:kk+64][sb*64 : sb*64+SW] (16 KB per sample block, 16-byte loads) and the A fragments
-    // (straight from global: 16 contiguous floats per lane and row) of the next slice are loaded
-    // into registers while the current one is multiplied; U goes through two LDS buffers, one
-    // barrier per slice
-    constexpr int PR = 16 * NSW;  // 16-byte pieces per U row
-    f4_t un[4 * NSW];
+    f4_t un[4];
     f4_t an[2][4];
     auto gload = [&](int kk) {
 #pragma unroll
-        for (int h = 0; h < 4 * NSW; ++h) {
-            const int e = tid + h * 256;  // 4-element piece
-            un[h] = *reinterpret_cast<const f4_t*>(U + (int64_t)(kk + e / PR) * sp + sb * 64 +
-                                                   (e % PR) * 4);
+        for (int h = 0; h < 4; ++h) {
+            const int e = tid + h * 256;  // 4-element piece, 16 per U row
+            un[h] = *reinterpret_cast<const f4_t*>(U + (int64_t)(kk + e / 16) * sp + sb * 64 +
+                                                   (e % 16) * 4);
         }
 #pragma unroll
         for (int bi = 0; bi < 2; ++bi) {
@@ -212,9 +194,9 @@ __global__ __launch_bounds__(256) void k_ugemm(SlotSet S, const int64_t* __restr
     gload(0);
     for (int kk = 0, cur = 0; kk < kend; kk += 64, cur ^= 1) {
 #pragma unroll
-        for (int h = 0; h < 4 * NSW; ++h) {
+        for (int h = 0; h < 4; ++h) {
             const int e = tid + h * 256;
-            const int r = e / PR, c4 = (e % PR) * 4;
+            const int r = e / 16, c4 = (e % 16) * 4;
             Ut[cur][r][c4] = un[h][0];
             Ut[cur][r][c4 + 1] = un[h][1];
             Ut[cur][r][c4 + 2] = un[h][2];
@@ -229,99 +211,18 @@ __global__ __launch_bounds__(256) void k_ugemm(SlotSet S, const int64_t* __restr
         if (kk + 64 < kend) gload(kk + 64);
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
-            float bv[2 * NSW];
+            float bv[2];
 #pragma unroll
-            for (int bj = 0; bj < 2 * NSW; ++bj)
-                bv[bj] = Ut[cur][kq * 16 + t][32 * NSW * wc + 16 * bj + r16];
+            for (int bj = 0; bj < 2; ++bj) bv[bj] = Ut[cur][kq * 16 + t][32 * wc + 16 * bj + r16];
 #pragma unroll
             for (int bi = 0; bi < 2; ++bi)
 #pragma unroll
-                for (int bj = 0; bj < 2 * NSW; ++bj)
+                for (int bj = 0; bj < 2; ++bj)
                     acc[bi][bj] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[bi][t], bv[bj],
                                                                        acc[bi][bj], 0, 0, 0);
         }
     }
 
-    double* pb = partial + b * pstride;
-    const double* fp = S.fpost64 + slot * S.vstride;
-    const double* Wv = S.W64 + slot * S.vstride;
-    const double* zv = S.z64 + slot * S.vstride;
-    double colsum[2 * NSW];
-#pragma unroll
-    for (int bj = 0; bj < 2 * NSW; ++bj) {
-        double d = 0.0;
-#pragma unroll
-        for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = i * 64 + 32 * wr + 16 * bi + kq * 4 + r;
-                if (row < n) d += is_term<LIK>(fp[row] + (double)acc[bi][bj][r], y[row], Wv[row], zv[row]);
-            }
-        d += __shfl_xor(d, 16, 64);
-        d += __shfl_xor(d, 32, 64);
-        colsum[bj] = d;
-    }
-    if (kq == 0) {
-#pragma unroll
-        for (int bj = 0; bj < 2 * NSW; ++bj) csum[wr][32 * NSW * wc + 16 * bj + r16] = colsum[bj];
-    }
-    __syncthreads();
-    if (tid < SW) pb[(int64_t)i * sp + sb * 64 + tid] = csum[0][tid] + csum[1][tid];
-}
-
-// The same product and epilogue on f64 MFMA (v_mfma_f64_16x16x4_f64) for the call's WIDE slots
-// (S.wide: trace(L L^T) > APM_WIDE_Q, set by k_slot_write_vec), from the slot's fp64 factor and
-// the fp64 U buffer: where the entries of f_s are large (sigma = e^18.5: |f_s| ~ 1e4), the fp32
-// rounding of L and U alone moves log f by ~10 nats (DESIGN.md §3.3). Rare (extreme theta),
-// so plainly staged: 64x64 output tile per workgroup, L and U slices of 16 through LDS.
-template <int LIK>
-__global__ __launch_bounds__(256) void k_ugemm64(SlotSet S, const int64_t* __restrict__ slots,
-                                                 UPool P, const int64_t* __restrict__ ubufs,
-                                                 const double* __restrict__ y, int n, int np,
-                                                 double* __restrict__ partial, int64_t pstride,
-                                                 const int* __restrict__ status, int nsb) {
-    const int nb = np / 64;
-    const int b = blockIdx.y;
-    if (status[b] != 0) return;
-    const int64_t slot = slots[b];
-    if (!S.wide[slot]) return;
-    const int i = (int)blockIdx.x / nsb, sb = (int)blockIdx.x % nsb;
-    (void)nb;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wr = w >> 1, wc = w & 1;
-    const int r16 = lane & 15, kq = lane >> 4;
-    __shared__ double La[64][17];
-    __shared__ double Ub[16][65];
-    __shared__ double csum[2][64];
-    const double* L = S.L64[slot];
-    if (!L) return;  // wide by this call, buffer not attached yet: recomputed after it is
-    const double* U = P.base + ubufs[b] * P.stride;
-    const int sp = P.sp;
-    d4_t acc[2][2];
-#pragma unroll
-    for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-        for (int bj = 0; bj < 2; ++bj) acc[bi][bj] = d4_t{0.0, 0.0, 0.0, 0.0};
-    const int kend = (i + 1) * 64;
-    for (int kk = 0; kk < kend; kk += 16) {
-        for (int e = tid; e < 64 * 16; e += 256) {
-            const int r = e >> 4, c = e & 15;
-            La[r][c] = L[(int64_t)(i * 64 + r) * np + kk + c];
-            Ub[e >> 6][e & 63] = U[(int64_t)(kk + (e >> 6)) * sp + sb * 64 + (e & 63)];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-#pragma unroll
-            for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-                for (int bj = 0; bj < 2; ++bj)
-                    acc[bi][bj] = __builtin_amdgcn_mfma_f64_16x16x4f64(
-                        La[32 * wr + 16 * bi + r16][4 * t + kq],
-                        Ub[4 * t + kq][32 * wc + 16 * bj + r16], acc[bi][bj], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    // f64 MFMA output map: lane l, reg r -> row (l >> 4) + 4r, col l & 15
     double* pb = partial + b * pstride;
     const double* fp = S.fpost64 + slot * S.vstride;
     const double* Wv = S.W64 + slot * S.vstride;
@@ -334,7 +235,60 @@ __global__ __launch_bounds__(256) void k_ugemm64(SlotSet S, const int64_t* __res
         for (int bi = 0; bi < 2; ++bi)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int row = i * 64 + 32 * wr + 16 * bi + kq + 4 * r;
+                const int row = i * 64 + 32 * wr + 16 * bi + F32_CROW(lane, r);
+                if (row < n) d += is_term<LIK>(fp[row] + (double)acc[bi][bj][r], y[row], Wv[row], zv[row]);
+            }
+        d += __shfl_xor(d, 16, 64);
+        d += __shfl_xor(d, 32, 64);
+        colsum[bj] = d;
+    }
+    if (kq == 0) {
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj) csum[wr][32 * wc + 16 * bj + r16] = colsum[bj];
+    }
+    __syncthreads();
+    if (tid < 64) pb[(int64_t)i * sp + sb * 64 + tid] = csum[0][tid] + csum[1][tid];
+}
+
+// The same product and epilogue on f64 MFMA (v_mfma_f64_16x16x4_f64) for the call's WIDE slots
+// (S.wide: trace(L L^T) > APM_WIDE_Q, set by k_slot_write_vec), from the slot's fp64 factor and
+// the fp64 U buffer: where the entries of f_s are large (sigma = e^18.5: |f_s| ~ 1e4), the fp32
+// rounding of L and U alone moves log f by ~10 nats (DESIGN.md §3.3). Rare (extreme theta),
+// so plainly staged (ugemm_tile.h's ugemm_tile64): 64x64 output tile per workgroup.
+template <int LIK>
+__global__ __launch_bounds__(256) void k_ugemm64(SlotSet S, const int64_t* __restrict__ slots,
+                                                 UPool P, const int64_t* __restrict__ ubufs,
+                                                 const double* __restrict__ y, int n, int np,
+                                                 double* __restrict__ partial, int64_t pstride,
+                                                 const int* __restrict__ status, int nsb) {
+    const int b = blockIdx.y;
+    if (status[b] != 0) return;
+    const int64_t slot = slots[b];
+    if (!S.wide[slot]) return;
+    const int i = (int)blockIdx.x / nsb, sb = (int)blockIdx.x % nsb;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wr = w >> 1, wc = w & 1;
+    const int r16 = lane & 15, kq = lane >> 4;
+    __shared__ double La[64][17];
+    __shared__ double Ub[16][65];
+    __shared__ double csum[2][64];
+    const double* L = S.L64[slot];
+    if (!L) return;  // wide by this call, buffer not attached yet: recomputed after it is
+    const int sp = P.sp;
+    d4_t acc[2][2];
+    ugemm_tile64(acc, L, P.base + ubufs[b] * P.stride, np, sp, i, sb, La, Ub);
+    double* pb = partial + b * pstride;
+    const double* fp = S.fpost64 + slot * S.vstride;
+    const double* Wv = S.W64 + slot * S.vstride;
+    const double* zv = S.z64 + slot * S.vstride;
+    double colsum[2];
+#pragma unroll
+    for (int bj = 0; bj < 2; ++bj) {
+        double d = 0.0;
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = i * 64 + 32 * wr + 16 * bi + F64_CROW(lane, r);
                 if (row < n) d += is_term<LIK>(fp[row] + acc[bi][bj][r], y[row], Wv[row], zv[row]);
             }
         d += __shfl_xor(d, 16, 64);

@@ -12,18 +12,22 @@ partial Gram copy, the Newton lookahead with far updates, explicit-inverse panel
 5/2 ARD context at N = 200, and two isotropic kinds whose features need a second LDS chunk of the
 pair-distance tile (csrc/pair_tile.h): SE at N = 130, d = 40 (a second chunk of 8 features) and
 Matern 3/2 at N = 129, d = 33 (the two-pass gradient, a second chunk of one feature, a last tile
-of one row). One case is one shape under one setting of the environment knobs;
+of one row), and the N = 65 shape once more with 9 chains (n65x9: its three thetas on 9 slots and
+9 distinct U buffers), whose 2 x 1 x 9 = 18 work items run the u-path's fp32 kernels in their
+XCD-remapped order (8 chains and more; 18 is no multiple of 8). One case is one shape under one
+setting of the environment knobs;
 run each in a process of its own (the knobs are read when a context is created):
 
     python tools/ab_values.py --list-small
     APM_LIB=... python tools/ab_values.py --small n1089:APM_POST32_Q=0 out_dir/
 
-The default setting of a shape runs every call (IS theta-call + u-call + slot read, PriorMC,
-Laplace, apm_theta_eval_K, apm_predict with one and three row tiles of test inputs,
+The default setting of a shape runs every call (IS theta-call + u-call + slot read, apm_is_loo and
+apm_is_loo_psis with the log ratios on that u-call's samples, PriorMC, Laplace, apm_theta_eval_K, apm_predict with one and three row tiles of test inputs,
 apm_laplace_grad, apm_ep_eval / apm_ep_predict / apm_ep_grad, the EST_IS_EP theta-call,
 apm_is_predict with both proposals and one and two blocks of test inputs, apm_u_eval_diag,
 apm_is_spread, apm_laplace and apm_ep with their covariances); a knob setting repeats the IS call,
-which is what the knobs reach. After every call the launch counts of all APM_PROF_* kinds (profiling
+which is what the knobs reach, and APM_WIDE_Q=0 (every slot wide: the u-path's f64 kernels) the two
+LOO calls as well. n65x9 runs the IS call and the two LOO calls, under those two settings. After every call the launch counts of all APM_PROF_* kinds (profiling
 level 2) are saved beside the arrays.
 
     python tools/ab_values.py --compare a.npz b.npz      (or two directories of npz files)
@@ -41,17 +45,21 @@ sys.path.insert(0, os.path.join(REPO, 'tests'))  # grad_restatement.make_case, e
 # name -> (n, d, kernel kind name, data seed); 65 and 1089 take tests/edge_cases.py's seeds
 SMALL_SHAPES = {'n64': (64, 4, 'KERNEL_ARD', 3064), 'n65': (65, 4, 'KERNEL_ARD', None),
                 'n1089': (1089, 5, 'KERNEL_ARD', None), 'm200': (200, 4, 'KERNEL_M52_ARD', 5200),
-                'iso130': (130, 40, 'KERNEL_ISO', 3170), 'm129': (129, 33, 'KERNEL_M32_ISO', 5162)}
+                'iso130': (130, 40, 'KERNEL_ISO', 3170), 'm129': (129, 33, 'KERNEL_M32_ISO', 5162),
+                'n65x9': (65, 4, 'KERNEL_ARD', None)}
+REMAP = 'n65x9'  # n65's thetas three times over: 9 chains
 # the knobs that reach a rare host path: fp64 Newton; fp32 operands; fp64 rerun, then chol(K)
 # again on the main stream; the fp64 bottom block with its gap; attach / rewrite of fp64 slot
 # factors; the reference-route check of every chain (the value tests/test_gpu_configs.py uses)
 SMALL_KNOBS = ('', 'APM_MIXED=0', 'APM_H3=0', 'APM_REFINE_TOL=0', 'APM_POST32_Q=0',
                'APM_WIDE_Q=0', 'APM_ICM_Q=1')
+LOO_KNOBS = ('', 'APM_WIDE_Q=0')  # the settings that also run apm_is_loo and apm_is_loo_psis
 S_IMP = 16
 
 
 def small_cases():
-    return ['{0}:{1}'.format(s, k) if k else s for s in SMALL_SHAPES for k in SMALL_KNOBS]
+    return ['{0}:{1}'.format(s, k) if k else s for s in SMALL_SHAPES for k in SMALL_KNOBS
+            if s != REMAP or k in LOO_KNOBS]
 
 
 def run(path):
@@ -95,6 +103,8 @@ def run_small(case, outdir):
     c = gr.make_case(n, d, 'iso' if kind_name.endswith('_ISO') else 'ard',
                      edge_cases.SEEDS[n] if seed is None else seed)
     X, y, th = c['X'], c['y'], c['thetas']
+    if shape == REMAP:
+        th = np.tile(th, (3, 1))
     B = th.shape[0]
     idx = np.arange(B)
     out = {}
@@ -102,7 +112,7 @@ def run_small(case, outdir):
     def context():
         ctx = _native.Context(X, y, kind, 1e-8, S_IMP, max_batch=B, n_slots=B, n_ubufs=B)
         ctx.prof_enable(2)
-        ctx.u_normal(idx, np.full(B, 7), idx)
+        ctx.u_normal(idx, np.full(B, 7), idx)  # (one counter per buffer: the chains differ)
         return ctx
 
     def launches(ctx, call):
@@ -124,8 +134,17 @@ def run_small(case, outdir):
     out.update(is_v1=v1, is_st=st, is_nops=nops, is_v2=v2, is_st2=st2, is_guard=ctx.guard_read(B))
     slots(ctx, 'is')
     launches(ctx, 'is')
+    if knob in LOO_KNOBS:
+        for k, a in zip(('logf', 'loo', 'lpd', 'essloo', 'gauss', 'ess', 'st'),
+                        ctx.is_loo(idx, idx)):
+            out['loo_' + k] = a
+        launches(ctx, 'loo')
+        for k, a in zip(('logf', 'loo', 'khat', 'khatw', 'logratio', 'st'),
+                        ctx.is_loo_psis(idx, idx, want_logratio=True)):
+            out['psis_' + k] = a
+        launches(ctx, 'psis')
     ctx.close()
-    if not knob:
+    if not knob and shape != REMAP:
         ctx = context()
         v, st, nops = ctx.theta_eval(_native.EST_PRIORMC, th, idx, idx)
         out.update(pmc_v=v, pmc_st=st, pmc_nops=nops)
