@@ -109,7 +109,9 @@ class _BatchedChains(object):
         C = self.n_chains
         self.ctx = _native.Context(X, y, kind, epsilon, n_imp, max_batch=C, n_slots=2 * C,
                                    n_ubufs=3 * C, device=device, likelihood=likelihood)
-        # the EP fit of 'is_ep' theta-calls: dict of damping / diff_tol / max_sweeps (probit only)
+        # the EP fit of 'is_ep' theta-calls: dict of damping / diff_tol / max_sweeps, and
+        # quadrature (True: the tilted moments by the rule of DESIGN.md §27, which the logit needs;
+        # without it the library refuses an 'is_ep' theta-call on a logit context)
         self.ep_settings = None if ep_settings is None else dict(ep_settings)
         if self.ep_settings is not None:
             self.ctx.set_ep(**self.ep_settings)

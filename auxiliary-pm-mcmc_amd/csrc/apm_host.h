@@ -262,6 +262,10 @@ struct __attribute__((visibility("hidden"))) apm_ctx {
     // and the site and scratch vectors (EpVecs), allocated at the first EP call
     double ep_damping = 0.8, ep_tol = 1e-8;
     int64_t ep_max_sweeps = 100;
+    // apm_set_ep_quadrature: the tilted moments by the rule of ep_quad.h (k_ep_sites_q) for
+    // either likelihood, which opens EP to the logit; 0 keeps the closed-form probit kernel and
+    // every refusal of a logit context
+    int ep_quad = 0;
     EpVecs ep{};
     // the importance-sampling predictive (apm_is_predict), allocated at its first call: the
     // reversed transpose of each chain's U buffer (max_batch x sp x np), the weights (max_batch x

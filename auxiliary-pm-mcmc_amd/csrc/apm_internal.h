@@ -409,6 +409,11 @@ void launch_ep_prep(EpVecs e, NewtonVecs v, int np, Live live, int nchains, hipS
 // K_rr, mu = v.fnew and mu_prev = v.f: var, the damped candidate sites, lz, dm and bad
 void launch_ep_sites(MatB A, MatB K, int n, int nb, NewtonVecs v, const double* y, EpVecs e,
                      double damping, Live live, int nchains, hipStream_t s);
+// launch_ep_sites with the tilted moments of likelihood lik (APM_LIK_*) by the quadrature rule
+// of ep_quad.h: lz carries log Z^ for log Phi(z), and bad is also set at a site
+// outside the rule's covered region
+void launch_ep_sites_q(int lik, MatB A, MatB K, int n, int nb, NewtonVecs v, const double* y,
+                       EpVecs e, double damping, Live live, int nchains, hipStream_t s);
 // per live chain: n_iter += 1; a bad cavity -> status = fail_code; from the second sweep on
 // mean(dm) < diff_tol -> logz = sum lz - sum ldet[0, nb), active = 0; else the candidates become
 // the sites; v.f <- v.fnew

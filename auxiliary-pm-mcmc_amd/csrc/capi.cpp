@@ -82,7 +82,7 @@ int cached_call(int device, int64_t n, int64_t d, int kind, Body body) {
 // names (rest_bad: evaluated only with a context).
 struct ThetaArgs {
     const char* early = nullptr;  // a refusal that needs no context (apm_is_predict's est)
-    bool probit_only = false;
+    bool probit_only = false;     // (unless the context's EP moments come by quadrature)
     const char* device_why = "";  // why a PRECOMPUTED context is refused: "needs ... (...)"
     bool batch = false;           // count in [1, max_batch]
     int64_t count = 0;
@@ -99,7 +99,7 @@ int check_theta_call(apm_ctx* c, const char* who, const ThetaArgs& a, Rest rest_
     };
     if (!c) return no(nullptr, "null context");
     if (a.early) return no(c, a.early);
-    if (a.probit_only && c->lik != APM_LIK_PROBIT)
+    if (a.probit_only && c->lik != APM_LIK_PROBIT && !c->ep_quad)
         return no(c, "probit only (the logit's tilted moments need quadrature)");
     if (c->kind == APM_KERNEL_PRECOMPUTED) return no(c, a.device_why);
     if (a.rows && a.m <= 0) return no(c, "m <= 0");
@@ -278,7 +278,7 @@ int apm_theta_eval(apm_ctx* c, int est, int64_t count, const double* thetas, int
     if (!c || count <= 0 || count > c->max_batch || !thetas || !out_logf || !status ||
         est < 0 || est > APM_EST_IS_EP || c->kind == APM_KERNEL_PRECOMPUTED || ldt < c->P)
         return fail(c, APM_E_INVALID, "apm_theta_eval: bad arguments");
-    if (est == APM_EST_IS_EP && c->lik != APM_LIK_PROBIT)
+    if (est == APM_EST_IS_EP && c->lik != APM_LIK_PROBIT && !c->ep_quad)
         return fail(c, APM_E_INVALID, "apm_theta_eval: APM_EST_IS_EP is probit only (the logit's "
                                       "tilted moments need quadrature)");
     if (est != APM_EST_LAPLACE) {
@@ -322,7 +322,7 @@ int apm_theta_eval_K(apm_ctx* c, int est, const double* K, int64_t ldk, int64_t 
                      int64_t slot, double* out_logf, int* status, int64_t* nops) {
     if (!c || !K || ldk < c->n || !out_logf || !status || est < 0 || est > APM_EST_IS_EP)
         return fail(c, APM_E_INVALID, "apm_theta_eval_K: bad arguments");
-    if (est == APM_EST_IS_EP && c->lik != APM_LIK_PROBIT)
+    if (est == APM_EST_IS_EP && c->lik != APM_LIK_PROBIT && !c->ep_quad)
         return fail(c, APM_E_INVALID, "apm_theta_eval_K: APM_EST_IS_EP is probit only (the "
                                       "logit's tilted moments need quadrature)");
     if (est != APM_EST_LAPLACE &&
@@ -688,7 +688,7 @@ bool ep_settings_ok(double damping, double diff_tol, int64_t max_sweeps) {
 int apm_set_ep(apm_ctx* ctx, double damping, double diff_tol, int64_t max_sweeps) {
     if (!ctx || !ep_settings_ok(damping, diff_tol, max_sweeps))
         return fail(ctx, APM_E_INVALID, "apm_set_ep: bad arguments");
-    if (ctx->lik != APM_LIK_PROBIT)
+    if (ctx->lik != APM_LIK_PROBIT && !ctx->ep_quad)
         return fail(ctx, APM_E_INVALID, "apm_set_ep: probit only (the logit's tilted moments need "
                                         "quadrature)");
     ctx->ep_damping = damping;
@@ -696,6 +696,15 @@ int apm_set_ep(apm_ctx* ctx, double damping, double diff_tol, int64_t max_sweeps
     ctx->ep_max_sweeps = max_sweeps;
     return APM_SUCCESS;
 }
+
+int apm_set_ep_quadrature(apm_ctx* ctx, int on) {
+    if (!ctx || (on != 0 && on != 1))
+        return fail(ctx, APM_E_INVALID, "apm_set_ep_quadrature: bad arguments");
+    ctx->ep_quad = on;
+    return APM_SUCCESS;
+}
+
+int apm_ep_quadrature(const apm_ctx* ctx) { return ctx ? ctx->ep_quad : APM_E_INVALID; }
 
 int apm_ep_eval(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, double* logz,
                 double* mu, double* var, double* tau, double* nu, int64_t ldo, int* status,
@@ -781,8 +790,17 @@ int apm_ep(int device, const double* K, int64_t n, int64_t ldk, const double* y,
            double damping, double diff_tol, int64_t max_sweeps, double* mu_out, double* var_out,
            double* tau_out, double* nu_out, double* C_out, int64_t ldc, double* logz_out,
            int64_t* n_sweeps_out, int* status) {
+    return apm_ep_lik(device, APM_LIK_PROBIT, K, n, ldk, y, calc_cov, damping, diff_tol,
+                      max_sweeps, mu_out, var_out, tau_out, nu_out, C_out, ldc, logz_out,
+                      n_sweeps_out, status);
+}
+
+int apm_ep_lik(int device, int lik, const double* K, int64_t n, int64_t ldk, const double* y,
+               int calc_cov, double damping, double diff_tol, int64_t max_sweeps, double* mu_out,
+               double* var_out, double* tau_out, double* nu_out, double* C_out, int64_t ldc,
+               double* logz_out, int64_t* n_sweeps_out, int* status) {
     if (!K || !y || n <= 0 || ldk < n || !status || !ep_settings_ok(damping, diff_tol, max_sweeps) ||
-        (calc_cov && (!C_out || ldc < n)))
+        (calc_cov && (!C_out || ldc < n)) || (lik != APM_LIK_PROBIT && lik != APM_LIK_LOGIT))
         return fail(nullptr, APM_E_INVALID, "apm_ep: bad arguments");
     // (apm_laplace's cached context of the shape)
     return cached_call(device, n, 0, APM_KERNEL_PRECOMPUTED, [&](apm_ctx*& c) {
@@ -790,7 +808,9 @@ int apm_ep(int device, const double* K, int64_t n, int64_t ldk, const double* y,
         c->ep_damping = damping;
         c->ep_tol = diff_tol;
         c->ep_max_sweeps = max_sweeps;
-        c->lik = APM_LIK_PROBIT;  // (augmented() and the shared kernels read it)
+        c->lik = lik;  // (augmented() and the shared kernels read it)
+        // the probit's moments are closed form, the logit's come by the rule
+        c->ep_quad = lik == APM_LIK_LOGIT;
         std::vector<double> Kp;  // (alive until the syncs below)
         upload_padded_K(c, K, ldk, Kp);
         EpFit fit;

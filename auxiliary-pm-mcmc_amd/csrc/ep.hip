@@ -9,9 +9,10 @@
 //   tau~_new = max(1/s^ - tau_-, 0),  nu~_new = mu^/s^ - nu_-,  damped by delta;
 //   log Z_EP = sum_i [log Phi(z) + 1/2 log(1 + tau~/tau_-) + 1/2 nu~ mu - 1/2 nu~^2 sigma2
 //              + 1/2 mu_- tau_- (tau~ mu_- - 2 nu~) sigma2] - sum_i log L_ii
-// (R&W eqs. 3.65, 3.73-3.74 with tau_- + tau~ = 1/sigma2). Probit only: the logit's tilted
-// moments need quadrature.
+// (R&W eqs. 3.65, 3.73-3.74 with tau_- + tau~ = 1/sigma2). These closed-form moments are the
+// probit's; k_ep_sites_q takes them by quadrature for either likelihood.
 #include "apm_internal.h"
+#include "ep_quad.h"
 
 // S^1/2 and nu~ into the Newton vectors (Ws, W, b); rows >= n have tau~ = nu~ = 0 throughout
 __global__ __launch_bounds__(256) void k_ep_prep(EpVecs e, NewtonVecs v, int np, Live live) {
@@ -77,6 +78,143 @@ void launch_ep_sites(MatB A, MatB K, int n, int nb, NewtonVecs v, const double* 
                      double damping, Live live, int nchains, hipStream_t s) {
     APM_LAUNCH(k_ep_sites, dim3((64 * nb + 3) / 4, nchains), dim3(256), 0, s, A, K, n, nb, v, y,
                e, damping, live);
+}
+
+// The tilted moments of p(y f) N(f | mu_-, s_-) by quadrature, on a whole wave:
+// the sums S_k of p(t) (t - m)^k N(t | m, s_-) over t = y f, m = y mu_-, k = 0, 1, 2, with the
+// largest exponent E of their terms taken out, so every lane returns log Z^ = E + log S_0,
+// e1 = S_1/S_0 and e2 = S_2/S_0 (mu^ = mu_- + y e1, s^ = e2 - e1^2). Two nodes per lane, the three
+// sums by the wave's butterfly, every loop of fixed length; the tables are ep_quad.h's.
+//   s_- <= v0: the 128-node Gauss-Hermite rule on the cavity, t_k = m + sqrt(2 s_-) x_k.
+//   s_- >  v0: p = H + r with H the unit step and r(t) = -sign(t) p(-|t|), which decays like
+//     e^-|t| (logit) or faster. The step's moments about m are closed form in alpha = m/sd:
+//     Phi, sd phi, s_- (Phi - alpha phi). The correction is the integral over u of
+//     p(-u) [(-u - m)^k N(-u | m, s_-) - (u - m)^k N(u | m, s_-)] by 8-node Gauss-Legendre on 8
+//     panels of [0, T_in] and 8 of [T_in, T]. The logit's part at -u is a Gaussian of deviation
+//     sd about c = -m - s_- times 1/(1 + e^-u), and [T_in, T] follows that Gaussian down by
+//     e^-36 from its peak (c > 0: T = c + 8.5 sd) or from its value at 0 (T = c + sqrt(c^2 +
+//     72.25 s_-)), T >= 2 T_in. The probit's T is 2 T_in: its r is below 1e-23 past T_in.
+// The covered region (include/apm.h states it): the logit while an outer panel is no wider than
+// 2 sd, which is c <= 7.5 sd + 20, and, where c < 0, while alpha >= -30 (there the step dominates
+// and the moments about m cancel like alpha^4); the probit while the product's peak is inside
+// the nodes (narrow: x* <= 8; wide: -m <= min(5 (1 + s_-), 300), the second bound because the
+// moments about m cancel like (m / sd^)^2). A site outside is reported through `covered` and
+// fails its chain (APM_STATUS_EP_CAVITY): the rule is never silently wrong.
+struct EpMoments {
+    double lz, e1, e2;
+    bool covered;
+};
+template <int LIK>
+__device__ __forceinline__ EpMoments ep_quad_moments(double m, double vc, int lane) {
+    static_assert(APM_EPQ_GH_N == 128 && APM_EPQ_GL_N == 8 && APM_EPQ_PANELS == 16,
+                  "two nodes per lane of a wave");
+    const double sd = sqrt(vc);
+    double E, s0, s1, s2;
+    if (vc <= APM_EPQ_V0) {  // (wave-uniform)
+        const double sc = 1.4142135623730951 * sd;
+        const double d0 = sc * APM_EPQ_GH_X[lane], d1 = sc * APM_EPQ_GH_X[lane + 64];
+        const double l0 = lik_logp<LIK>(m + d0) + APM_EPQ_GH_LW[lane];
+        const double l1 = lik_logp<LIK>(m + d1) + APM_EPQ_GH_LW[lane + 64];
+        E = wave_max_d(fmax(l0, l1));
+        const double a0 = exp(l0 - E), a1 = exp(l1 - E);
+        s0 = wave_sum_d(a0 + a1);
+        s1 = wave_sum_d(a0 * d0 + a1 * d1);
+        s2 = wave_sum_d(a0 * d0 * d0 + a1 * d1 * d1);
+        // (the probit's integrand peaks at x* = -m sd / (sqrt2 (1 + s_-)) in the rule's variable)
+        const bool covered = LIK == APM_LIK_LOGIT ||
+                             -m * sd <= APM_EPQ_X_MAX * 1.4142135623730951 * (1.0 + sd * sd);
+        return EpMoments{E + log(s0), s1 / s0, s2 / s0, covered};
+    }
+    constexpr double t_in = LIK == APM_LIK_LOGIT ? APM_EPQ_T_IN_LOGIT : APM_EPQ_T_IN_PROBIT;
+    double t_end = 2.0 * t_in;
+    bool covered;
+    if constexpr (LIK == APM_LIK_LOGIT) {
+        const double c = -m - sd * sd, ts = APM_EPQ_TAIL * sd;
+        t_end = fmax(t_end, c + (c > 0.0 ? ts : sqrt(c * c + ts * ts)));
+        covered = t_end - t_in <= 8.0 * APM_EPQ_H_MAX * sd &&
+                  (c >= 0.0 || m >= -APM_EPQ_A_MAX * sd);
+    } else {
+        covered = -m <= fmin(APM_EPQ_PEAK_MAX * (1.0 + sd * sd), APM_EPQ_M_MAX);
+    }
+    // lane l: node l & 7 of panel l >> 3 of [0, T_in] (u[0]) and of [T_in, T] (u[1])
+    const double frac = ((double)(lane >> 3) + APM_EPQ_GL_XI[lane & 7]) / 8.0;
+    const double lwn = APM_EPQ_GL_LW[lane & 7] - 2.0794415416798357;  // (log 8)
+    const double u[2] = {t_in * frac, t_in + (t_end - t_in) * frac};
+    const double lW[2] = {log(t_in) + lwn, log(t_end - t_in) + lwn};
+    const double alpha = m / sd, lsd = log(sd), i2v = 2.0 * sd * sd;
+    double lm[2], lp[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const double base = lik_logp<LIK>(-u[k]) + lW[k] - lsd - 0.91893853320467274178;
+        lm[k] = base - (u[k] + m) * (u[k] + m) / i2v;  // the node at t = -u
+        lp[k] = base - (u[k] - m) * (u[k] - m) / i2v;  // the node at t = +u
+    }
+    const double lP = log_ndtr_d(alpha);
+    E = fmax(lP, wave_max_d(fmax(fmax(lm[0], lp[0]), fmax(lm[1], lp[1]))));
+    s0 = s1 = s2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const double am = exp(lm[k] - E), ap = exp(lp[k] - E);
+        const double dm = -(u[k] + m), dp = u[k] - m;
+        s0 += am - ap;
+        s1 += dm * am - dp * ap;
+        s2 += dm * dm * am - dp * dp * ap;
+    }
+    s0 = wave_sum_d(s0);
+    s1 = wave_sum_d(s1);
+    s2 = wave_sum_d(s2);
+    const double P = exp(lP - E), ph = exp(-0.5 * alpha * alpha - 0.91893853320467274178 - E);
+    const double z = P + s0;
+    return EpMoments{E + log(z), (sd * ph + s1) / z, (sd * sd * (P - alpha * ph) + s2) / z,
+                     covered};
+}
+
+// k_ep_sites with the tilted moments by quadrature, for either likelihood (apm_set_ep_quadrature):
+// the same grid, row norm and outputs; every lane of the wave forms the cavity (the loads are
+// wave-uniform), the wave evaluates the rule, and lane 0 finishes the damped sites. The row's
+// term of log Z_EP carries log Z^ in the place of log Phi(z); a site outside the rule's covered
+// region counts as a bad cavity.
+template <int LIK>
+__global__ __launch_bounds__(256) void k_ep_sites_q(MatB A, MatB K, int n, int nb, NewtonVecs v,
+                                                    const double* __restrict__ y, EpVecs e,
+                                                    double damping, Live live) {
+    const int b = blockIdx.y;
+    if (!live_chain(live, b)) return;
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int np = 64 * nb;
+    if (r >= np) return;
+    const int64_t o = b * e.stride + r;
+    if (r >= n) {  // (wave-uniform)
+        if (lane == 0) {
+            e.var[o] = e.ctau[o] = e.cnu[o] = e.lz[o] = e.dm[o] = 0.0;
+            e.bad[o] = 0;
+        }
+        return;
+    }
+    const double s = row_sqnorm_d2(A.base + b * A.cstride + (int64_t)(np + r) * A.ld, np, lane);
+    const double var = K.base[b * K.cstride + (int64_t)r * K.ld + r] - s;
+    const double tau = e.tau[o], nu = e.nu[o], yi = y[r];
+    const double mu = v.fnew[b * v.vstride + r], dmu = mu - v.f[b * v.vstride + r];
+    const double tc = 1.0 / var - tau, nc = mu / var - nu;
+    const double muc = nc / tc, vc = 1.0 / tc;
+    const EpMoments q = ep_quad_moments<LIK>(yi * muc, vc, lane);
+    if (lane != 0) return;
+    const double muh = muc + yi * q.e1;
+    const double vh = q.e2 - q.e1 * q.e1;
+    const double tn = fmax(1.0 / vh - tc, 0.0), nn = muh / vh - nc;
+    e.var[o] = var;
+    e.ctau[o] = (1.0 - damping) * tau + damping * tn;
+    e.cnu[o] = (1.0 - damping) * nu + damping * nn;
+    e.lz[o] = q.lz + 0.5 * log1p(tau / tc) + 0.5 * nu * mu - 0.5 * nu * nu * var +
+              0.5 * muc * tc * (tau * muc - 2.0 * nu) * var;
+    e.dm[o] = dmu * dmu;
+    e.bad[o] = (tc > 0.0 && tc < INFINITY && q.covered) ? 0 : 1;  // (a NaN fails the comparisons)
+}
+
+void launch_ep_sites_q(int lik, MatB A, MatB K, int n, int nb, NewtonVecs v, const double* y,
+                       EpVecs e, double damping, Live live, int nchains, hipStream_t s) {
+    APM_LIK_DISPATCH(lik, APM_LAUNCH(k_ep_sites_q<LIK>, dim3((64 * nb + 3) / 4, nchains),
+                                     dim3(256), 0, s, A, K, n, nb, v, y, e, damping, live));
 }
 
 // Per chain: the rows' terms summed in a fixed order (block_sum_d: each thread its rows in

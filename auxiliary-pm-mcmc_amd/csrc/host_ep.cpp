@@ -1,7 +1,9 @@
 // Parallel expectation propagation for the probit (ep.hip): the sweep loop. One
 // sweep is the posterior from the current sites, which is the fp64 Newton iteration's algebra with
 // W := tau~ and b := nu~ (newton(..., mixed = false, ...)), the rows of V^T = (K S^1/2) L^-T by
-// grad_block's first pass, and the site kernel; one host read of the per-chain flags per sweep.
+// grad_block's first pass, and the site kernel - the probit's closed form, or with the context's
+// quadrature switch on the rule of DESIGN.md §27 for either likelihood; one host read of the
+// per-chain flags per sweep.
 #include "apm_host.h"
 
 namespace apm_host {
@@ -54,7 +56,12 @@ int ep_fit(apm_ctx* c, int count, std::vector<int>& st_h) {
         chol_solve_rows(c, c->A, nb, /*row_start=*/nb, /*R=*/2 * nb, /*Cb=*/nb, count);
         {   // bytes: the n solved rows of np entries each (the vectors are small beside them)
             ProfScope ps(c, APM_PROF_EP_SITES, 8.0 * (double)c->n * np * c->live_n);
-            launch_ep_sites(c->A, c->K, c->n, nb, c->v, c->y, c->ep, c->ep_damping, lv, count, s);
+            if (c->ep_quad)
+                launch_ep_sites_q(c->lik, c->A, c->K, c->n, nb, c->v, c->y, c->ep, c->ep_damping,
+                                  lv, count, s);
+            else
+                launch_ep_sites(c->A, c->K, c->n, nb, c->v, c->y, c->ep, c->ep_damping, lv, count,
+                                s);
         }
         launch_ep_chain(c->ep, c->v, c->n, np, c->ldet, c->lstride, nb, c->ep_tol,
                         APM_STATUS_EP_CAVITY, c->active, c->status, c->n_iter, count, s);

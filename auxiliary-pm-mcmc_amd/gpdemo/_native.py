@@ -101,6 +101,10 @@ _SIGS = {
     'apm_ep_grad': (_i, [_p, _i64, _p, _i64, _p, _p, _i64, _p, _p]),
     'apm_ep': (_i, [_i, _p, _i64, _i64, _p, _i, _d, _d, _i64, _p, _p, _p, _p, _p, _i64, _p, _p,
                     _p]),
+    'apm_ep_lik': (_i, [_i, _i, _p, _i64, _i64, _p, _i, _d, _d, _i64, _p, _p, _p, _p, _p, _i64, _p,
+                        _p, _p]),
+    'apm_set_ep_quadrature': (_i, [_p, _i]),
+    'apm_ep_quadrature': (_i, [_p]),
     'apm_laplace': (_i, [_i, _p, _i64, _i64, _p, _i, _i, _d, _i64, _p, _p, _i64, _p, _p, _p]),
     'apm_laplace_lik': (_i, [_i, _i, _p, _i64, _i64, _p, _i, _i, _d, _i64, _p, _p, _i64, _p, _p,
                              _p]),
@@ -233,9 +237,11 @@ def laplace(K, y, calc_cov, calc_lml, diff_f_tol, max_iters, device=None, likeli
     return f, C, float(lml[0]), int(nit[0]), int(st[0])
 
 
-def ep(K, y, calc_cov, damping, diff_tol, max_sweeps, device=None):
-    """Stand-alone EP fit on a K of the caller's (include/apm.h apm_ep):
-    ``(mu, var, tau, nu, C, logz, n_sweeps, status)``, C None without calc_cov."""
+def ep(K, y, calc_cov, damping, diff_tol, max_sweeps, device=None, likelihood='probit'):
+    """Stand-alone EP fit on a K of the caller's (include/apm.h apm_ep / apm_ep_lik):
+    ``(mu, var, tau, nu, C, logz, n_sweeps, status)``, C None without calc_cov. The probit takes
+    the closed-form tilted moments, the logit the quadrature rule."""
+    lik = likelihood_code(likelihood)
     lib = load_library()
     K = _f64(K)
     y = _f64(y)
@@ -245,10 +251,13 @@ def ep(K, y, calc_cov, damping, diff_tol, max_sweeps, device=None):
     logz = np.zeros(1)
     nsw = np.zeros(1, dtype=np.int64)
     st = np.zeros(1, dtype=np.int32)
-    _check(lib.apm_ep(_device(device), _ptr(K), n, n, _ptr(y),
-                      int(bool(calc_cov)), float(damping), float(diff_tol), int(max_sweeps),
-                      _ptr(mu), _ptr(var), _ptr(tau), _ptr(nu), _ptr(C), n, _ptr(logz), _ptr(nsw),
-                      _ptr(st)))
+    tail = (_ptr(K), n, n, _ptr(y), int(bool(calc_cov)), float(damping), float(diff_tol),
+            int(max_sweeps), _ptr(mu), _ptr(var), _ptr(tau), _ptr(nu), _ptr(C), n, _ptr(logz),
+            _ptr(nsw), _ptr(st))
+    if lik == LIK_PROBIT:  # (the entry point that predates the likelihood argument)
+        _check(lib.apm_ep(_device(device), *tail))
+    else:
+        _check(lib.apm_ep_lik(_device(device), lik, *tail))
     return mu, var, tau, nu, C, float(logz[0]), int(nsw[0]), int(st[0])
 
 
@@ -323,10 +332,11 @@ class Context(object):
     life: every cache slot it writes is read back under the same one."""
 
     def __init__(self, X, y, kernel_kind, epsilon, n_imp, max_batch=1, n_slots=4, n_ubufs=4,
-                 device=None, likelihood='probit'):
+                 device=None, likelihood='probit', ep_quadrature=False):
         lik = likelihood_code(likelihood)
         lib = load_library()
         self.lib = lib
+        self.ep_quadrature = False
         self.device = _device(device)
         y = _f64(y)
         self.n = y.shape[0]
@@ -348,6 +358,8 @@ class Context(object):
         self.likelihood = likelihood
         if lik != LIK_PROBIT:  # (the library's default)
             _check(lib.apm_set_likelihood(self._h, lik), self._h)
+        if ep_quadrature:
+            self.set_ep_quadrature(True)
         self.slots = _SlotPool(self)
         self.ubufs = _Pool(int(n_ubufs))
         # calls per batch size (bench.py reports the timed region's; launch shapes depend on it)
@@ -496,7 +508,18 @@ class Context(object):
         where status != 0 (include/apm.h apm_laplace_grad)."""
         return self._gradient(self.lib.apm_laplace_grad, thetas)
 
-    def set_ep(self, damping=0.8, diff_tol=1e-8, max_sweeps=100):
+    def set_ep_quadrature(self, on):
+        """EP's tilted moments by the quadrature rule (include/apm.h apm_set_ep_quadrature):
+        needed for, and only then accepted on, a logit context."""
+        _check(self.lib.apm_set_ep_quadrature(self._h, int(bool(on))), self._h)
+        self.ep_quadrature = bool(on)
+
+    def set_ep(self, damping=0.8, diff_tol=1e-8, max_sweeps=100, quadrature=None):
+        """The EP settings of every later fit on the context. `quadrature` (True / False) is the
+        switch of :meth:`set_ep_quadrature`, set first (a logit context is refused without it);
+        None leaves the switch as the context has it (off unless ``ep_quadrature=True``)."""
+        if quadrature is not None:
+            self.set_ep_quadrature(quadrature)
         _check(self.lib.apm_set_ep(self._h, float(damping), float(diff_tol), int(max_sweeps)),
                self._h)
 

@@ -179,6 +179,14 @@ def _spread_result(logf, ess, wmax, block, n_cubic_ops):
             'ess': ess, 'wmax': wmax, 'block': int(block), 'n_cubic_ops': int(n_cubic_ops)}
 
 
+def _require_quadrature(likelihood, quadrature):
+    """EP's closed-form tilted moments are the probit's: NotImplementedError for another
+    likelihood unless the moments come by quadrature (before any device call)."""
+    if _native.likelihood_code(likelihood) != _native.LIK_PROBIT and not quadrature:
+        raise NotImplementedError('expectation propagation is implemented for the probit '
+                                  'likelihood only, unless quadrature=True')
+
+
 def _check_spread_args(n_imp, n_rep, blocks):
     """ValueError for what apm_is_spread would refuse, before any device call."""
     if n_imp is None or int(n_imp) < 1:
@@ -209,7 +217,7 @@ class _SpreadMixin(object):
         _check_spread_args(n_imp, n_rep, blocks)
         ctx = self._prob.ctx(int(n_imp))
         if self._spread_est == _native.EST_IS_EP:
-            ctx.set_ep(*self.ep_settings)
+            ctx.set_ep(*self.ep_settings, quadrature=self.quadrature)
         ctx.u_normal([_UBUF], [seed], [0])
         slot = ctx.slots.acquire()
         try:
@@ -303,27 +311,29 @@ class LogMarginalLikelihoodEPEstimator(_EstimatorBase):
     call signature is the Laplace estimator's, so it can stand wherever that one does (e.g. as
     the deterministic target of PM-MH). ``n_cubic_ops`` grows by 2 per sweep, one factorisation
     and one matrix triangular solve: the project's own accounting. ``damping``, ``diff_tol`` and
-    ``max_sweeps`` are the EP settings; ``likelihood='logit'`` raises ``NotImplementedError``
-    (its tilted moments need quadrature)."""
+    ``max_sweeps`` are the EP settings. ``quadrature=True`` takes the tilted moments by the
+    quadrature rule of DESIGN.md §27 instead of the probit's closed form; ``likelihood='logit'``
+    needs it and raises ``NotImplementedError`` without it."""
 
     def __init__(self, X, y, kernel_func, likelihood='probit', damping=0.8, diff_tol=1e-8,
-                 max_sweeps=100):
-        if _native.likelihood_code(likelihood) != _native.LIK_PROBIT:
-            raise NotImplementedError('expectation propagation is implemented for the probit '
-                                      'likelihood only')
+                 max_sweeps=100, quadrature=False):
+        _require_quadrature(likelihood, quadrature)
         super(LogMarginalLikelihoodEPEstimator, self).__init__(X, y, kernel_func, likelihood)
         self.ep_settings = (float(damping), float(diff_tol), int(max_sweeps))
+        self.quadrature = bool(quadrature)
         self.n_sweeps = None
 
     def __call__(self, theta):
         if self._prob.device_gram:
             ctx = self._prob.ctx(1)
-            ctx.set_ep(*self.ep_settings)
+            ctx.set_ep(*self.ep_settings, quadrature=self.quadrature)
             logz, _, _, _, _, st, nsw = ctx.ep(np.atleast_1d(theta)[None])
             logz, st, nsw = float(logz[0]), int(st[0]), int(nsw[0])
         else:
             self.kernel_func(self._K, self.X, theta)
-            logz, nsw, st = _native.ep(self._K, self.y, False, *self.ep_settings)[5:]
+            # (a K of the caller's: apm_ep_lik, the probit's closed form or the logit's rule)
+            logz, nsw, st = _native.ep(self._K, self.y, False, *self.ep_settings,
+                                       likelihood=self.likelihood)[5:]
         raise_for_ep_status(st, self.ep_settings[2])
         self.n_sweeps = nsw
         self.n_cubic_ops += 2 * nsw
@@ -335,14 +345,15 @@ class LogMarginalLikelihoodApproxPosteriorISEstimator(_SpreadMixin, _EstimatorBa
     proposal (reference estimators.py:90-241). ``ns``: (n_data, n_imp_sample) N(0,1) draws.
 
     With ``post_approx_func=ep_approximation`` the proposal is the posterior of the converged
-    expectation-propagation fit instead (``EST_IS_EP`` theta-calls; probit only:
-    ``likelihood='logit'`` raises ``NotImplementedError``). ``damping``, ``diff_tol`` and
+    expectation-propagation fit instead (``EST_IS_EP`` theta-calls, DESIGN.md §17;
+    ``likelihood='logit'`` needs ``quadrature=True``, the tilted moments by the rule of DESIGN.md
+    §27, and raises ``NotImplementedError`` without it). ``damping``, ``diff_tol`` and
     ``max_sweeps`` are that fit's settings; ``n_cubic_ops`` then grows by two per sweep plus the
     estimator's own three."""
 
     def __init__(self, X, y, kernel_func, post_approx_func, likelihood='probit', damping=0.8,
-                 diff_tol=1e-8, max_sweeps=100):
-        lik = _native.likelihood_code(likelihood)
+                 diff_tol=1e-8, max_sweeps=100, quadrature=False):
+        _native.likelihood_code(likelihood)
         name = getattr(post_approx_func, '__name__', '')
         if not (getattr(post_approx_func, 'apm_fused', False) or
                 name == 'laplace_approximation'):
@@ -351,13 +362,13 @@ class LogMarginalLikelihoodApproxPosteriorISEstimator(_SpreadMixin, _EstimatorBa
                 '(gpdemo.latent_posterior_approximations.laplace_approximation / '
                 'ep_approximation); got {0!r}'.format(post_approx_func))
         self._est = _native.EST_IS_EP if name == 'ep_approximation' else _native.EST_IS
-        if self._est == _native.EST_IS_EP and lik != _native.LIK_PROBIT:
-            raise NotImplementedError('expectation propagation is implemented for the probit '
-                                      'likelihood only')
+        if self._est == _native.EST_IS_EP:
+            _require_quadrature(likelihood, quadrature)
         super(LogMarginalLikelihoodApproxPosteriorISEstimator, self).__init__(
             X, y, kernel_func, likelihood)
         self.post_approx_func = post_approx_func
         self.ep_settings = (float(damping), float(diff_tol), int(max_sweeps))
+        self.quadrature = bool(quadrature)
         self._spread_est = self._est
 
     def _spread_raise(self, status, ctx):
@@ -377,7 +388,7 @@ class LogMarginalLikelihoodApproxPosteriorISEstimator(_SpreadMixin, _EstimatorBa
         if cached_results is None:
             ctx = self._prob.ctx(ns.shape[1])
             if self._est == _native.EST_IS_EP:
-                ctx.set_ep(*self.ep_settings)
+                ctx.set_ep(*self.ep_settings, quadrature=self.quadrature)
             ctx.u_upload(_UBUF, ns)
             slot = ctx.slots.acquire()
             cache = DeviceCache(ctx, slot, self._est, self, theta)

@@ -186,8 +186,9 @@ class EPGradient(_EvidenceGradient):
     (``apm_ep_grad``).
 
     ``kernel_func`` must be one of the device kernels (``gpdemo.kernels.make_kernel_func``); a
-    foreign callable raises ``NotImplementedError``, and so does ``likelihood='logit'`` (its
-    tilted moments need quadrature). ``damping`` / ``diff_tol`` / ``max_sweeps`` are the EP
+    foreign callable raises ``NotImplementedError``, and so does ``likelihood='logit'`` without
+    ``quadrature=True`` (the tilted moments by the quadrature rule of DESIGN.md §27; the gradient
+    itself has no likelihood in it). ``damping`` / ``diff_tol`` / ``max_sweeps`` are the EP
     settings; ``max_batch`` thetas are fitted per device call.
 
     The derivative is the explicit one at the EP fixed point, so it is only as exact as the fit
@@ -200,13 +201,13 @@ class EPGradient(_EvidenceGradient):
     _name = 'logz'
 
     def __init__(self, X, y, kernel_func, damping=0.8, diff_tol=1e-16, max_sweeps=1000,
-                 max_batch=8, device=None, likelihood='probit'):
-        if _native.likelihood_code(likelihood) != _native.LIK_PROBIT:
+                 max_batch=8, device=None, likelihood='probit', quadrature=False):
+        if _native.likelihood_code(likelihood) != _native.LIK_PROBIT and not quadrature:
             raise NotImplementedError('expectation propagation is implemented for the probit '
-                                      'likelihood only')
+                                      'likelihood only, unless quadrature=True')
         self.max_sweeps = int(max_sweeps)
         self._make_context(X, y, kernel_func, max_batch, device, likelihood)
-        self._ctx.set_ep(damping, diff_tol, max_sweeps)
+        self._ctx.set_ep(damping, diff_tol, max_sweeps, quadrature=bool(quadrature))
         self.n_sweeps = None
 
     def _evaluate(self, th):

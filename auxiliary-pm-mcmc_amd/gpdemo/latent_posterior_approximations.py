@@ -50,19 +50,22 @@ laplace_approximation.apm_fused = True
 
 
 def ep_approximation(K, y, calc_cov=True, calc_lml=False, damping=0.8, diff_tol=1e-8,
-                     max_sweeps=100, return_sites=False):
-    """Expectation-propagation approximation of the latent posterior for the probit likelihood
-    (Rasmussen & Williams §3.6; parallel EP with damped site updates), computed on
-    the GPU. No reference counterpart. The return shape is ``laplace_approximation``'s:
+                     max_sweeps=100, return_sites=False, likelihood='probit'):
+    """Expectation-propagation approximation of the latent posterior (Rasmussen & Williams §3.6;
+    parallel EP with damped site updates), computed on the GPU. ``likelihood``:
+    ``'probit'`` (closed-form tilted moments) or ``'logit'`` (moments by the quadrature rule of
+    DESIGN.md §27); a ``ValueError`` otherwise. No reference counterpart. The return shape is
+    ``laplace_approximation``'s:
     ``(mu, C, lml, n_ops)``, ``(mu, lml, n_ops)``, ``(mu, C, n_ops)`` or ``(mu, n_ops)`` with
     ``mu`` the posterior mean, ``C`` the posterior covariance, ``lml = log Z_EP`` and ``n_ops``
     the project's own count of O(N^3) operations, two per sweep (one factorisation and one matrix
     triangular solve) plus one for ``C``. With ``return_sites=True`` a dict with the site
     parameters ``tau`` and ``nu``, the marginal variances ``var`` and ``n_sweeps`` is appended.
     Raises ``MaximumIterationsExceededError`` (no convergence in ``max_sweeps``),
-    ``numpy.linalg.LinAlgError`` (a factorisation failed) or ``InvalidCavityError``."""
+    ``numpy.linalg.LinAlgError`` (a factorisation failed) or ``InvalidCavityError`` (a cavity
+    precision was not positive, or a site left the quadrature rule's covered region)."""
     mu, var, tau, nu, C, logz, n_sweeps, status = _native.ep(K, y, calc_cov, damping, diff_tol,
-                                                             max_sweeps)
+                                                             max_sweeps, likelihood=likelihood)
     raise_for_ep_status(status, max_sweeps)
     n_ops = 2 * n_sweeps + (1 if calc_cov else 0)
     out = (mu,) + ((C,) if calc_cov else ()) + ((logz,) if calc_lml else ()) + (n_ops,)

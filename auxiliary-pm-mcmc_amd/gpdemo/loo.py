@@ -67,7 +67,8 @@ class ISLeaveOneOut(object):
     """Leave-one-out predictive densities at the training points ``(X, y)`` for pairs
     ``(theta, u)``, shaped like :class:`gpdemo.predict.ISPredictor`.
 
-    ``proposal`` is the importance distribution, ``'laplace'`` or ``'ep'`` (probit only);
+    ``proposal`` is the importance distribution, ``'laplace'`` or ``'ep'`` (under
+    ``likelihood='logit'`` the EP proposal needs ``quadrature=True``, DESIGN.md §27);
     ``diff_f_tol`` / ``max_iters`` are the Newton settings, ``damping`` / ``diff_tol`` /
     ``max_sweeps`` the EP fit's. ``kernel_func`` must be a device kernel
     (``gpdemo.kernels.make_kernel_func``). The arguments are checked first and the device context
@@ -75,14 +76,15 @@ class ISLeaveOneOut(object):
 
     def __init__(self, X, y, kernel_func, n_imp, proposal='laplace', likelihood='probit',
                  max_batch=8, diff_f_tol=1e-4, max_iters=1000, damping=0.8, diff_tol=1e-8,
-                 max_sweeps=100, device=None):
+                 max_sweeps=100, device=None, quadrature=False):
         lik = _native.likelihood_code(likelihood)
         if proposal not in ('laplace', 'ep'):
             raise ValueError("proposal must be 'laplace' or 'ep', got {0!r}".format(proposal))
-        if proposal == 'ep' and lik != _native.LIK_PROBIT:
+        if proposal == 'ep' and lik != _native.LIK_PROBIT and not quadrature:
             raise NotImplementedError('expectation propagation is implemented for the probit '
-                                      'likelihood only')
+                                      'likelihood only, unless quadrature=True')
         self.likelihood, self.proposal = likelihood, proposal
+        self.quadrature = bool(quadrature)
         self._est = _native.EST_IS_EP if proposal == 'ep' else _native.EST_IS
         self._kind, self._eps = _kernel_spec(kernel_func)
         if self._kind == _native.KERNEL_PRECOMPUTED:
@@ -113,7 +115,7 @@ class ISLeaveOneOut(object):
                                   likelihood=self.likelihood)
             ctx.set_newton(*self._newton)
             if self._est == _native.EST_IS_EP:
-                ctx.set_ep(*self._ep)
+                ctx.set_ep(*self._ep, quadrature=self.quadrature)
             self._ctx = ctx
         return self._ctx
 

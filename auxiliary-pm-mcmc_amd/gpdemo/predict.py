@@ -146,19 +146,22 @@ class EPPredictor(LaplacePredictor):
     """The same predictive quantities from the expectation-propagation fit
     instead of the Laplace fit: ``mu* = k*^T a``, ``var* = k** - |L^-1 (S^1/2 . k*)|^2`` with the
     EP sites' ``S = diag(tau~)``, ``a`` and ``L = chol(I + S^1/2 K S^1/2)``, ``pi* = Phi(mu* /
-    sqrt(1 + var*))`` (Rasmussen & Williams Alg. 3.6). Probit only: ``likelihood='logit'`` raises
-    ``NotImplementedError``. ``damping``, ``diff_tol`` and ``max_sweeps`` are the EP settings;
-    the methods are :class:`LaplacePredictor`'s, ``self.n_iter`` holding the sweep counts."""
+    sqrt(1 + var*))`` (Rasmussen & Williams Alg. 3.6). ``quadrature=True`` takes the tilted
+    moments by the quadrature rule of DESIGN.md §27; ``likelihood='logit'`` needs it (``pi*`` is
+    then the Gauss-Hermite average of sigma, as :class:`LaplacePredictor`'s) and raises
+    ``NotImplementedError`` without it. ``damping``, ``diff_tol`` and ``max_sweeps`` are the EP
+    settings; the methods are :class:`LaplacePredictor`'s, ``self.n_iter`` holding the sweep
+    counts."""
 
     def __init__(self, X, y, kernel_func, X_test, damping=0.8, diff_tol=1e-8, max_sweeps=100,
-                 max_batch=8, device=None, likelihood='probit'):
-        if _native.likelihood_code(likelihood) != _native.LIK_PROBIT:
+                 max_batch=8, device=None, likelihood='probit', quadrature=False):
+        if _native.likelihood_code(likelihood) != _native.LIK_PROBIT and not quadrature:
             raise NotImplementedError('expectation propagation is implemented for the probit '
-                                      'likelihood only')
+                                      'likelihood only, unless quadrature=True')
         super(EPPredictor, self).__init__(X, y, kernel_func, X_test, max_batch=max_batch,
                                           device=device, likelihood=likelihood)
         self.max_sweeps = int(max_sweeps)
-        self._ctx.set_ep(damping, diff_tol, max_sweeps)
+        self._ctx.set_ep(damping, diff_tol, max_sweeps, quadrature=bool(quadrature))
 
     def __call__(self, thetas, on_error='raise'):
         """``(mean, var, prob)``, each (T, M); a theta whose EP fit fails raises
@@ -185,22 +188,24 @@ class ISPredictor(object):
     ``n_imp``: no Gaussian approximation of ``p(f | theta, y)`` is left in it, unlike
     :class:`LaplacePredictor` and :class:`EPPredictor`.
 
-    ``proposal`` is the importance distribution, ``'laplace'`` or ``'ep'`` (probit only:
-    ``likelihood='logit'`` raises ``NotImplementedError``); ``diff_f_tol`` / ``max_iters`` are the
+    ``proposal`` is the importance distribution, ``'laplace'`` or ``'ep'`` (with
+    ``likelihood='logit'`` the EP proposal needs ``quadrature=True``, DESIGN.md §27, and raises
+    ``NotImplementedError`` without it); ``diff_f_tol`` / ``max_iters`` are the
     Newton settings, ``damping`` / ``diff_tol`` / ``max_sweeps`` the EP fit's. ``kernel_func`` must
     be a device kernel (``gpdemo.kernels.make_kernel_func``). The arguments are checked first and
     the device context is created at the first call."""
 
     def __init__(self, X, y, kernel_func, X_test, n_imp, proposal='laplace', likelihood='probit',
                  max_batch=8, diff_f_tol=1e-4, max_iters=1000, damping=0.8, diff_tol=1e-8,
-                 max_sweeps=100, device=None):
+                 max_sweeps=100, device=None, quadrature=False):
         lik = _native.likelihood_code(likelihood)
         if proposal not in ('laplace', 'ep'):
             raise ValueError("proposal must be 'laplace' or 'ep', got {0!r}".format(proposal))
-        if proposal == 'ep' and lik != _native.LIK_PROBIT:
+        if proposal == 'ep' and lik != _native.LIK_PROBIT and not quadrature:
             raise NotImplementedError('expectation propagation is implemented for the probit '
-                                      'likelihood only')
+                                      'likelihood only, unless quadrature=True')
         self.likelihood, self.proposal = likelihood, proposal
+        self.quadrature = bool(quadrature)
         self._est = _native.EST_IS_EP if proposal == 'ep' else _native.EST_IS
         self._kind, self._eps = _kernel_spec(kernel_func)
         if self._kind == _native.KERNEL_PRECOMPUTED:
@@ -232,7 +237,7 @@ class ISPredictor(object):
                                   likelihood=self.likelihood)
             ctx.set_newton(*self._newton)
             if self._est == _native.EST_IS_EP:
-                ctx.set_ep(*self._ep)
+                ctx.set_ep(*self._ep, quadrature=self.quadrature)
             self._ctx = ctx
         return self._ctx
 

@@ -14,7 +14,8 @@
  *                         likelihood (:103-106) with respect to theta
  *   apm_ep_eval        <- no reference counterpart: expectation propagation for the probit (the
  *   apm_ep_predict        fit, log Z_EP, the marginals and the predictive distribution; R&W §3.6)
- *   apm_ep                with the sweeps' factorisations and solves on the device
+ *   apm_ep                with the sweeps' factorisations and solves on the device; the logit by
+ *   apm_ep_lik            quadrature of the tilted moments (apm_set_ep_quadrature, opt-in)
  *   apm_ep_grad        <- no reference counterpart: the gradient of log Z_EP with respect to theta
  *   apm_u_eval_diag    <- no reference counterpart: the cached u-call cut into blocks of samples, with
  *   apm_is_spread         each block's weight ESS, over independent redraws of u on the device
@@ -59,7 +60,8 @@ extern "C" {
 #define APM_STATUS_GUARD 5    /* a device-side invariant of the theta-call failed (apm_guard_read;
                                  DESIGN.md §11): the value is withheld -> DeviceInvariantError
                                  (no reference counterpart: the reference has no device) */
-#define APM_STATUS_EP_CAVITY 6 /* an EP cavity precision 1/sigma_i^2 - tau~_i was <= 0 or not finite
+#define APM_STATUS_EP_CAVITY 6 /* an EP cavity precision 1/sigma_i^2 - tau~_i was <= 0 or not finite,
+                                  or (moments by quadrature) a site left the rule's covered region
                                   -> InvalidCavityError (no reference counterpart: the reference has
                                   no EP) */
 
@@ -106,9 +108,9 @@ extern "C" {
 #define APM_EST_LAPLACE 2  /* LogMarginalLikelihoodLaplaceEstimator */
 /* APM_EST_IS with the importance distribution N(mu, (K^-1 + diag tau~)^-1) of the converged
  * expectation-propagation fit (apm_set_ep settings) in place of the Laplace
- * posterior. Probit only: APM_E_INVALID on an APM_LIK_LOGIT context. The cache slot holds the
- * same state as an APM_EST_IS slot (f_post = mu, W = tau~, z = nu~, cst = 1/2 mu^T nu~ -
- * 1/2 log|B|), so apm_u_eval, apm_slot_read, apm_guard_read and the apm_cache_* calls serve it
+ * posterior. APM_E_INVALID on an APM_LIK_LOGIT context unless apm_set_ep_quadrature is on.
+ * The cache slot holds the same state as an APM_EST_IS slot (f_post = mu, W = tau~, z = nu~,
+ * cst = 1/2 mu^T nu~ - 1/2 log|B|), so apm_u_eval, apm_slot_read, apm_guard_read and the apm_cache_* calls serve it
  * unchanged. status[i]: APM_STATUS_CHOL_B, APM_STATUS_EP_CAVITY or APM_STATUS_MAXITER of the fit,
  * APM_STATUS_CHOL_K, APM_STATUS_CHOL_C or APM_STATUS_GUARD as for APM_EST_IS; a failed chain is
  * treated as a failed APM_EST_IS chain. n_cubic_ops[i] = 2 n_sweeps + 1 + 2 (two per sweep,
@@ -266,9 +268,41 @@ int apm_laplace_grad(apm_ctx *ctx, int64_t count, const double *thetas, int64_t 
  *   log Z_EP = sum log Phi(z_i) + 1/2 sum log(1 + tau~_i/tau_-i) - sum log L_ii + 1/2 nu~^T mu
  *              - 1/2 sum nu~_i^2 sigma2_i + 1/2 sum mu_-i tau_-i (tau~_i mu_-i - 2 nu~_i) sigma2_i
  * (R&W eqs. 3.65, 3.73-3.74), every sum over the n data rows in a fixed order. Everything is
- * fp64. The logit is out of scope (its tilted moments have no closed form and need quadrature):
- * every EP entry point returns APM_E_INVALID on a context whose likelihood is APM_LIK_LOGIT.
+ * fp64. These closed-form moments are the default, and with them every EP entry point returns
+ * APM_E_INVALID on a context whose likelihood is APM_LIK_LOGIT (its tilted moments have no closed
+ * form and need quadrature).
+ *
+ * Moments by quadrature (apm_set_ep_quadrature(ctx, 1)) replace step 4 for either
+ * likelihood p, and open every EP entry point, APM_EST_IS_EP included, to the logit. With t = y f,
+ * m = y mu_-, sd = sqrt(s_-), the rule forms S_k = int p(t) (t - m)^k N(t | m, s_-) dt, k = 0, 1,
+ * 2, with the largest exponent of its terms taken out, and
+ *   log Z^ = log S_0,  mu^ = mu_- + y S_1/S_0,  s^ = S_2/S_0 - (S_1/S_0)^2;
+ * log Z_EP carries sum log Z^_i in the place of sum log Phi(z_i) (the same number for the probit).
+ *   s_- <= 5: the 128-node Gauss-Hermite rule on the cavity, t_k = m + sqrt(2) sd x_k.
+ *   s_- >  5: p = H + r, H the unit step, r(t) = -sign(t) p(-|t|). The step's moments about m are
+ *     closed form (alpha = m/sd: Phi(alpha), sd phi(alpha), s_- (Phi(alpha) - alpha phi(alpha)));
+ *     the correction int_0^T p(-u) [(-u - m)^k N(-u | m, s_-) - (u - m)^k N(u | m, s_-)] du is
+ *     composite 8-node Gauss-Legendre, 8 panels on [0, T_in] and 8 on [T_in, T]. Logit: T_in = 20,
+ *     and with c = -m - s_-, T = max(40, c + 8.5 sd) for c > 0, max(40, c + sqrt(c^2 + 72.25 s_-))
+ *     otherwise. Probit: T_in = 10, T = 20.
+ * Against 30-digit quadrature the rule is within 4e-11 in log Z^, (mu^ error)/sqrt(s^) and
+ * (s^ error)/s^ for s_- from 1e-2 to e^10 and |alpha| <= 8. Its covered region is
+ *   logit:  s_- <= 5 everywhere; s_- > 5 while -m <= s_- + 7.5 sd + 20 and, where -m < s_-,
+ *           alpha >= -30 (together they admit every alpha >= -16.4);
+ *   probit: s_- <= 5 while -m sd <= 8 sqrt(2) (1 + s_-); s_- > 5 while -m <= min(5 (1 + s_-), 300).
+ * A site outside it fails its chain with APM_STATUS_EP_CAVITY, as a bad tau_- does: the label
+ * lies so many cavity deviations on the wrong side that the nodes no longer reach the tilted
+ * mass. The clamp of step 5 still removes rounding only (both likelihoods are log-concave).
  * apm_version() is unchanged: a caller detects EP by the presence of these symbols. */
+/* on = 1: every later EP fit on the context (apm_ep_eval, apm_ep_predict, apm_ep_grad, the
+ * APM_EST_IS_EP theta-calls and what reads their slots) takes its tilted moments by the rule
+ * above, under either likelihood, and apm_set_ep and those calls accept an APM_LIK_LOGIT context.
+ * on = 0 (the default): the closed-form probit moments and the refusals of the logit, exactly as
+ * before the switch existed. Any other value, or a NULL context: APM_E_INVALID. Host state only;
+ * nothing else on the context depends on it. */
+int apm_set_ep_quadrature(apm_ctx *ctx, int on);
+/* the switch (0 or 1); negative on a NULL context */
+int apm_ep_quadrature(const apm_ctx *ctx);
 /* damping in (0, 1], diff_tol >= 0, max_sweeps >= 1 (APM_E_INVALID otherwise); defaults 0.8,
  * 1e-8, 100 (DESIGN.md §16 has the study they come from) */
 int apm_set_ep(apm_ctx *ctx, double damping, double diff_tol, int64_t max_sweeps);
@@ -284,7 +318,8 @@ int apm_ep_eval(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ldt, 
                 int64_t *n_sweeps);
 /* The EP fit, then apm_predict's pass on the final S^1/2, a and L at the m test inputs Xs (m x d,
  * ldxs), in blocks of at most apm_padded_n rows: mean = k*^T a, var = s - |L^-1 (S^1/2 . k*)|^2
- * with s = exp(theta_0), prob = Phi(mean / sqrt(1 + var)); each count x m with row stride ldo,
+ * with s = exp(theta_0), prob = Phi(mean / sqrt(1 + var)) (a logit context: apm_predict's
+ * Gauss-Hermite average of sigma); each count x m with row stride ldo,
  * any of the three may be NULL, NaN rows for a failed chain. Nothing is clamped. */
 int apm_ep_predict(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ldt,
                    const double *Xs, int64_t m, int64_t ldxs, double *mean, double *var,
@@ -302,7 +337,8 @@ int apm_ep_predict(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ld
  * set a tight diff_tol (and max_sweeps to match) before fitting theta with it.
  * logz[i] (may be NULL) is bitwise the value apm_ep_eval returns for the same theta and
  * settings; status[i] is the fit's (APM_STATUS_CHOL_B, _EP_CAVITY, _MAXITER; a failed chain has
- * NaN logz and a NaN row); n_sweeps[i] (may be NULL). Probit only, ISO or ARD context of any
+ * NaN logz and a NaN row); n_sweeps[i] (may be NULL). Probit only unless apm_set_ep_quadrature is
+ * on (the expression has no likelihood in it), ISO or ARD context of any
  * family, count <= max_batch (APM_E_INVALID otherwise). A chain's outputs do not depend on its
  * position in the batch nor on the other chains. Uses the context's work matrix like every
  * theta-call; cache slots and U buffers are not touched. apm_version() is unchanged: a caller
@@ -452,12 +488,18 @@ int apm_laplace_lik(int device, int lik, const double *K, int64_t n, int64_t ldk
 /* EP's stand-alone twin of apm_laplace (no reference counterpart): the caller supplies K (n x n,
  * ldk) and the settings; mu_out, var_out, tau_out, nu_out (n each), logz_out and n_sweeps_out
  * may be NULL; calc_cov: C_out (n x n, ldc) = K - V^T V, the posterior covariance, formed as
- * apm_laplace's. Probit only. On a failed fit (*status != 0) the outputs are NaN and C_out is
- * left alone. */
+ * apm_laplace's. Probit, by the closed-form moments. On a failed fit (*status != 0) the outputs
+ * are NaN and C_out is left alone. */
 int apm_ep(int device, const double *K, int64_t n, int64_t ldk, const double *y, int calc_cov,
            double damping, double diff_tol, int64_t max_sweeps, double *mu_out, double *var_out,
            double *tau_out, double *nu_out, double *C_out, int64_t ldc, double *logz_out,
            int64_t *n_sweeps_out, int *status);
+/* the same under likelihood lik (APM_LIK_*); apm_ep is apm_ep_lik(APM_LIK_PROBIT). The probit
+ * takes the closed-form moments, the logit the quadrature rule of apm_set_ep_quadrature. */
+int apm_ep_lik(int device, int lik, const double *K, int64_t n, int64_t ldk, const double *y,
+               int calc_cov, double damping, double diff_tol, int64_t max_sweeps, double *mu_out,
+               double *var_out, double *tau_out, double *nu_out, double *C_out, int64_t ldc,
+               double *logz_out, int64_t *n_sweeps_out, int *status);
 
 /* ---- device-time accounting of the hot kernels (HIP events on the context stream) ------------ */
 #define APM_PROF_GRAM 0
