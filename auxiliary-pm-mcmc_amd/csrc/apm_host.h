@@ -459,6 +459,31 @@ void newton_is(apm_ctx* c, int count, std::vector<int>& st_h);
 void feed_chol_k(apm_ctx* c);
 void drain_chol_k(apm_ctx* c);
 void u_eval_device(apm_ctx* c, int count, bool wide);
+// The frame of a cached u-call (apm_u_eval, the diagnostics, the two LOO calls), whose arguments
+// the caller has checked. The opening stages the call's slots and U buffers, clears the device
+// statuses and, unless eval is false (apm_is_spread redraws the buffers first), enqueues
+// u_eval_device: k_ugemm leaves the per-sample sums in c->partial, k_lme log f in c->out. It
+// returns whether a slot of the call is wide (the host mirror), for the f64 twins of later
+// launches. A new cached u-call supplies its kernels between the two and names its outputs.
+bool u_call_open(apm_ctx* c, int count, const int64_t* slots, const int64_t* ubufs,
+                 bool eval = true);
+// The closing copies each row output (count rows of `width` doubles from dev, row stride dev_ld,
+// to host, row stride ld) and per-chain scalar (count doubles) whose host pointer is not null,
+// then the statuses, synchronises once and writes NaN over the rows and scalars of every chain
+// with status != 0 or whose slot's last theta-call failed. A row output without dev is one the
+// caller has enqueued the copy of itself: it is only NaN-filled.
+struct URows {
+    double* host;
+    int64_t ld;
+    const double* dev;
+    int64_t dev_ld, width;
+};
+struct UScalar {
+    double* host;
+    const double* dev;
+};
+void u_call_close(apm_ctx* c, int count, const int64_t* slots, std::initializer_list<URows> rows,
+                  std::initializer_list<UScalar> scalars, int* status);
 void theta_eval_impl(apm_ctx* c, int est, int count, bool gram, double* out_logf, int* status,
                      int64_t* nops);
 

@@ -528,7 +528,7 @@ void launch_lme(const double* partial, int64_t pstride, int nb, int S, int sp, S
 
 // ---- is_diag.hip: block estimates and weight diagnostics of the IS estimate --
 // per chain b and block j < nblk of B samples of `partial` (k_ugemm's per-sample sums, log w_s as
-// k_lme forms it): logf, ess and wmax at out[q * qstride + b * ostride + off + j], q = 0, 1, 2;
+// is_weights.h forms it): logf, ess and wmax at out[q * qstride + b * ostride + off + j], q = 0, 1, 2;
 // chains with status != 0 are skipped
 void launch_lme_blocks(const double* partial, int64_t pstride, int nb, int B, int nblk, int sp,
                        const double* cst, const int64_t* slots, double* out, int64_t qstride,
@@ -537,7 +537,7 @@ void launch_lme_blocks(const double* partial, int64_t pstride, int nb, int B, in
 
 // ---- is_predict.hip: importance-sampling predictive at test inputs ----------
 // wbar[b * sp + s] = the self-normalised weight of sample s < S from the per-sample sums the
-// theta-call's k_ugemm left in `partial` (k_lme's log w_s), exact zeros for s in [S, sp);
+// theta-call's k_ugemm left in `partial` (is_weights.h), exact zeros for s in [S, sp);
 // ess[b] = 1 / sum_s wbar_s^2
 void launch_is_weights(const double* partial, int64_t pstride, int nb, int S, int sp,
                        const double* cst, const int64_t* slots, double* wbar, double* ess,
@@ -566,18 +566,20 @@ void launch_is_finish(const double* pp, int64_t npr, int nst, int ms, const doub
                       int nchains, hipStream_t s);
 
 // ---- is_loo.hip: leave-one-out predictive densities from the IS samples ------
-// logw[b * sp + s] = log of the self-normalised weight of sample s < S (k_lme's log w_s from
+// logw[b * sp + s] = log of the self-normalised weight of sample s < S (is_weights.h, from
 // `partial`), -inf for s in [S, sp); ess[b] = k_is_weights' value; chains with status != 0 skipped
 void launch_is_logw(const double* partial, int64_t pstride, int nb, int S, int sp,
                     const double* cst, const int64_t* slots, double* logw, double* ess,
                     const int* status, int nchains, hipStream_t s);
 // per (chain, row block, sample tile): C_chol U as launch_ugemm forms it (wide: the f64 twin for
-// the call's wide slots too), f = f_post + acc, and per row < n the tile's five log-space sums of
-// t = log wbar - log p and t' = log wbar + log p into pp[((b 5 + q) np + row) (sp / 64) + tile],
-// q = 0: max t, 1: sum e^(t - max), 2: sum e^(2 (t - max)), 3: max t', 4: sum e^(t' - max')
-void launch_is_loo_gemm(int lik, SlotSet S, const int64_t* slots, UPool P, const int64_t* ubufs,
-                        const double* y, int n, int np, const double* logw, double* pp,
-                        const int* status, int nchains, bool wide, hipStream_t s);
+// the call's wide slots too), f = f_post + acc, t = log wbar - log p(y_row | f) (-inf where log
+// wbar is) and one of two epilogues on the rows < n. store: every t at out[(b np + row) sp + s],
+// rows [n, np) left alone. Else the tile's five log-space sums of t and t' = log wbar + log p at
+// out[((b 5 + q) np + row) (sp / 64) + tile], q = 0: max t, 1: sum e^(t - max), 2: sum e^(2 (t -
+// max)), 3: max t', 4: sum e^(t' - max')
+void launch_is_row_gemm(int lik, bool store, SlotSet S, const int64_t* slots, UPool P,
+                        const int64_t* ubufs, const double* y, int n, int np, const double* logw,
+                        double* out, const int* status, int nchains, bool wide, hipStream_t s);
 // the sample tiles in order -> loo, lpd, ess_loo, and the cavity density gauss from the slot's
 // rowq, W64, z64 and fpost64, at out[q * qstride + b * npr + row], q = 0 .. 3 (row < n)
 void launch_is_loo_finish(int lik, const double* pp, int64_t npr, int nst, int n, SlotSet S,
@@ -585,11 +587,6 @@ void launch_is_loo_finish(int lik, const double* pp, int64_t npr, int nst, int n
                           const int* status, int nchains, hipStream_t s);
 
 // ---- is_psis.hip: Pareto-smoothed leave-one-out densities and k-hat ----------
-// launch_is_loo_gemm's product with a storing epilogue: T[(b np + row) sp + s] = log wbar_s -
-// log p(y_row | f_row,s) for row < n (-inf where log wbar_s is), rows [n, np) left alone
-void launch_psis_gemm(int lik, SlotSet S, const int64_t* slots, UPool P, const int64_t* ubufs,
-                      const double* y, int n, int np, const double* logw, double* T,
-                      const int* status, int nchains, bool wide, hipStream_t s);
 // per (chain, row < n) of T (chain stride tstride, row stride sp, the first S columns): the tail
 // fit and the smoothed sum into out[b npr + row] (loo_psis) and out[qstride + b npr + row] (khat);
 // per chain the fit on logw[b sp ..] into khat_w[b]. S <= APM_PSIS_MAX_SAMPLES.

@@ -1,9 +1,10 @@
 // The C-ABI (include/apm.h): argument checks, the per-call staging of the host's inputs, the
 // translation of a HipError into APM_E_HIP and the NaN rows of failed chains, each frame written
-// once (ctx_call, cached_call, check_theta_call, finish_rows). The orchestration behind the entry
-// points is in the host_*.cpp units (apm_host.h): a batched theta-call here names its fit and its
-// tail there and launches nothing itself. What still launches from this file is one kernel behind
-// a staged copy (the U-buffer calls, apm_gram, apm_gram_cross, the self-tests, the marker).
+// once (ctx_call, cached_call, check_theta_call, check_u_call, finish_rows). The orchestration
+// behind the entry points is in the host_*.cpp units (apm_host.h): a batched theta-call here names
+// its fit and its tail there and launches nothing itself. What still launches from this file is one
+// kernel behind a staged copy (the U-buffer calls, apm_gram, apm_gram_cross, the self-tests, the
+// marker).
 #include <cmath>
 #include <limits>
 #include <mutex>
@@ -109,6 +110,27 @@ int check_theta_call(apm_ctx* c, const char* who, const ThetaArgs& a, Rest rest_
     if (a.lds && a.ldt < c->P) return no(c, "ldt < theta length");
     if (a.lds && a.ldg < c->P) return no(c, "ldg < theta length");
     if (rest_bad()) return no(c, a.rest_msg);
+    return APM_SUCCESS;
+}
+
+// ---- the cached u-calls with outputs of their own (apm_u_eval_diag, apm_is_spread, apm_is_loo,
+// apm_is_loo_psis): what each has checked, in the one order all of them keep - the context, count,
+// the pointers every such call needs and the entry point's further ones (more_null), the entry
+// point's own checks (own: the first message that applies or null, evaluated only with a context),
+// and last the two index lists. apm_u_eval keeps its single message.
+template <class Own>
+int check_u_call(apm_ctx* c, const char* who, int64_t count, const int64_t* slots,
+                 const int64_t* ubufs, const int* status, bool more_null, Own own) {
+    const auto no = [&](apm_ctx* cc, const char* m) {
+        return fail(cc, APM_E_INVALID, std::string(who) + ": " + m);
+    };
+    if (!c) return no(nullptr, "null context");
+    if (count <= 0 || count > c->max_batch) return no(c, "count outside [1, max_batch]");
+    if (!slots || !ubufs || !status || more_null) return no(c, "bad arguments");
+    if (const char* m = own()) return no(c, m);
+    if (!check_idx(c, count, slots, c->n_slots, "slot") ||
+        !check_idx(c, count, ubufs, c->n_ubufs, "ubuf"))
+        return APM_E_INVALID;
     return APM_SUCCESS;
 }
 
@@ -349,11 +371,7 @@ int apm_u_eval(apm_ctx* c, int64_t count, const int64_t* slots, const int64_t* u
         !check_idx(c, count, ubufs, c->n_ubufs, "ubuf"))
         return APM_E_INVALID;
     return ctx_call(c, SKEW, [&] {
-        upload_idx(c, (int)count, slots, ubufs);
-        HIPC(hipMemsetAsync(c->status, 0, sizeof(int) * count, c->stream));
-        bool wide = false;
-        for (int64_t b = 0; b < count; ++b) wide |= c->slot_wide[slots[b]] != 0;
-        u_eval_device(c, (int)count, wide);
+        u_call_open(c, (int)count, slots, ubufs);  // (no closing: nothing here reads slot_failed)
         read_back(c, {RB{c->out, (int)sizeof(double) * (int)count, out_logf},
                       RB{c->status, (int)sizeof(int) * (int)count, status}});
     });
@@ -362,26 +380,21 @@ int apm_u_eval(apm_ctx* c, int64_t count, const int64_t* slots, const int64_t* u
 // ---- block estimates and weight diagnostics of the IS estimate (host_is_diag.cpp) ------------
 namespace {
 
-// the checks apm_u_eval_diag and apm_is_spread share (draws: the latter's seeds / counters)
+// what apm_u_eval_diag and apm_is_spread share (draws: the latter's seeds / counters)
 int is_diag_call(apm_ctx* c, const char* who, int64_t count, const int64_t* slots,
                  const int64_t* ubufs, bool draws, const uint64_t* seeds, const uint64_t* counters,
                  int64_t n_rep, int64_t block, double* logf, double* ess, double* wmax,
                  int64_t ldo, int* status) {
-    const std::string w(who);
-    if (!c) return fail(nullptr, APM_E_INVALID, w + ": null context");
-    if (count <= 0 || count > c->max_batch)
-        return fail(c, APM_E_INVALID, w + ": count outside [1, max_batch]");
-    if (!slots || !ubufs || !status || (draws && (!seeds || !counters)))
-        return fail(c, APM_E_INVALID, w + ": bad arguments");
-    if (block < 1 || block > c->S) return fail(c, APM_E_INVALID, w + ": block outside [1, n_imp]");
-    if (n_rep < 1) return fail(c, APM_E_INVALID, w + ": n_rep < 1");
-    const int64_t nblk = c->S / block;
-    if (n_rep > APM_SPREAD_MAX_BLOCKS || n_rep * nblk > APM_SPREAD_MAX_BLOCKS)
-        return fail(c, APM_E_INVALID, w + ": n_rep * nblk above APM_SPREAD_MAX_BLOCKS");
-    if (ldo < n_rep * nblk) return fail(c, APM_E_INVALID, w + ": ldo < n_rep * nblk");
-    if (!check_idx(c, count, slots, c->n_slots, "slot") ||
-        !check_idx(c, count, ubufs, c->n_ubufs, "ubuf"))
-        return APM_E_INVALID;
+    const int rc = check_u_call(c, who, count, slots, ubufs, status,
+                                draws && (!seeds || !counters), [&]() -> const char* {
+        if (block < 1 || block > c->S) return "block outside [1, n_imp]";
+        if (n_rep < 1) return "n_rep < 1";
+        const int64_t nblk = c->S / block;
+        if (n_rep > APM_SPREAD_MAX_BLOCKS || n_rep * nblk > APM_SPREAD_MAX_BLOCKS)
+            return "n_rep * nblk above APM_SPREAD_MAX_BLOCKS";
+        return ldo < n_rep * nblk ? "ldo < n_rep * nblk" : nullptr;
+    });
+    if (rc != APM_SUCCESS) return rc;
     return ctx_call(c, SKEW, [&] {
         is_diag_run(c, (int)count, slots, ubufs, draws ? seeds : nullptr, counters, n_rep, block,
                     logf, ess, wmax, ldo, status);
@@ -408,15 +421,10 @@ int apm_is_spread(apm_ctx* c, int64_t count, const int64_t* slots, const int64_t
 int apm_is_loo(apm_ctx* c, int64_t count, const int64_t* slots, const int64_t* ubufs,
                double* out_logf, double* loo, double* lpd, double* ess_loo, double* gauss,
                int64_t ldo, double* ess, int* status) {
-    if (!c) return fail(nullptr, APM_E_INVALID, "apm_is_loo: null context");
-    if (count <= 0 || count > c->max_batch)
-        return fail(c, APM_E_INVALID, "apm_is_loo: count outside [1, max_batch]");
-    if (!slots || !ubufs || !status) return fail(c, APM_E_INVALID, "apm_is_loo: bad arguments");
-    if ((loo || lpd || ess_loo || gauss) && ldo < c->n)
-        return fail(c, APM_E_INVALID, "apm_is_loo: ldo < n");
-    if (!check_idx(c, count, slots, c->n_slots, "slot") ||
-        !check_idx(c, count, ubufs, c->n_ubufs, "ubuf"))
-        return APM_E_INVALID;
+    const int rc = check_u_call(c, "apm_is_loo", count, slots, ubufs, status, false, [&] {
+        return (loo || lpd || ess_loo || gauss) && ldo < c->n ? "ldo < n" : nullptr;
+    });
+    if (rc != APM_SUCCESS) return rc;
     return ctx_call(c, SKEW, [&] {
         is_loo_run(c, (int)count, slots, ubufs, out_logf, loo, lpd, ess_loo, gauss, ldo, ess,
                    status);
@@ -427,20 +435,13 @@ int apm_is_loo(apm_ctx* c, int64_t count, const int64_t* slots, const int64_t* u
 int apm_is_loo_psis(apm_ctx* c, int64_t count, const int64_t* slots, const int64_t* ubufs,
                     double* out_logf, double* loo_psis, double* khat, int64_t ldo, double* khat_w,
                     double* logratio, int64_t ldr, int* status) {
-    if (!c) return fail(nullptr, APM_E_INVALID, "apm_is_loo_psis: null context");
-    if (count <= 0 || count > c->max_batch)
-        return fail(c, APM_E_INVALID, "apm_is_loo_psis: count outside [1, max_batch]");
-    if (!slots || !ubufs || !status)
-        return fail(c, APM_E_INVALID, "apm_is_loo_psis: bad arguments");
-    if (c->S > APM_PSIS_MAX_SAMPLES)
-        return fail(c, APM_E_INVALID, "apm_is_loo_psis: n_imp above APM_PSIS_MAX_SAMPLES");
-    if ((loo_psis || khat) && ldo < c->n)
-        return fail(c, APM_E_INVALID, "apm_is_loo_psis: ldo < n");
-    if (logratio && ldr < (int64_t)c->n * c->S)
-        return fail(c, APM_E_INVALID, "apm_is_loo_psis: ldr < n*n_imp");
-    if (!check_idx(c, count, slots, c->n_slots, "slot") ||
-        !check_idx(c, count, ubufs, c->n_ubufs, "ubuf"))
-        return APM_E_INVALID;
+    const int rc = check_u_call(c, "apm_is_loo_psis", count, slots, ubufs, status, false,
+                                [&]() -> const char* {
+        if (c->S > APM_PSIS_MAX_SAMPLES) return "n_imp above APM_PSIS_MAX_SAMPLES";
+        if ((loo_psis || khat) && ldo < c->n) return "ldo < n";
+        return logratio && ldr < (int64_t)c->n * c->S ? "ldr < n*n_imp" : nullptr;
+    });
+    if (rc != APM_SUCCESS) return rc;
     return ctx_call(c, SKEW, [&] {
         is_psis_run(c, (int)count, slots, ubufs, out_logf, loo_psis, khat, ldo, khat_w, logratio,
                     ldr, status);

@@ -5,9 +5,8 @@
 // wide slots) and then k_lme_blocks on the per-sample sums it leaves in c->partial. apm_is_spread
 // does so n_rep times, each time after k_u_normal has redrawn the U buffers from the Philox
 // stream (seed, counter + r): every replicate is enqueued on the main stream without a host
-// synchronisation, the block values collect in the staging array, and one read-back ends the call.
-#include <limits>
-
+// synchronisation, the block values collect in the staging array, and one read-back ends the call
+// (the cached u-call's frame: u_call_open without the launches, u_call_close).
 #include "apm_host.h"
 
 namespace apm_host {
@@ -33,10 +32,8 @@ void is_diag_run(apm_ctx* c, int count, const int64_t* slots, const int64_t* ubu
     const int64_t B = c->max_batch, cap = APM_SPREAD_MAX_BLOCKS;
     const int nblk = (int)(c->S / block);
     const int64_t tot = n_rep * nblk;  // values per chain and quantity (<= cap: checked)
-    upload_idx(c, count, slots, ubufs);
-    HIPC(hipMemsetAsync(c->status, 0, sizeof(int) * count, s));
-    bool wide = false;
-    for (int b = 0; b < count; ++b) wide |= c->slot_wide[slots[b]] != 0;
+    // (the u-path is launched per replicate below, after the redraw where there is one)
+    const bool wide = u_call_open(c, count, slots, ubufs, /*eval=*/false);
     std::vector<uint64_t> keys;  // (alive until the sync below)
     if (seeds) {
         keys.resize((size_t)(B + n_rep * count));
@@ -59,20 +56,10 @@ void is_diag_run(apm_ctx* c, int count, const int64_t* slots, const int64_t* ubu
         launch_lme_blocks(c->partial, c->pstride, c->nb, (int)block, nblk, c->sp, c->Sl.cst,
                           c->d_slots, c->sd_out, B * cap, cap, r * nblk, c->status, count, s);
     }
-    double* const outs[3] = {logf, ess, wmax};
-    for (int q = 0; q < 3; ++q)
-        if (outs[q])
-            HIPC(hipMemcpy2DAsync(outs[q], sizeof(double) * ldo, c->sd_out + q * B * cap,
-                                  sizeof(double) * cap, sizeof(double) * tot, count,
-                                  hipMemcpyDeviceToHost, s));
-    HIPC(hipMemcpyAsync(status, c->status, sizeof(int) * count, hipMemcpyDeviceToHost, s));
-    sync(c);
-    // a slot whose last theta-call failed was never written: its values mean nothing
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    for (int b = 0; b < count; ++b)
-        if (status[b] != 0 || c->slot_failed[slots[b]])
-            for (double* o : outs)
-                if (o) std::fill(o + b * ldo, o + b * ldo + tot, nan);
+    u_call_close(c, count, slots,
+                 {{logf, ldo, c->sd_out, cap, tot}, {ess, ldo, c->sd_out + B * cap, cap, tot},
+                  {wmax, ldo, c->sd_out + 2 * B * cap, cap, tot}},
+                 {}, status);
 }
 
 }  // namespace apm_host

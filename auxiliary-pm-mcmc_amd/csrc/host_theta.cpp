@@ -4,6 +4,8 @@
 //   Gram -> Newton loop { prep, K b, form B|rhs, chol(B) (+ forward solve), L^T solve, a, K a,
 //   check } -> augmented chol [[B,.],[K W^1/2, K],[0, f_post^T]] -> slot -> L.U + likelihood -> LME
 // The only host syncs are one per Newton iteration (convergence flags) and one at the end.
+#include <limits>
+
 #include "apm_host.h"
 
 // the guard's bounds (k_guard_check): r1 nats of 1/2 log-determinant between the
@@ -28,6 +30,38 @@ void u_eval_device(apm_ctx* c, int count, bool wide) {
     }
     launch_lme(c->partial, c->pstride, c->nb, c->S, c->sp, c->Sl, c->d_slots, c->out, c->status,
                count, c->stream);
+}
+
+bool u_call_open(apm_ctx* c, int count, const int64_t* slots, const int64_t* ubufs, bool eval) {
+    upload_idx(c, count, slots, ubufs);
+    HIPC(hipMemsetAsync(c->status, 0, sizeof(int) * count, c->stream));
+    bool wide = false;
+    for (int b = 0; b < count; ++b) wide |= c->slot_wide[slots[b]] != 0;
+    if (eval) u_eval_device(c, count, wide);
+    return wide;
+}
+
+void u_call_close(apm_ctx* c, int count, const int64_t* slots, std::initializer_list<URows> rows,
+                  std::initializer_list<UScalar> scalars, int* status) {
+    hipStream_t s = c->stream;
+    for (const URows& r : rows)
+        if (r.host && r.dev)
+            HIPC(hipMemcpy2DAsync(r.host, sizeof(double) * r.ld, r.dev, sizeof(double) * r.dev_ld,
+                                  sizeof(double) * r.width, count, hipMemcpyDeviceToHost, s));
+    for (const UScalar& q : scalars)
+        if (q.host)
+            HIPC(hipMemcpyAsync(q.host, q.dev, sizeof(double) * count, hipMemcpyDeviceToHost, s));
+    HIPC(hipMemcpyAsync(status, c->status, sizeof(int) * count, hipMemcpyDeviceToHost, s));
+    sync(c);
+    // a slot whose last theta-call failed was never written: its values mean nothing
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int b = 0; b < count; ++b)
+        if (status[b] != 0 || c->slot_failed[slots[b]]) {
+            for (const URows& r : rows)
+                if (r.host) std::fill(r.host + b * r.ld, r.host + b * r.ld + r.width, nan);
+            for (const UScalar& q : scalars)
+                if (q.host) q.host[b] = nan;
+        }
 }
 
 namespace {

@@ -10,13 +10,13 @@
 // against the row-reversed U buffer, so no K^-1 is ever applied to a computed f_s.
 #include "apm_internal.h"
 #include "gh_logit.h"
+#include "is_weights.h"
 #include "tile64.h"
 
 // ------------------------------------------------------------------------------- weights
-// Per chain: log w_s = cst + sum_i partial[i][s] as k_lme forms it (the per-sample values the
-// theta-call's k_ugemm left in `partial`, added in the same order), wbar_s = exp(log w_s - max) /
-// sum over the S real samples (each thread its samples in order, then block_sum_d: a fixed
-// order), exact zeros for the padded columns [S, sp), ess = 1 / sum wbar_s^2.
+// Per chain, from the per-sample values the theta-call's k_ugemm left in `partial`: the
+// self-normalised weights wbar_s, exact zeros for the padded columns [S, sp), and ess = 1 / sum
+// wbar_s^2 (is_weights.h's is_self_normalise, storing the weights themselves).
 __global__ __launch_bounds__(256) void k_is_weights(const double* __restrict__ partial,
                                                     int64_t pstride, int nb, int S, int sp,
                                                     const double* __restrict__ cst,
@@ -25,33 +25,8 @@ __global__ __launch_bounds__(256) void k_is_weights(const double* __restrict__ p
                                                     double* __restrict__ ess, Live live) {
     const int b = blockIdx.x;
     if (!live_chain(live, b)) return;
-    __shared__ double red[4];
-    const double* pb = partial + b * pstride;
-    double* wb = wbar + (int64_t)b * sp;
-    const double c0 = cst[slots[b]];
-    double mx = -INFINITY;
-    for (int s = threadIdx.x; s < S; s += 256) {
-        double v = c0;
-        for (int i = 0; i < nb; ++i) v += pb[(int64_t)i * sp + s];
-        wb[s] = v;
-        mx = fmax(mx, v);
-    }
-    mx = block_max_d(mx, red);
-    double se = 0.0;
-    for (int s = threadIdx.x; s < S; s += 256) {
-        const double e = exp(wb[s] - mx);
-        wb[s] = e;
-        se += e;
-    }
-    se = block_sum_d(se, red);
-    double s2 = 0.0;
-    for (int s = threadIdx.x; s < sp; s += 256) {
-        const double w = s < S ? wb[s] / se : 0.0;
-        wb[s] = w;
-        s2 = fma(w, w, s2);
-    }
-    s2 = block_sum_d(s2, red);
-    if (threadIdx.x == 0) ess[b] = 1.0 / s2;
+    is_self_normalise<false>(partial + b * pstride, nb, S, sp, cst[slots[b]],
+                             wbar + (int64_t)b * sp, ess + b);
 }
 
 void launch_is_weights(const double* partial, int64_t pstride, int nb, int S, int sp,

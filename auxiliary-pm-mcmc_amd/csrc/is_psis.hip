@@ -4,110 +4,14 @@
 //
 // §23's product f = f_post + C_chol U once more, with an epilogue that stores every log ratio
 //   t_si = log wbar_s - log p(y_i | f_si)
-// instead of reducing it (k_psis_gemm, its f64 twin), and one workgroup per (chain, row) that sorts
-// the row in LDS, fits the generalised Pareto distribution to its upper tail (Zhang & Stephens
-// 2009 with the priors of the `loo` package) and sums the row with the tail replaced by the fitted
-// quantiles (k_psis_rows; include/apm.h has the steps). The same fit on the row log wbar gives the
-// tail shape of the weights themselves.
+// instead of reducing it (is_loo.hip's k_is_row_gemm pair with its storing epilogue), and one
+// workgroup per (chain, row) that sorts the row in LDS, fits the generalised Pareto distribution to
+// its upper tail (Zhang & Stephens 2009 with the priors of the `loo` package) and sums the row with
+// the tail replaced by the fitted quantiles (k_psis_rows; include/apm.h has the steps). The same
+// fit on the row log wbar gives the tail shape of the weights themselves.
 #include <cfloat>
 
 #include "apm_internal.h"
-#include "ugemm_tile.h"
-
-// ------------------------------------------------------------------------------- the epilogue
-// On a 64 x 64 tile of f held as is_loo.hip's loo_epilogue takes it: lp = lik_logp_mixed(y f),
-// t = log wbar - lp (-inf for a sample without weight) stored at T[row sp + column] for the rows
-// < n. The 16 lanes of a row write 16 consecutive doubles.
-template <int LIK, bool F64MAP>
-__device__ __forceinline__ void psis_epilogue(const double (&f)[2][2][4], int row0, int n,
-                                              const double* __restrict__ y,
-                                              const double* __restrict__ lwt,
-                                              double* __restrict__ T, int sp) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wr = w >> 1, wc = w & 1;
-    const int r16 = lane & 15;
-    const double lw0 = lwt[32 * wc + r16], lw1 = lwt[32 * wc + 16 + r16];
-#pragma unroll
-    for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int rl = 32 * wr + 16 * bi + (F64MAP ? F64_CROW(lane, r) : F32_CROW(lane, r));
-            if (row0 + rl >= n) continue;
-            const double yr = y[row0 + rl];
-            const double lp0 = lik_logp_mixed<LIK>(yr * f[bi][0][r]);
-            const double lp1 = lik_logp_mixed<LIK>(yr * f[bi][1][r]);
-            double* o = T + (int64_t)(row0 + rl) * sp + 32 * wc + r16;
-            o[0] = lw0 == -INFINITY ? lw0 : lw0 - lp0;
-            o[16] = lw1 == -INFINITY ? lw1 : lw1 - lp1;
-        }
-}
-
-// ------------------------------------------------------------------------------- the GEMM
-// k_is_loo_gemm's tile with the storing epilogue: ugemm_tile.h's work-item order and product, which
-// are k_ugemm's, so f_s is bitwise the f_s the weights were formed at.
-// T: [chain][row < np][sp].
-template <int LIK>
-__global__ __launch_bounds__(256) void k_psis_gemm(SlotSet S, const int64_t* __restrict__ slots,
-                                                   UPool P, const int64_t* __restrict__ ubufs,
-                                                   const double* __restrict__ y, int n, int np,
-                                                   const double* __restrict__ logw,
-                                                   double* __restrict__ T,
-                                                   const int* __restrict__ status, int nsb,
-                                                   int nchains) {
-    int b, i, sb;
-    ugemm_item(np / 64, nsb, nchains, b, i, sb);
-    if (status[b] != 0) return;
-    __shared__ float Ut[2][64][65];
-
-    const int64_t slot = slots[b];
-    if (S.wide[slot]) return;  // k_psis_gemm64
-    const int sp = P.sp;
-    f4_t acc[2][2];
-    ugemm_tile32(acc, S.L + slot * S.lstride, P.base32 + ubufs[b] * P.stride, np, sp, i, sb, Ut);
-
-    double f[2][2][4];
-    ugemm_add_fpost<false>(f, acc, S.fpost64 + slot * S.vstride, i);
-    psis_epilogue<LIK, false>(f, i * 64, n, y, logw + (int64_t)b * sp + sb * 64,
-                              T + (int64_t)b * np * sp + sb * 64, sp);
-}
-
-// The same on the f64 MFMA for the call's wide slots: k_ugemm64's product (ugemm_tile64).
-template <int LIK>
-__global__ __launch_bounds__(256) void k_psis_gemm64(SlotSet S, const int64_t* __restrict__ slots,
-                                                     UPool P, const int64_t* __restrict__ ubufs,
-                                                     const double* __restrict__ y, int n, int np,
-                                                     const double* __restrict__ logw,
-                                                     double* __restrict__ T,
-                                                     const int* __restrict__ status, int nsb) {
-    const int b = blockIdx.y;
-    if (status[b] != 0) return;
-    const int64_t slot = slots[b];
-    if (!S.wide[slot]) return;
-    const int i = (int)blockIdx.x / nsb, sb = (int)blockIdx.x % nsb;
-    __shared__ double La[64][17];
-    __shared__ double Ub[16][65];
-    const double* L = S.L64[slot];
-    if (!L) return;  // (as k_ugemm64; a slot read by a u-call has its buffer attached)
-    const int sp = P.sp;
-    d4_t acc[2][2];
-    ugemm_tile64(acc, L, P.base + ubufs[b] * P.stride, np, sp, i, sb, La, Ub);
-    double f[2][2][4];
-    ugemm_add_fpost<true>(f, acc, S.fpost64 + slot * S.vstride, i);
-    psis_epilogue<LIK, true>(f, i * 64, n, y, logw + (int64_t)b * sp + sb * 64,
-                             T + (int64_t)b * np * sp + sb * 64, sp);
-}
-
-void launch_psis_gemm(int lik, SlotSet S, const int64_t* slots, UPool P, const int64_t* ubufs,
-                      const double* y, int n, int np, const double* logw, double* T,
-                      const int* status, int nchains, bool wide, hipStream_t s) {
-    const int nb = np / 64, nsb = P.sp / 64;
-    const long total = (long)nb * nsb * nchains;
-    APM_LIK_DISPATCH(lik, APM_LAUNCH(k_psis_gemm<LIK>, dim3((unsigned)total), dim3(256), 0, s, S,
-                                     slots, P, ubufs, y, n, np, logw, T, status, nsb, nchains));
-    if (wide)
-        APM_LIK_DISPATCH(lik, APM_LAUNCH(k_psis_gemm64<LIK>, dim3((unsigned)(nb * nsb), nchains),
-                                         dim3(256), 0, s, S, slots, P, ubufs, y, n, np, logw, T,
-                                         status, nsb));
-}
 
 // ------------------------------------------------------------------------------- the rows
 // The largest tail: M <= ceil(3 sqrt(APM_PSIS_MAX_SAMPLES)) = 192, so the fit's grid has

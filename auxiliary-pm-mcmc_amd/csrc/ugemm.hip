@@ -11,6 +11,7 @@
 // vanishing gradient in f_s at the Laplace mode - as in the reference's own evaluation. The large
 // terms (1/2 W f^2, z f, the -x^2/2 of log Phi) are formed and summed in fp64.
 #include "apm_internal.h"
+#include "is_weights.h"
 #include "ugemm_tile.h"
 
 // ------------------------------------------------------------------------------- U buffers
@@ -317,7 +318,7 @@ void launch_ugemm(int lik, SlotSet S, const int64_t* slots, UPool P, const int64
                                          pstride, status, nsb));
 }
 
-// logsumexp_s(lw_s) - log S per chain
+// logsumexp_s(lw_s) - log S per chain (is_weights.h's is_lme without the diagnostics)
 __global__ __launch_bounds__(256) void k_lme(const double* __restrict__ partial, int64_t pstride,
                                              int nb, int S, int sp, SlotSet Sl,
                                              const int64_t* __restrict__ slots,
@@ -325,40 +326,7 @@ __global__ __launch_bounds__(256) void k_lme(const double* __restrict__ partial,
                                              const int* __restrict__ status) {
     const int b = blockIdx.x;
     if (status[b] != 0) return;
-    __shared__ double red[4];
-    __shared__ double lw[1024];
-    const double* pb = partial + b * pstride;
-    const double cst = Sl.cst[slots[b]];
-    double mx = -INFINITY;
-    for (int s = threadIdx.x; s < S; s += 256) {
-        double v = cst;
-        int i = 0;
-        for (; i + 16 <= nb; i += 16) {  // 16 loads in flight, added in order
-            double t[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) t[q] = pb[(int64_t)(i + q) * sp + s];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) v += t[q];
-        }
-        for (; i < nb; ++i) v += pb[(int64_t)i * sp + s];
-        if (s < 1024) lw[s] = v;
-        mx = fmax(mx, v);
-    }
-    mx = block_max_d(mx, red);
-    __syncthreads();
-    double se = 0.0;
-    for (int s = threadIdx.x; s < S; s += 256) {
-        double v;
-        if (s < 1024) {
-            v = lw[s];
-        } else {
-            v = cst;
-            for (int i = 0; i < nb; ++i) v += pb[(int64_t)i * sp + s];
-        }
-        se += exp(v - mx);
-    }
-    se = block_sum_d(se, red);
-    if (threadIdx.x == 0) out[b] = (isfinite(mx) ? mx + log(se) : mx) - log((double)S);
+    is_lme<false>(partial + b * pstride, nb, S, sp, Sl.cst[slots[b]], out + b, 0);
 }
 
 void launch_lme(const double* partial, int64_t pstride, int nb, int S, int sp, SlotSet Sl,

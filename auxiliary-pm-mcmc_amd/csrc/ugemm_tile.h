@@ -1,7 +1,7 @@
 // The u-path's product C_chol U on a 64 x 64 tile (row block i, sample block sb), once per
-// precision, for the three kernel pairs that form the samples f_s = f_post + C_chol u_s:
-// k_ugemm / k_ugemm64 (ugemm.hip: the weights), k_is_loo_gemm / k_is_loo_gemm64 (is_loo.hip) and
-// k_psis_gemm / k_psis_gemm64 (is_psis.hip). They differ in their epilogues alone. LOO and PSIS
+// precision, for the two kernel pairs that form the samples f_s = f_post + C_chol u_s:
+// k_ugemm / k_ugemm64 (ugemm.hip: the weights) and k_is_row_gemm / k_is_row_gemm64 (is_loo.hip:
+// the row-wise epilogues of LOO and PSIS). They differ in their epilogues alone. LOO and PSIS
 // need f_s bitwise as the weights were formed at it, so the work-item order, the staging and the
 // accumulation order are written once, here. The one exception is k_ugemm, which carries the text
 // of ugemm_tile32 itself (it measured 0.8 % slower through the call): a change to

@@ -223,6 +223,28 @@ def test_bitwise_properties(nat):
         np.testing.assert_array_equal(a, b)
 
 
+@pytest.mark.parametrize('likelihood', ['probit', 'logit'])
+def test_ess_and_logf_are_is_predicts_bitwise(nat, likelihood):
+    """apm_is_predict forms the weights and apm_is_loo their logarithms from one text
+    (csrc/is_weights.h): ess = 1 / sum wbar_s^2 is one value bitwise, and so is log f. N = 65 (two
+    row blocks: the ascending per-sample sum has two terms) and n_imp = 100 (a padded sample tile,
+    threads that own no sample), three chains."""
+    c = _make_case(65, 4, 5, 'ard', 365)
+    ctx = nat.Context(c['X'], c['y'], nat.KERNEL_ARD, EPS, 100, max_batch=3, n_slots=3, n_ubufs=3,
+                      likelihood=likelihood)
+    idx = np.arange(3)
+    try:
+        ctx.u_normal(idx, [41, 42, 43], [0, 0, 0])
+        logf_p, _, _, _, ess_p, st_p, _ = ctx.is_predict(nat.EST_IS, c['thetas'], idx, idx, c['Xs'])
+        logf_l, _, _, _, _, ess_l, st_l = ctx.is_loo(idx, idx)
+    finally:
+        ctx.close()
+    assert not st_p.any() and not st_l.any()
+    assert np.isfinite(ess_p).all() and np.all((ess_p >= 1.0) & (ess_p <= 100.0))
+    np.testing.assert_array_equal(ess_l, ess_p)
+    np.testing.assert_array_equal(logf_l, logf_p)
+
+
 def test_priormc_slots_are_accepted(nat):
     """A PriorMC slot (W = z = 0, factor chol(K)): loo is the prior-proposal estimate and gauss
     the prior predictive, log Phi(0) = log 1/2 at every point of a zero-mean prior."""
