@@ -371,9 +371,14 @@ int apm_u_eval(apm_ctx* c, int64_t count, const int64_t* slots, const int64_t* u
         !check_idx(c, count, ubufs, c->n_ubufs, "ubuf"))
         return APM_E_INVALID;
     return ctx_call(c, SKEW, [&] {
-        u_call_open(c, (int)count, slots, ubufs);  // (no closing: nothing here reads slot_failed)
+        u_call_open(c, (int)count, slots, ubufs);
         read_back(c, {RB{c->out, (int)sizeof(double) * (int)count, out_logf},
                       RB{c->status, (int)sizeof(int) * (int)count, status}});
+        // u_call_close's rule for the one scalar here: a slot whose last theta-call failed was
+        // never written, and c->out keeps an earlier call's value where k_lme wrote nothing
+        for (int b = 0; b < (int)count; ++b)
+            if (status[b] != 0 || c->slot_failed[slots[b]])
+                out_logf[b] = std::numeric_limits<double>::quiet_NaN();
     });
 }
 

@@ -498,6 +498,9 @@ void theta_eval_impl(apm_ctx* c, int est, int count, bool gram, double* out_logf
         for (int b = 0; b < count; ++b) c->slot_failed[pin_slots(c)[b]] = st_h[b] != 0;
     for (int b = 0; b < count; ++b) {
         status[b] = st_h[b];
+        // no kernel writes c->out[b] for a failed chain: what was read back is an earlier call's
+        // value at that position, which depends on the batches that ran before
+        if (st_h[b] != 0) out_logf[b] = std::numeric_limits<double>::quiet_NaN();
         if (nops) {
             if (est == APM_EST_PRIORMC) nops[b] = 1;                   // estimators.py:322
             else if (est == APM_EST_LAPLACE) nops[b] = it_h[b];        // lpa.py:441-443 (i)

@@ -171,7 +171,8 @@ int apm_u_combine(apm_ctx *ctx, int64_t count, const int64_t *dst, const int64_t
 /* ---- estimator calls ------------------------------------------------------------------------- */
 /* theta-call for `count` chains: thetas row i (ldt stride) -> log-estimate out_logf[i]; the
  * per-theta state is written to cache slot slots[i]. ubufs/slots are ignored for APM_EST_LAPLACE.
- * n_cubic_ops[i] follows the reference's accounting (estimators.py:81,217,322). */
+ * n_cubic_ops[i] follows the reference's accounting (estimators.py:81,217,322). out_logf[i] is
+ * NaN where status[i] != 0. */
 int apm_theta_eval(apm_ctx *ctx, int estimator, int64_t count, const double *thetas, int64_t ldt,
                    const int64_t *ubufs, const int64_t *slots, double *out_logf, int *status,
                    int64_t *n_cubic_ops);
@@ -345,7 +346,8 @@ int apm_ep_predict(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ld
  * detects this entry point by its symbol. */
 int apm_ep_grad(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ldt, double *logz,
                 double *grad, int64_t ldg, int *status, int64_t *n_sweeps);
-/* cached u-call: reuse slots[i]'s per-theta state with draws ubufs[i] */
+/* cached u-call: reuse slots[i]'s per-theta state with draws ubufs[i]; out_logf[i] is NaN where
+ * status[i] != 0 or the slot's last theta-call failed (such a slot holds no state) */
 int apm_u_eval(apm_ctx *ctx, int64_t count, const int64_t *slots, const int64_t *ubufs,
                double *out_logf, int *status);
 /* ---- replicate spread and weight diagnostics of the IS estimate (no reference counterpart;
