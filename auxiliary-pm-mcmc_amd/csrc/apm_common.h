@@ -15,6 +15,9 @@ typedef double d4_t __attribute__((ext_vector_type(4)));
 typedef float f4_t __attribute__((ext_vector_type(4)));
 typedef float f2_t __attribute__((ext_vector_type(2)));
 typedef double d2_t __attribute__((ext_vector_type(2)));
+// operands of __builtin_amdgcn_global_load_lds (LDS-DMA staging)
+typedef __attribute__((address_space(3))) void lds_void_t;
+typedef __attribute__((address_space(1))) void glb_void_t;
 
 // per-chain status codes (mirrored in gpdemo/_native.py)
 enum {

@@ -7,6 +7,7 @@
 #include "apm_common.h"
 #include "tile_lists.h"  // the update lists the launchers below run over (plain C++)
 #include "tri_index.h"   // lower_tri_index (plain C++ as well)
+#include "update_item.h"  // the lists' entry formats and the work-item order (plain C++ as well)
 
 // A batched fp64 matrix: chain b's element (r, c) lives at base[b*cstride + r*ld + c].
 struct MatB {

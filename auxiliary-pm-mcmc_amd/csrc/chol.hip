@@ -106,22 +106,11 @@ long update_tile_count(int i0, int R, int j0, int jend) {
     return n;
 }
 
-// Work item w -> (chain, tile) with an XCD-aware remap: workgroups are dealt round-robin over the
-// 8 XCDs (MI355X_MICROARCH.md, dispatch), so XCD x = L % 8 is given the contiguous work range
-// [x*q+min(x,r), ...) (bijective for any count). Consecutive work items are consecutive tiles of
-// one chain in the host-built super-tile order (8x8 tiles: 8 row panels + 8 column panels = 2 MiB
-// of operands per super-tile), so the operand panels a workgroup needs are in its XCD's L2.
-__device__ __forceinline__ long xcd_remap(long L, long total) {
-    const long xcd = L & 7, q = total >> 3, r = total & 7;
-    const long base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + (L >> 3);
-}
-
-// Fused diag (fd.enabled): tiles[0] must be the diagonal tile (d, d) the next column step
-// factors. Workgroups 0 .. nchains-1 (dispatched first) update chain b's tile (d, d), keep it in
-// LDS and factor it with wave 0 (diag_compute; all four waves store it, diag_store), so its
-// latency hides under the rest of the launch;
-// the other workgroups take the remaining (ntiles - 1) tiles of every chain.
+// Work item -> (chain, list entry): update_item (update_item.h), XCD-aware. Fused diag
+// (fd.enabled): tiles[0] must be the diagonal tile (d, d) the next column step factors. Workgroups
+// 0 .. nchains-1 (dispatched first) update chain b's tile (d, d), keep it in LDS and factor it
+// (fused_diag, diag.h), so its latency hides under the rest of the launch; the other workgroups
+// take the remaining (ntiles - 1) tiles of every chain.
 __global__ __launch_bounds__(256, UPD_WPE) void k_chol_update(MatB A, int k0, int kc,
                                                               const unsigned* __restrict__ tiles,
                                                               int ntiles, int nchains, int plus,
@@ -131,21 +120,11 @@ __global__ __launch_bounds__(256, UPD_WPE) void k_chol_update(MatB A, int k0, in
         GemmSmem g;
         DiagSmem d;
     } sm;
-    int b, t;
-    const bool fused = fd.enabled && (int)blockIdx.x < nchains;
-    if (fused) {
-        b = blockIdx.x;
-        t = 0;
-    } else {
-        const int nt = fd.enabled ? ntiles - 1 : ntiles;
-        const long L = (long)blockIdx.x - (fd.enabled ? nchains : 0);
-        const long w = xcd_remap(L, (long)nt * nchains);
-        b = (int)(w / nt);
-        t = (int)(w % nt) + (fd.enabled ? 1 : 0);
-    }
+    const UpdateItem it = update_item((long)blockIdx.x, fd.enabled, ntiles, nchains);
+    const int b = it.b;
     if (!live_chain(live, b)) return;
-    const unsigned ij = tiles[t];
-    const int i = (int)(ij >> 16), j = (int)(ij & 0xffff);
+    const Tile64 e(tiles[it.t]);
+    const int i = e.i(), j = e.j();
     double* Ab = A.base + b * A.cstride;
     double* Aij = Ab + (int64_t)(i * 64) * A.ld + j * 64;
     d4_t acc[2][2];
@@ -165,31 +144,13 @@ __global__ __launch_bounds__(256, UPD_WPE) void k_chol_update(MatB A, int k0, in
         tile_gemm_nt<false>(acc, Ai, A.ld, Aj, A.ld, 64 * kc, sm.g, Cold, A.ld);
     else
         tile_gemm_nt<true>(acc, Ai, A.ld, Aj, A.ld, 64 * kc, sm.g, Cold, A.ld);
-    if (!fused) {
+    if (!it.fused) {
         tile_acc_store(acc, Aij, A.ld, wr, wc, lane);
         return;
     }
     // tile_gemm_nt ended on a barrier: the GEMM staging area is free for the diag working set
-#pragma unroll
-    for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-        for (int bj = 0; bj < 2; ++bj)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                sm.d.T[(32 * wr + 16 * bi + F64_CROW(lane, r)) * DP + 32 * wc + 16 * bj +
-                       (lane & 15)] = acc[bi][bj][r];
-    __syncthreads();
-    if (wv == 0) {  // rolled pivot loops: the unrolled (DPP) form would cost this kernel a wave
-        const bool ok = diag_compute<false>(sm.d, lane);
-        if (lane == 0) sm.d.ok = ok;
-    }
-    __syncthreads();
-    if (!sm.d.ok) {
-        if (threadIdx.x == 0) live.status[b] = fd.fail_code;
-        return;
-    }
-    diag_store<double>(sm.d, Aij, A.ld, fd.Dinv + b * fd.dstride + (int64_t)i * 4096,
-                       fd.ldet + b * fd.lstride + i, threadIdx.x, 256);
+    tile_acc_store(acc, sm.d.T, DP, wr, wc, lane);
+    fused_diag(sm.d, Aij, A.ld, b, i, fd, live);
 }
 
 void launch_chol_update(MatB A, int k0, int kc, const unsigned* tiles, int ntiles, bool plus,
@@ -201,8 +162,8 @@ void launch_chol_update(MatB A, int k0, int kc, const unsigned* tiles, int ntile
 }
 
 // ------------------------------------------------------------------------- 128x128 trailing update
-// The fp64 twin of chol32_update.hip's k_chol_update32_t128 (super-tile entries and validity rules of
-// build_update_supertiles): one 128x128 super-tile per workgroup, each wave a 64x64 tile as 4x4
+// The fp64 twin of chol32_update.hip's k_chol_update32_t128 (super-tile entries: SuperTile,
+// update_item.h): one 128x128 super-tile per workgroup, each wave a 64x64 tile as 4x4
 // v_mfma_f64_16x16x4_f64 accumulators (128 VGPRs). Per byte staged it feeds twice the MFMAs of the
 // 64x64 kernel, whose operand-load rate co-limits it. Operands move global -> LDS with 16-byte
 // LDS-DMA loads (global_load_lds_dwordx4: no staging registers, no ds_write pass), two buffers of
@@ -213,26 +174,22 @@ void launch_chol_update(MatB A, int k0, int kc, const unsigned* tiles, int ntile
 #ifndef T64_ABL
 #define T64_ABL 0
 #endif
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) void glb_void_t;
 struct __attribute__((aligned(16))) GemmSmem64T {
     double a[2][128][KS64T];
     double b[2][128][KS64T];
 };
 
 template <bool NEG, bool INIT = false>
-__device__ __forceinline__ void update_t128_body(MatB A, int k0, int kc, unsigned e, int b,
+__device__ __forceinline__ void update_t128_body(MatB A, int k0, int kc, SuperTile e, int b,
                                                  bool fused, Live live, FusedDiag<double> fd,
                                                  GemmSmem64T& smg, DiagSmem& smd, MatB S) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, wr = wv >> 1, wc = wv & 1;
     const int r16 = lane & 15, kq = lane >> 4;
-    const int ti = (int)(e >> 18), tj = (int)((e >> 4) & 0x3fff);
-    const bool rv0 = e & 1u, rv1 = e & 2u, cv0 = e & 4u, cv1 = e & 8u;
-    const int ra0 = rv0 ? ti : ti + 1, ra1 = rv1 ? ti + 1 : ti;
-    const int cb0 = cv0 ? tj : tj + 1, cb1 = cv1 ? tj + 1 : tj;
+    const int ti = e.i(), tj = e.j();
+    const int ra0 = e.ra0(), ra1 = e.ra1(), cb0 = e.cb0(), cb1 = e.cb1();
     double* Ab = A.base + b * A.cstride;
     const int oi = ti + wr, oj = tj + wc;
-    const bool mine = (wr ? rv1 : rv0) && (wc ? cv1 : cv0) && oj <= oi;
+    const bool mine = e.writes(wr, wc);
 
     // LDS-DMA staging: wave wv moves operand rows 32wv .. 32wv+31 (4 instructions of 8 rows);
     // lane l takes row +l/8 and stores slot l%8, i.e. global piece (l%8) ^ (l/8)
@@ -353,19 +310,7 @@ __device__ __forceinline__ void update_t128_body(MatB A, int k0, int kc, unsigne
                 for (int r = 0; r < 4; ++r)
                     smd.T[(16 * bi + F64_CROW(lane, r)) * DP + 16 * bj + r16] = acc[bi][bj][r];
     }
-    __syncthreads();
-    if (wv == 0) {  // rolled pivot loops (register budget), as in k_chol_update
-        const bool ok = diag_compute<false>(smd, lane);
-        if (lane == 0) smd.ok = ok;
-    }
-    __syncthreads();
-    if (!smd.ok) {
-        if (tid == 0) live.status[b] = fd.fail_code;
-        return;
-    }
-    diag_store<double>(smd, Ab + (int64_t)(ti * 64) * A.ld + tj * 64, A.ld,
-                       fd.Dinv + b * fd.dstride + (int64_t)ti * 4096, fd.ldet + b * fd.lstride + ti,
-                       tid, 256);
+    fused_diag(smd, Ab + (int64_t)(ti * 64) * A.ld + tj * 64, A.ld, b, ti, fd, live);
 }
 
 __global__ __launch_bounds__(256, 2) void k_chol_update_t128(MatB A, int k0, int kc,
@@ -377,25 +322,16 @@ __global__ __launch_bounds__(256, 2) void k_chol_update_t128(MatB A, int k0, int
         GemmSmem64T g;
         DiagSmem d;
     } sm;
-    int b, t;
-    const bool fused = fd.enabled && (int)blockIdx.x < nchains;
-    if (fused) {
-        b = blockIdx.x;
-        t = 0;
-    } else {
-        const int nt = fd.enabled ? ntiles - 1 : ntiles;
-        const long L = (long)blockIdx.x - (fd.enabled ? nchains : 0);
-        const long w = xcd_remap(L, (long)nt * nchains);
-        b = (int)(w / nt);
-        t = (int)(w % nt) + (fd.enabled ? 1 : 0);
-    }
+    const UpdateItem it = update_item((long)blockIdx.x, fd.enabled, ntiles, nchains);
+    const int b = it.b;
     if (!live_chain(live, b)) return;
+    const SuperTile e(tiles[it.t]);
     if (plus == 2)  // A_ij = I_ij + Y_i Y_j^T (the SYRK of the UL factorisation, postcov.hip)
-        update_t128_body<false, true>(A, k0, kc, tiles[t], b, fused, live, fd, sm.g, sm.d, S);
+        update_t128_body<false, true>(A, k0, kc, e, b, it.fused, live, fd, sm.g, sm.d, S);
     else if (plus)  // A_ij += ...
-        update_t128_body<false>(A, k0, kc, tiles[t], b, fused, live, fd, sm.g, sm.d, S);
+        update_t128_body<false>(A, k0, kc, e, b, it.fused, live, fd, sm.g, sm.d, S);
     else
-        update_t128_body<true>(A, k0, kc, tiles[t], b, fused, live, fd, sm.g, sm.d, S);
+        update_t128_body<true>(A, k0, kc, e, b, it.fused, live, fd, sm.g, sm.d, S);
 }
 
 void launch_chol_update_t128(MatB A, int k0, int kc, const unsigned* tiles, int ntiles, int plus,

@@ -82,9 +82,7 @@ __global__ __launch_bounds__(256, BULK ? DF_BULK_WPE : DF_WPE) void k_chol_panel
         // runs on XCD s % 8, which takes a contiguous range of chains), so that the workgroups
         // sharing a chain's diagonal-block tiles share an L2 and few chains' panels are live in
         // the Infinity Cache at a time
-        const long rows = R - row0, total = rows * nchains, L = blockIdx.x;
-        const long xcd = L & 7, q = total >> 3, rm = total & 7;
-        const long item = (xcd < rm ? xcd * (q + 1) : rm * (q + 1) + (xcd - rm) * q) + (L >> 3);
+        const long rows = R - row0, item = xcd_remap((long)blockIdx.x, rows * nchains);
         b = (int)(item / rows);
         i = row0 + (int)(item % rows);
     } else {
@@ -494,7 +492,7 @@ __global__ __launch_bounds__(512, 1) void k_panel_inv_gemm32(MatF A, int K, int 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r16 = lane & 15, kq = lane >> 4;
     __shared__ InvGemmSmem sm;
     const int npair = (nb - Kend + 1) / 2;
-    const long w = xcd_remap32((long)blockIdx.x, (long)npair * nchains);
+    const long w = xcd_remap((long)blockIdx.x, (long)npair * nchains);
     const int b = (int)(w / npair), i0 = Kend + 2 * (int)(w % npair);
     const bool two = i0 + 1 < nb;  // (an odd count leaves the last workgroup one row tile)
     if (!live_chain(live, b) || (h3ok && !h3ok[b])) return;

@@ -5,49 +5,8 @@
 #include "diag.h"
 #include "tile32.h"
 
-// The work item (chain b, list entry t) of an update workgroup, XCD-aware as in k_chol_update
-// (chol.hip). fd.enabled: workgroups 0 .. nchains-1 take entry 0, the diagonal tile (d, d) of
-// chain b, and factor it in place after updating it (fused_diag32); returns whether this one does.
-__device__ __forceinline__ bool update_item32(const FusedDiag<float>& fd, int ntiles, int nchains,
-                                              int& b, int& t) {
-    const bool fused = fd.enabled && (int)blockIdx.x < nchains;
-    if (fused) {
-        b = blockIdx.x;
-        t = 0;
-    } else {
-        const int nt = fd.enabled ? ntiles - 1 : ntiles;
-        const long L = (long)blockIdx.x - (fd.enabled ? nchains : 0);
-        const long w = xcd_remap32(L, (long)nt * nchains);
-        b = (int)(w / nt);
-        t = (int)(w % nt) + (fd.enabled ? 1 : 0);
-    }
-    return fused;
-}
-// The fused diagonal step on the updated tile (i, i) that the workgroup has put into d.T
-// (diag_compute + diag_store in fp32 arithmetic: the Newton factor is refined in fp64); a
-// breakdown sets the chain's status.
-// (kept out of line: inlined, the unrolled diagonal step doubles every update kernel's code for
-// the nchains workgroups of a launch that run it)
-__device__ __noinline__ bool diag_compute32(DiagSmem32& d, int lane) {
-    return diag_compute<true, float>(d, lane);
-}
-__device__ __forceinline__ void fused_diag32(DiagSmem32& d, float* Aii, int64_t ld, int b, int i,
-                                             const FusedDiag<float>& fd, const Live& live) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    __syncthreads();
-    if (wv == 0) {
-        const bool ok = diag_compute32(d, lane);
-        if (lane == 0) d.ok = ok;
-    }
-    __syncthreads();
-    if (!d.ok) {
-        if (threadIdx.x == 0) live.status[b] = fd.fail_code;
-        return;
-    }
-    diag_store<float>(d, Aii, ld, fd.Dinv + b * fd.dstride + (int64_t)i * 4096,
-                      fd.ldet + b * fd.lstride + i, threadIdx.x, 256);
-}
-
+// The work item of an update workgroup: update_item (update_item.h); the fused diagonal step on
+// entry 0 of a fused launch: fused_diag (diag.h).
 __global__ __launch_bounds__(256) void k_chol_update32(MatF A, int k0, int kc,
                                                        const unsigned* __restrict__ tiles,
                                                        int ntiles, int nchains, Live live,
@@ -58,11 +17,11 @@ __global__ __launch_bounds__(256) void k_chol_update32(MatF A, int k0, int kc,
         GemmSmem32 g;
         DiagSmem32 d;
     } sm;
-    int b, t;
-    const bool fused = update_item32(fd, ntiles, nchains, b, t);
+    const UpdateItem it = update_item((long)blockIdx.x, fd.enabled, ntiles, nchains);
+    const int b = it.b;
     if (!live_chain(live, b)) return;
-    const unsigned ij = tiles[t];
-    const int i = (int)(ij >> 16), j = (int)(ij & 0xffff);
+    const Tile64 e(tiles[it.t]);
+    const int i = e.i(), j = e.j();
     float* Ab = A.base + b * A.cstride;
     float* Aij = Ab + (int64_t)(i * 64) * A.ld + j * 64;
     f4_t acc[2][2];
@@ -79,19 +38,12 @@ __global__ __launch_bounds__(256) void k_chol_update32(MatF A, int k0, int kc,
         tile_gemm_nt32<true>(acc, Ab + (int64_t)(i * 64) * A.ld + k0 * 64, A.ld,
                              Ab + (int64_t)(j * 64) * A.ld + k0 * 64, A.ld, 64 * kc, sm.g, Aij,
                              A.ld);
-    if (!fused) {
+    if (!it.fused) {
         tile32_store(acc, Aij, A.ld, wr, wc, lane);
         return;
     }
-#pragma unroll
-    for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-        for (int bj = 0; bj < 2; ++bj)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                sm.d.T[(32 * wr + 16 * bi + F32_CROW(lane, r)) * DP + 32 * wc + 16 * bj +
-                       (lane & 15)] = acc[bi][bj][r];
-    fused_diag32(sm.d, Aij, A.ld, b, i, fd, live);
+    tile32_store(acc, sm.d.T, DP, wr, wc, lane);
+    fused_diag(sm.d, Aij, A.ld, b, i, fd, live);
 }
 
 void launch_chol_update32(MatF A, int k0, int kc, const unsigned* tiles, int ntiles, Live live,
@@ -187,12 +139,12 @@ __device__ __forceinline__ void rhs_row_update32(float* Ab, int64_t ld, int ti, 
 __global__ __launch_bounds__(256) void k_rhs_row_update32(MatF A, int k0, int kc,
                                                           const unsigned* __restrict__ tiles,
                                                           int ntiles, int nchains, Live live) {
-    const long w = xcd_remap32((long)blockIdx.x, (long)ntiles * nchains);
+    const long w = xcd_remap((long)blockIdx.x, (long)ntiles * nchains);
     const int b = (int)(w / ntiles);
     if (!live_chain(live, b)) return;
-    const unsigned e = tiles[w % ntiles];
-    rhs_row_update32(A.base + b * A.cstride, A.ld, (int)(e >> 18), (int)((e >> 4) & 0x3fff),
-                     e & 4u, e & 8u, k0, kc, threadIdx.x);
+    const SuperTile e(tiles[w % ntiles]);
+    rhs_row_update32(A.base + b * A.cstride, A.ld, e.i(), e.j(), e.cv(0), e.cv(1), k0, kc,
+                     threadIdx.x);
 }
 
 void launch_rhs_row_update32(MatF A, int k0, int kc, const unsigned* tiles, int ntiles, Live live,
@@ -220,23 +172,22 @@ __global__ __launch_bounds__(256, 2) void k_chol_update32_t128(MatF A, int k0, i
         GemmSmemH3 h;
         DiagSmem32 d;
     } sm;
-    int b, t;
-    const bool fused = update_item32(fd, ntiles, nchains, b, t);
+    const UpdateItem it = update_item((long)blockIdx.x, fd.enabled, ntiles, nchains);
+    const int b = it.b;
+    const bool fused = it.fused;
     if (!live_chain(live, b)) return;
-    const unsigned e = tiles[t];
-    const int ti = (int)(e >> 18), tj = (int)((e >> 4) & 0x3fff);
-    const bool rv0 = e & 1u, rv1 = e & 2u, cv0 = e & 4u, cv1 = e & 8u;
+    const SuperTile e(tiles[it.t]);
+    const int ti = e.i(), tj = e.j();
     // operand row tiles of the two halves (an invalid half reuses the valid one)
-    const int ra0 = rv0 ? ti : ti + 1, ra1 = rv1 ? ti + 1 : ti;
-    const int cb0 = cv0 ? tj : tj + 1, cb1 = cv1 ? tj + 1 : tj;
+    const int ra0 = e.ra0(), ra1 = e.ra1(), cb0 = e.cb0(), cb1 = e.cb1();
     float* Ab = A.base + b * A.cstride;
     if (ti == rhs) {  // the right-hand-side row alone (its super-tile row holds no other tile)
-        rhs_row_update32(Ab, A.ld, ti, tj, cv0, cv1, k0, kc, tid);
+        rhs_row_update32(Ab, A.ld, ti, tj, e.cv(0), e.cv(1), k0, kc, tid);
         return;
     }
     // this wave's output tile
     const int oi = ti + wr, oj = tj + wc;
-    const bool mine = (wr ? rv1 : rv0) && (wc ? cv1 : cv0) && oj <= oi;
+    const bool mine = e.writes(wr, wc);
 
     f4_t acc[4][4];
     const int nsub = (64 * kc) / KS128;
@@ -253,7 +204,7 @@ __global__ __launch_bounds__(256, 2) void k_chol_update32_t128(MatF A, int k0, i
                         -Cw[(int64_t)(16 * bi + F32_CROW(lane, r)) * A.ld + 16 * bj + r16];
     };
     // super-tile rows below hlim (the appended right-hand side row), chains flagged in h3ok
-    const bool use_h3 = H3 && ti + (rv1 ? 1 : 0) < hlim && (!h3ok || h3ok[b]);
+    const bool use_h3 = H3 && ti + (e.rv(1) ? 1 : 0) < hlim && (!h3ok || h3ok[b]);
     if (!(ROLE == UPD32_NEWTON_PLANES && use_h3)) load_old();
     // one staged slice of the fp16x3 product: this wave's 4 x 4 blocks
     auto compute_h3 = [&](int cur) {
@@ -424,7 +375,7 @@ __global__ __launch_bounds__(256, 2) void k_chol_update32_t128(MatF A, int k0, i
                     sm.d.T[(16 * bi + F32_CROW(lane, r)) * DP + 16 * bj + r16] =
                         acc[bi][bj][r];
     }
-    fused_diag32(sm.d, Ab + (int64_t)(ti * 64) * A.ld + tj * 64, A.ld, b, ti, fd, live);
+    fused_diag(sm.d, Ab + (int64_t)(ti * 64) * A.ld + tj * 64, A.ld, b, ti, fd, live);
 }
 
 void launch_chol_update32_t128(MatF A, int k0, int kc, const unsigned* tiles, int ntiles,
@@ -484,24 +435,21 @@ __global__ __launch_bounds__(512, 1) void k_chol_update32_q256(MatF A, int k0, i
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, wr = wv >> 2, wc = wv & 3;
     const int r16 = lane & 15, kq = lane >> 4;
     __shared__ GemmSmemQ sm;
-    const long w = xcd_remap32((long)blockIdx.x, (long)nq * nchains);
+    const long w = xcd_remap((long)blockIdx.x, (long)nq * nchains);
     const int b = (int)(w / nq), t = (int)(w % nq);
     if (!live_chain(live, b) || (h3ok && !h3ok[b])) return;
-    const unsigned e = quads[t];
-    const int I = (int)(e >> 20), J = (int)((e >> 8) & 0xfff), rm = (e >> 4) & 15, cm = e & 15;
-    auto rt = [&](int a) { return (rm >> a) & 1 ? I + a : I; };
-    auto ct = [&](int c) { return (cm >> c) & 1 ? J + c : J; };
+    const QuadTile e(quads[t]);
+    const int I = e.i(), J = e.j();
     // this wave's two 64x64 output tiles: rows I + 2wr + {0, 1}, column J + wc
     const int oi0 = I + 2 * wr, oj = J + wc;
-    const bool v0 = ((rm >> (2 * wr)) & 1) && ((cm >> wc) & 1) && oj <= oi0;
-    const bool v1 = ((rm >> (2 * wr + 1)) & 1) && ((cm >> wc) & 1) && oj <= oi0 + 1;
+    const bool v0 = e.writes(2 * wr, wc), v1 = e.writes(2 * wr + 1, wc);
     float* Ab = A.base + b * A.cstride;
     f4_t acc[8][4];
     // LDS-DMA staging (stage_planes): wave wv fills rows 128 (wv & 1) .. +127 of array wv >> 1
     // (0: A hi, 1: A lo, 2: B hi, 3: B lo)
     const int arr = wv >> 1, half = wv & 1;
-    const int ta = arr < 2 ? rt(2 * half) : ct(2 * half);
-    const int tb = arr < 2 ? rt(2 * half + 1) : ct(2 * half + 1);
+    const int ta = arr < 2 ? e.rt(2 * half) : e.ct(2 * half);
+    const int tb = arr < 2 ? e.rt(2 * half + 1) : e.ct(2 * half + 1);
     const unsigned short* P = pl.base + b * pl.cstride + ((arr & 1) ? pl.lo : 0) +
                               plane_lane_off(lane);
     const unsigned short* p0 = P + (int64_t)ta * 64 * 32;

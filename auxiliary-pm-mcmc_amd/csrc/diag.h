@@ -394,3 +394,32 @@ __device__ void diag_store(DiagSmemT<R>& S, TS* At, int64_t ld, TS* D, double* l
     }
 }
 
+// The fused diagonal step of an update workgroup (256 threads) on the updated tile (i, i) of
+// chain b that it has put into d.T: wave 0 factors it, all four waves store it to Aii (pitch ld),
+// fd.Dinv and fd.ldet; a breakdown sets the chain's status instead. Arithmetic in the tile's type
+// (the fp32 Newton factor is refined in fp64). The fp64 kernels take the rolled pivot loops (the
+// unrolled DPP form would cost them a wave), the fp32 kernels the unrolled ones; both out of line
+// (inlined, the diagonal step doubles every update kernel's code for the nchains workgroups of a
+// launch that run it).
+template <class TS>
+__device__ __noinline__ bool fused_diag_compute(DiagSmemT<TS>& d, int lane) {
+    return diag_compute<sizeof(TS) != 8, TS>(d, lane);
+}
+template <class TS>
+__device__ __forceinline__ void fused_diag(DiagSmemT<TS>& d, TS* Aii, int64_t ld, int b, int i,
+                                           const FusedDiag<TS>& fd, const Live& live) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    __syncthreads();
+    if (wv == 0) {
+        const bool ok = fused_diag_compute(d, lane);
+        if (lane == 0) d.ok = ok;
+    }
+    __syncthreads();
+    if (!d.ok) {
+        if (threadIdx.x == 0) live.status[b] = fd.fail_code;
+        return;
+    }
+    diag_store<TS, TS>(d, Aii, ld, fd.Dinv + b * fd.dstride + (int64_t)i * 4096,
+                       fd.ldet + b * fd.lstride + i, threadIdx.x, 256);
+}
+

@@ -221,13 +221,6 @@ __device__ __forceinline__ void tile_gemm_nt32(f4_t (&acc)[2][2], const float* _
     }
 }
 
-// Same XCD-aware work mapping as k_chol_update (chol.hip).
-__device__ __forceinline__ long xcd_remap32(long L, long total) {
-    const long xcd = L & 7, q = total >> 3, r = total & 7;
-    const long base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + (L >> 3);
-}
-
 // tile32_store written through to memory (sc1): the dataflow panel's published tiles
 __device__ __forceinline__ void tile32_store_sc1(const f4_t (&acc)[2][2], float* T, int64_t ld,
                                                  int wr, int wc, int lane) {
@@ -244,8 +237,6 @@ __device__ __forceinline__ void tile32_store_sc1(const f4_t (&acc)[2][2], float*
 
 // ------------------------------------------------------- the 128- and 256-row fp16x3 kernels
 #define KS128 32  // their slice depth
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) void glb_void_t;
 
 // LDS-DMA staging of operand planes (Planes16): a 16-byte global_load_lds moves 16 rows x 64 B
 // per wave; lane l takes row l/4 of the group and stores LDS slot l%4, i.e. logical piece

@@ -1,19 +1,21 @@
 // The tile lists every factorisation's trailing-update launches run over, one list entry per
 // workgroup and chain (plain C++: built on the host, uploaded once per launch shape by
 // host_chol64.cpp). All three cover the tiles (i, j) with i in [i0, R), j0 <= j <= min(i, jend-1),
-// each exactly once. Packed entry formats:
-//   tiles        (i << 16) | j                       one 64x64 tile (k_chol_update, k_chol_update32)
-//   super-tiles  (i << 18) | (j << 4) | rv0 | rv1 << 1 | cv0 << 2 | cv1 << 3
-//                rows i, i+1 and columns j, j+1 (tile units) with per-half validity; tile
-//                (i+a, j+c) is written iff rv_a && cv_c && j+c <= i+a (k_chol_update_t128,
-//                k_chol_update32_t128, k_rhs_row_update32)
-//   quads        (I << 20) | (J << 8) | rmask << 4 | cmask
-//                row tiles I .. I+3 and column tiles J .. J+3 with per-tile validity; tile
-//                (I+a, J+c) is written iff rmask bit a, cmask bit c and J+c <= I+a
-//                (k_chol_update32_q256)
+// each exactly once. The packed entry formats (Tile64, SuperTile, QuadTile) and which tiles an
+// entry writes: update_item.h.
 #include "tile_lists.h"
 
 #include <algorithm>
+
+#include "update_item.h"
+
+template <class Entry>
+static bool writes_any(const Entry& e) {
+    for (int a = 0; a < Entry::E; ++a)
+        for (int c = 0; c < Entry::E; ++c)
+            if (e.writes(a, c)) return true;
+    return false;
+}
 
 // tiles in super-tile order (SxS tiles, super-rows top-down, super-columns left-right, row-major
 // inside), the rows of the gap [glo, ghi) left out
@@ -25,7 +27,7 @@ std::vector<unsigned> build_update_tiles(int i0, int R, int j0, int jend, int gl
             for (int i = I; i < std::min(I + S, R); ++i) {
                 if (i >= glo && i < ghi) continue;
                 for (int j = J; j < std::min(J + S, jend); ++j)
-                    if (j <= i) v.push_back(((unsigned)i << 16) | (unsigned)j);
+                    if (j <= i) v.push_back(Tile64::pack(i, j));
             }
     return v;
 }
@@ -52,15 +54,9 @@ std::vector<unsigned> build_update_supertiles(int i0, int R, int j0, int jend, i
             for (int p = P; p < std::min(P + S, nr); ++p)
                 for (int q = Q; q < std::min(Q + S, nc); ++q) {
                     const int i = rows[p], j = j0 + 2 * q;
-                    const bool rv0 = rowv(i), rv1 = pair[p] && rowv(i + 1);
-                    const bool cv0 = j < jend, cv1 = j + 1 < jend;
-                    bool any = false;
-                    for (int a = 0; a < 2; ++a)
-                        for (int c = 0; c < 2; ++c)
-                            any |= (a ? rv1 : rv0) && (c ? cv1 : cv0) && j + c <= i + a;
-                    if (!any) continue;
-                    v.push_back(((unsigned)i << 18) | ((unsigned)j << 4) | (rv0 ? 1u : 0u) |
-                                (rv1 ? 2u : 0u) | (cv0 ? 4u : 0u) | (cv1 ? 8u : 0u));
+                    const SuperTile e(SuperTile::pack(i, j, rowv(i), pair[p] && rowv(i + 1),
+                                                      j < jend, j + 1 < jend));
+                    if (writes_any(e)) v.push_back(e.e);
                 }
     return v;
 }
@@ -79,12 +75,8 @@ std::vector<unsigned> build_update_quads(int i0, int R, int j0, int jend) {
                         if (I + a < R) rm |= 1u << a;
                         if (Jq + a < jend) cm |= 1u << a;
                     }
-                    bool any = false;
-                    for (int a = 0; a < 4; ++a)
-                        for (int c = 0; c < 4; ++c)
-                            any |= ((rm >> a) & 1) && ((cm >> c) & 1) && Jq + c <= I + a;
-                    if (!any) continue;
-                    v.push_back(((unsigned)I << 20) | ((unsigned)Jq << 8) | (rm << 4) | cm);
+                    const QuadTile e(QuadTile::pack(I, Jq, rm, cm));
+                    if (writes_any(e)) v.push_back(e.e);
                 }
     return v;
 }

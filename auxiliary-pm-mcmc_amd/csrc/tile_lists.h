@@ -1,4 +1,4 @@
-// The update lists of tile_lists.cpp (entry formats there).
+// The update lists of tile_lists.cpp (entry formats: update_item.h).
 #pragma once
 #include <vector>
 

@@ -5,11 +5,7 @@
 #pragma once
 #include <math.h>
 
-#ifdef __HIPCC__
-#define APM_HD __host__ __device__
-#else
-#define APM_HD
-#endif
+#include "apm_hd.h"
 
 APM_HD inline void lower_tri_index(int t, int& i, int& j) {
     int r = (int)floor((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);

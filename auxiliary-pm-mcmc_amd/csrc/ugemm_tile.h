@@ -16,8 +16,11 @@
 #include "tile64.h"  // F64_CROW
 
 // The work item of workgroup blockIdx.x of the fp32 kernels' 1-D grid of nb nsb nchains.
-// XCD-aware order (as k_chol_update's xcd_remap): dispatch slot s runs on XCD s % 8, and
-// consecutive work items land on the same XCD. Items run chain-major, then row block (heaviest,
+// XCD-aware order: dispatch slot s runs on XCD s % 8, and consecutive work items land on the same
+// XCD. The expression is the text of xcd_remap (update_item.h), kept here: through the call
+// k_ugemm's prologue came out three instructions shorter, its loop 12 bytes earlier, and the
+// kernel 0.2 to 0.5 % slower (as §26 found for its loop); a change to xcd_remap is
+// made here too. Items run chain-major, then row block (heaviest,
 // i.e. longest K range, first; consecutive row blocks read nearly the same rows of U), then sample
 // block fastest - so the nsb workgroups that share row block i's slice of L run together on one
 // XCD and read it once from its L2, and a chain's U stays within one XCD's L2 / the Infinity Cache.

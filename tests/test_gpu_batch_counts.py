@@ -3,8 +3,9 @@ the chain alone.
 
 The rest of the suite pins the kernels along N and S at 1 to 5 chains (8 in two files) and runs 64
 chains only in full-size estimate parities, which cannot see one wrong tile. The work-item orders
-take another path from 8 chains up: ugemm_item (ugemm_tile.h: k_ugemm, k_is_row_gemm), xcd_remap
-(chol.hip), xcd_remap32 (tile32.h) and the copy in k_chol_panel_df32 (chol32_panel.hip) deal the
+take another path from 8 chains up: xcd_remap (update_item.h), which every update kernel of
+chol.hip and chol32_update.hip and the bulk rows of k_chol_panel_df32 (chol32_panel.hip) call and
+whose text ugemm_item (ugemm_tile.h: k_ugemm, k_is_row_gemm) carries itself, deals the
 items over the 8 XCDs with a branch on rem = total & 7, total = tiles x chains. At (N, S) =
 (130, 64) the u-path has total = 3 B, so B = 9 .. 15 reach every nonzero remainder, which neither
 8 nor 64 chains can; (65, 130) has total = 6 B with a padded sample block; N = 577 adds a far

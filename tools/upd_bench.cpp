@@ -19,8 +19,8 @@ __global__ void fill(double* p, size_t n, unsigned seed) {
 static double flops_of(const std::vector<unsigned>& t, int kc) {
     double f = 0;
     for (unsigned ij : t) {
-        int i = ij >> 16, j = ij & 0xffff;
-        f += (i == j) ? 64.0 * 65 * 64 * kc : 2.0 * 64 * 64 * 64 * kc;
+        const Tile64 e(ij);
+        f += (e.i() == e.j()) ? 64.0 * 65 * 64 * kc : 2.0 * 64 * 64 * 64 * kc;
     }
     return f;
 }
