@@ -16,7 +16,7 @@ full set of thetas.
 import numpy as np
 
 import grad_restatement as gr
-import matern_restatement as mr
+from cov_restatement import Cov
 
 EPS = 1e-8
 D = 4
@@ -56,19 +56,21 @@ def case(n, family=None, kind='ard'):
     return _CASES[key]
 
 
+def cov(c):
+    return Cov(c['family'] or 'se', c['kind'])
+
+
 def gram(c, theta):
-    if c['family'] is None:
-        return gr.gram(c['kind'], c['X'], theta, EPS)
-    return mr.gram(c['family'], c['kind'], c['X'], theta, EPS)
+    return cov(c).gram(c['X'], theta, EPS)
 
 
 def gram_cross(c, Xs, theta):
     """k(Xs_i, X_j) without epsilon: the SE one as test_gpu_predict forms it, from the C oracle's
     Gram of the stacked points."""
     if c['family'] is not None:
-        return mr.gram_cross(c['family'], c['kind'], Xs, c['X'], theta)
+        return cov(c).gram_cross(Xs, c['X'], theta)
     n = c['n']
-    G = gr.gram(c['kind'], np.concatenate([c['X'], Xs]), theta, EPS)
+    G = cov(c).gram(np.concatenate([c['X'], Xs]), theta, EPS)
     return G[n:, :n].copy()
 
 

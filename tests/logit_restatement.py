@@ -1,11 +1,10 @@
 """float64 numpy/scipy restatement of the logistic likelihood's paths, shared by
 test_logit_host.py and test_gpu_logit.py. A plain module. The oracle is probit-only, so this is
-the logit's yardstick: the Newton loop of latent_posterior_approximations.py:85-99 with the logit's
-grad / W (same f0 = 0, same stopping rule, W / L / a of the LAST iteration kept beside the updated
-f), the LML, the consistent importance-sampling form of DESIGN.md §3.2 and PriorMC, the
-predictive with pi* from a 400-node Gauss-Hermite rule, and the gradient formula of include/apm.h
-with the logit's g and d3. K and k* come from the caller (the C oracle's Gram, or
-matern_restatement's).
+the logit's yardstick: grad_restatement's Newton loop (latent_posterior_approximations.py:85-99)
+with the logit's grad / W (same f0 = 0, same stopping rule, W / L / a of the LAST iteration kept
+beside the updated f), the LML, the consistent importance-sampling form of DESIGN.md §3.2 and PriorMC, the
+predictive with pi* from a 400-node Gauss-Hermite rule, and grad_restatement's gradient formula
+with the logit's g and d3. K and k* come from the caller (cov_restatement).
 
 With t = y f, sigma(u) = 1/(1 + e^-u):
     log p = log sigma(t),  grad = y sigma(-t),  W = sigma(t) sigma(-t),
@@ -40,23 +39,12 @@ def d3(f, y):
     return -y * (sp * sm) * (sm - sp)  # (sm - sp = 1 - 2 sigma(t))
 
 
+LOGIT = gr.Likelihood(log_lik, grad_W, d3)
+
+
 def newton(K, y, tol=1e-4, max_iters=1000):
-    """The Newton loop; ``diffs`` keeps every iteration's mean((f_new - f)^2)."""
-    n = y.shape[0]
-    f, diffs = np.zeros(n), []
-    while True:
-        grad, W = grad_W(f, y)
-        Ws = np.sqrt(W)
-        L = la.cholesky(np.eye(n) + Ws[:, None] * K * Ws[None, :], lower=True)
-        b = W * f + grad
-        a = b - Ws * la.cho_solve((L, True), Ws * K.dot(b))
-        f_new = K.dot(a)
-        diffs.append(np.mean((f_new - f) ** 2))
-        f = f_new
-        if diffs[-1] < tol or len(diffs) >= max_iters:
-            break
-    lml = -0.5 * a.dot(f) + log_lik(y * f).sum() - np.log(L.diagonal()).sum()
-    return dict(f=f, a=a, W=W, Ws=Ws, L=L, lml=lml, n_iter=len(diffs), diffs=diffs)
+    """grad_restatement's Newton loop with the logit's grad / W and log p."""
+    return gr.newton(K, y, tol, max_iters, LOGIT)
 
 
 def lml(K, y, tol=1e-24):
@@ -144,21 +132,9 @@ def predictive(K, Ks, y, sigma, tol=1e-4, max_iters=1000):
 
 
 def laplace_grad(K, dKs, y, tol=1e-14, max_iters=1000):
-    """dict(lml, grad (P,), n_iter, diffs): grad_restatement.laplace_grad's algebra with the
-    logit's g and d3; dKs the P matrices dK/dtheta_j (grad_restatement.dK or
-    matern_restatement.dK)."""
-    nw = newton(K, y, tol, max_iters)
-    f, a, Ws, L = nw['f'], nw['a'], nw['Ws'], nw['L']
-    g = grad_W(f, y)[0]
-    Z = la.solve_triangular(L, np.diag(Ws), lower=True)
-    R = Z.T.dot(Z)
-    V = la.solve_triangular(L, Ws[:, None] * K, lower=True)
-    dS = K.diagonal() - (V * V).sum(0)
-    s2 = 0.5 * dS * d3(f, y)
-    q = s2 - R.dot(K.dot(s2))
-    M = 0.5 * np.outer(a, a) - 0.5 * R + 0.5 * (np.outer(q, g) + np.outer(g, q))
-    grad = np.array([float((M * D).sum()) for D in dKs])
-    return dict(lml=nw['lml'], grad=grad, n_iter=nw['n_iter'], diffs=nw['diffs'], f=nw['f'])
+    """dict(lml, grad (P,), n_iter, diffs, f): grad_restatement.laplace_grad's algebra with the
+    logit's g and d3; dKs the P matrices dK/dtheta_j (cov_restatement's Cov.dK)."""
+    return gr.laplace_grad(K, dKs, y, tol, max_iters, LOGIT)
 
 
 central_differences = gr.central_differences

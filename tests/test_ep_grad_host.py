@@ -8,8 +8,9 @@ import re
 import numpy as np
 import pytest
 
-import ep_grad_restatement as eg
+import cov_restatement as cr
 import grad_restatement as gr
+from cov_restatement import Cov
 from conftest import REPO
 
 EPS = 1e-8
@@ -29,8 +30,8 @@ def cases():
     """Data and the converged restatement gradient per shape and theta, computed once."""
     out = []
     for n, d, kind, seed in SHAPES:
-        c = gr.make_case(n, d, kind, seed, sigmas=SIGMAS)
-        c['ref'] = [eg.ep_grad(kind, c['X'], c['y'], th, EPS, **CONVERGED) for th in c['thetas']]
+        c = gr.make_case(n, d, kind, seed, rows=SIGMAS)
+        c['ref'] = [cr.ep_grad(Cov('se', kind), c['X'], c['y'], th, EPS, **CONVERGED) for th in c['thetas']]
         out.append(c)
     return out
 
@@ -79,7 +80,7 @@ def test_argument_checks_come_before_any_device_call():
 
 def _fd_error(kind, X, y, theta, family, grad):
     fd = gr.central_differences(
-        lambda th: eg.logz(kind, X, y, th, EPS, family, **CONVERGED), theta)
+        lambda th: cr.ep_logz(Cov(family, kind), X, y, th, EPS, **CONVERGED), theta)
     return np.abs(grad - fd).max() / max(1.0, np.abs(fd).max())
 
 
@@ -97,9 +98,9 @@ def test_analytic_against_central_differences(cases, ci):
 
 
 def test_analytic_against_central_differences_matern52():
-    c = gr.make_case(65, 4, 'ard', 404, sigmas=(0.3,))
+    c = gr.make_case(65, 4, 'ard', 404, rows=(0.3,))
     th = c['thetas'][0]
-    ref = eg.ep_grad('ard', c['X'], c['y'], th, EPS, family='52', **CONVERGED)
+    ref = cr.ep_grad(Cov('52', 'ard'), c['X'], c['y'], th, EPS, **CONVERGED)
     err = _fd_error('ard', c['X'], c['y'], th, '52', ref['grad'])
     print('EP grad vs fd Matern 5/2 (65, 4, ard): {0:.3e}'.format(err))
     assert err <= 1e-6
@@ -116,8 +117,8 @@ def test_iso_equals_ard_with_equal_length_scales(cases):
     assert c['kind'] == 'iso'
     for th, iso in zip(c['thetas'], c['ref']):
         th_ard = np.r_[th[0], np.full(c['d'], th[1])]
-        ard = eg.ep_grad('ard', c['X'], c['y'], th_ard, EPS,
-                         K=eg.gram('iso', c['X'], th, EPS), **CONVERGED)
+        ard = cr.ep_grad(Cov('se', 'ard'), c['X'], c['y'], th_ard, EPS,
+                         K=Cov('se', 'iso').gram(c['X'], th, EPS), **CONVERGED)
         assert ard['n_sweeps'] == iso['n_sweeps']
         scale = max(1.0, np.abs(ard['grad'][1:]).sum())
         assert abs(iso['grad'][0] - ard['grad'][0]) <= 1e-12 * max(1.0, abs(ard['grad'][0]))
@@ -128,12 +129,12 @@ def test_epsilon_is_not_in_the_gradient():
     """epsilon = 1e-2: the gradient with dK/dtheta_0 = S matches central differences of log Z_EP
     (theta does not move the jitter), and the reading that keeps epsilon on dK/dtheta_0's diagonal
     is off by more than 1e-6."""
-    c = gr.make_case(130, 5, 'ard', 402, sigmas=(0.3, -1.0))
+    c = gr.make_case(130, 5, 'ard', 402, rows=(0.3, -1.0))
     for th in c['thetas']:
-        ref = eg.ep_grad('ard', c['X'], c['y'], th, 1e-2, **CONVERGED)
-        wrong = eg.ep_grad('ard', c['X'], c['y'], th, 1e-2, eps_in_dk0=True, **CONVERGED)
+        ref = cr.ep_grad(Cov('se', 'ard'), c['X'], c['y'], th, 1e-2, **CONVERGED)
+        wrong = cr.ep_grad(Cov('se', 'ard'), c['X'], c['y'], th, 1e-2, wrong='eps_in_dk0', **CONVERGED)
         fd = gr.central_differences(
-            lambda t: eg.logz('ard', c['X'], c['y'], t, 1e-2, **CONVERGED), th)
+            lambda t: cr.ep_logz(Cov('se', 'ard'), c['X'], c['y'], t, 1e-2, **CONVERGED), th)
         scale = max(1.0, np.abs(fd).max())
         off = np.abs(ref['grad'] - wrong['grad']).max() / scale
         print('epsilon rule theta_0 {0}: fd error {1:.3e}, wrong reading off by {2:.3e}'
@@ -154,7 +155,7 @@ def test_class_default_tolerance(cases):
     worst = 0.0
     for ci, c in enumerate(cases):
         for th, ref in zip(c['thetas'], c['ref']):
-            got = eg.ep_grad(c['kind'], c['X'], c['y'], th, EPS, **settings)
+            got = cr.ep_grad(Cov('se', c['kind']), c['X'], c['y'], th, EPS, **settings)
             err = np.abs(got['grad'] - ref['grad']).max() / max(1.0, np.abs(ref['grad']).max())
             print('default diff_tol shape {0} theta_0 {1}: {2:.3e} ({3} of {4} sweeps)'
                   .format(SHAPES[ci][:3], th[0], err, got['n_sweeps'], ref['n_sweeps']))

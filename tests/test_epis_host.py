@@ -14,6 +14,7 @@ from scipy.stats import multivariate_normal
 
 import epis_restatement as eis
 import grad_restatement as gr
+from cov_restatement import Cov
 from conftest import REPO
 
 EPS = 1e-8
@@ -75,7 +76,7 @@ def states():
         c = gr.make_case(n, d, kind, seed)
         c['st'] = []
         for th in c['thetas']:
-            K = gr.gram(kind, c['X'], th, EPS)
+            K = Cov('se', kind).gram(c['X'], th, EPS)
             c['st'].append((K, eis.state(K, c['y']), eis.laplace_state(K, c['y'])))
         out.append(c)
     return out

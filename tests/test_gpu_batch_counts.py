@@ -33,16 +33,16 @@ from scipy.special import logsumexp
 
 import apm_oracle as orc
 import batch_counts_cases as bc
-import ep_grad_restatement as eg
+import cov_restatement as cr
 import ep_restatement as ep
 import epis_restatement as eis
-import grad_restatement as gr
 import is_loo_restatement as ilr
 import is_predict_restatement as ipr
 import is_spread_restatement as sr
 import test_gpu_ep as tge
 import test_gpu_ep_grad as tgeg
 import test_gpu_grad as tgg
+from cov_restatement import Cov
 from predict_restatement import predictive
 from test_gpu_epis import IS_TOL
 from test_gpu_is_loo import W_TOL, _r32
@@ -312,12 +312,12 @@ def family_refs(refs):
         tge.assert_stop_margin(fit)
         epis = eis.state(K, y)
         out.append(dict(
-            predict=predictive(K, Ks, y, s), grad=gr.laplace_grad('ard', c['X'], y, th, EPS,
-                                                                  tol=tgg.NEWTON_TOL),
+            predict=predictive(K, Ks, y, s),
+            grad=cr.laplace_grad(Cov('se', 'ard'), c['X'], y, th, EPS, tol=tgg.NEWTON_TOL),
             is_predict=ipr.predictive(K, Ks, s, y, r['U1'][b], _fit(K, y, 'laplace', 'probit'),
                                       'probit'),
             ep=fit, ep_predict=ep.at_test_inputs(Ks, s, fit),
-            ep_grad=eg.ep_grad('ard', c['X'], y, th, EPS),
+            ep_grad=cr.ep_grad(Cov('se', 'ard'), c['X'], y, th, EPS),
             epis=eis.is_consistent(y, epis, r['U1'][b]), epis_sweeps=epis['n_sweeps']))
     return out
 

@@ -1,7 +1,7 @@
 """The constant (bias) covariance term on the device (APM_COV_BIAS): Gram and
 cross-Gram, the four estimators' theta-calls, the range flags at a large beta, the three
 predictives, the Laplace and EP gradients, beta = 0 against the base kind, batch neutrality, a
-base-kind context beside a biased one and a batched sampler - against tests/bias_restatement.py
+base-kind context beside a biased one and a batched sampler - against tests/cov_restatement.py
 and the oracle's estimators run with its kernel_func. The maxima measured on an MI355X are in
 DESIGN.md §22's parity table."""
 import math
@@ -10,10 +10,12 @@ import numpy as np
 import pytest
 
 import apm_oracle as orc
-import bias_restatement as br
+import cov_checks as cc
+import cov_restatement as cr
 import epis_restatement as eis
 import grad_restatement as gr
 import is_predict_restatement as ipr
+from cov_restatement import Cov
 
 pytestmark = pytest.mark.gpu
 
@@ -23,9 +25,11 @@ TOL = 1e-9          # fp64 against fp64 through the same factorisation (x max(1,
 NEWTON_TOL = 1e-14  # the gradient's Newton tolerance
 PROB_TOL = 1e-3     # the IS predictive's averages (2 x the 5e-4 nats of the weights)
 FLOOR, CAP = 1e-12, 1e-6  # §19's yardstick rule for its fp64 quantities
-# bias_restatement.make_case's thetas are (theta_0, log beta) in (0.3, 3, -1) x (-2, 1.5); the
-# tests use four of them (max_batch <= 4): (0.3, -2), (0.3, 1.5), (3, 1.5), (-1, -2)
+# the thetas are drawn for (theta_0, log beta) in (0.3, 3, -1) x (-2, 1.5); the tests use four of
+# them (max_batch <= 4): (0.3, -2), (0.3, 1.5), (3, 1.5), (-1, -2)
+ROWS = [(s0, lb) for s0 in (0.3, 3.0, -1.0) for lb in (-2.0, 1.5)]
 SEL = [0, 1, 3, 4]
+FAR = 1000.0  # the far test row: S* underflows to exactly 0 for the Matern kinds too
 # (purpose, family, n, d, kind) -> data seed, the first one from 1200 on whose labels are 60-95 %
 # positive and for which, at all four thetas, the restatement cannot disagree with the device on
 # an iteration count:
@@ -55,7 +59,7 @@ def _case(what, family, n, d, kind):
     """Data of one (purpose, family, shape), drawn once and left unchanged."""
     key = (what, family, n, d, kind)
     if key not in _CASES:
-        c = br.make_case(n, d, kind, SEEDS[key])
+        c = gr.make_case(n, d, kind, SEEDS[key], rows=ROWS, offset=1.0)
         c['family'], c['thetas'] = family, c['thetas'][SEL]
         _CASES[key] = c
     return _CASES[key]
@@ -68,17 +72,13 @@ def nat(gpu_available):
     return _native
 
 
+def _cov(family, kind, bias=True):
+    return Cov(family, kind, bias=bias)
+
+
 def _ctx(nat, c, n_imp=1, max_batch=4, n_slots=4, n_ubufs=4, bias=True):
-    return nat.Context(c['X'], c['y'], br.native_kind(c['family'], c['kind'], bias), EPS, n_imp,
+    return nat.Context(c['X'], c['y'], _cov(c['family'], c['kind'], bias).native_kind, EPS, n_imp,
                        max_batch=max_batch, n_slots=n_slots, n_ubufs=n_ubufs)
-
-
-def _test_inputs(c, m):
-    rng = np.random.RandomState(1000 + c['n'])
-    Xs = rng.normal(size=(m, c['d']))
-    Xs[0] = c['X'][7 % c['n']]    # coincides with a training point
-    Xs[-1] = c['X'][3 % c['n']] + 1000.0   # so far away that S* underflows to exactly 0
-    return Xs
 
 
 # ------------------------------------------------------------------ 1. Gram and cross-Gram
@@ -97,23 +97,23 @@ def _gram_inputs(n, d, kind, dup, log_beta):
     return X, th
 
 
-GRAM_CASES = ([(f, k, n, d, False) for f, k in br.FAMILY_KINDS for n, d in ((1, 1), (129, 64))] +
+GRAM_CASES = ([(f, k, n, d, False) for f, k in cr.FAMILY_KINDS for n, d in ((1, 1), (129, 64))] +
               [(f, k, 300, 7, False) for f, k in (('se', 'ard'), ('52', 'iso'))] +
               [(f, k, 200, 3, True) for f, k in (('se', 'ard'), ('52', 'iso'))])
 
 
 @pytest.mark.parametrize('family,kind,n,d,dup', GRAM_CASES)
 def test_gram_vs_restatement(nat, family, kind, n, d, dup):
-    """Entry by entry within br.gram_bound (the base kind's bound on S plus 3u |K_ref|), log beta
+    """Entry by entry within Cov.gram_bound (the base kind's bound on S plus 3u |K_ref|), log beta
     -2 and 1.5; K exactly symmetric, its diagonal s + beta + eps within 3 ulp, every entry of the
     caller's (n, n) array written (the identity padding stays inside the library)."""
     import gpdemo.kernels as krn
     for log_beta in (-2.0, 1.5):
         X, th = _gram_inputs(n, d, kind, dup, log_beta)
         K = np.full((n, n), np.nan)
-        krn.make_kernel_func(br.name(family, kind), EPS, bias=True)(K, X, th)
-        Kref = br.gram(family, kind, X, th, EPS)
-        err, bound = np.abs(K - Kref), br.gram_bound(family, kind, X, X, th, Kref)
+        krn.make_kernel_func(_cov(family, kind).name, EPS, bias=True)(K, X, th)
+        Kref = _cov(family, kind).gram(X, th, EPS)
+        err, bound = np.abs(K - Kref), _cov(family, kind).gram_bound(X, X, th, Kref)
         print('bias gram {0}: max error / bound = {1:.3f}'.format(
             (family, kind, n, d, dup, log_beta), float((err / bound).max())))
         assert np.all(err <= bound)
@@ -122,10 +122,10 @@ def test_gram_vs_restatement(nat, family, kind, n, d, dup):
         assert np.all(np.abs(K.diagonal() - dg) <= 3 * np.spacing(dg))
         assert np.all(K >= math.exp(log_beta) * (1 - 1e-15))  # beta everywhere, no padding zeros
         with pytest.raises(IndexError):
-            nat.gram(br.native_kind(family, kind), K, X, th[:-1], EPS)
+            nat.gram(_cov(family, kind).native_kind, K, X, th[:-1], EPS)
 
 
-@pytest.mark.parametrize('family,kind', br.FAMILY_KINDS)
+@pytest.mark.parametrize('family,kind', cr.FAMILY_KINDS)
 @pytest.mark.parametrize('m,n,d', [(70, 130, 5), (1, 129, 40)])
 def test_gram_cross_vs_restatement(nat, family, kind, m, n, d):
     """The same bound for k(Xs_i, X_j) + beta; no epsilon where a test point coincides with a
@@ -136,10 +136,10 @@ def test_gram_cross_vs_restatement(nat, family, kind, m, n, d):
     for log_beta in (-2.0, 1.5):
         th = np.r_[0.3, 0.5 * math.log(d) + rng.uniform(-0.3, 0.1, size=d if kind == 'ard' else 1),
                    log_beta]
-        Ks = nat.gram_cross(br.native_kind(family, kind), Xs, X, th)
+        Ks = nat.gram_cross(_cov(family, kind).native_kind, Xs, X, th)
         assert Ks.shape == (m, n)
-        ref = br.gram_cross(family, kind, Xs, X, th)
-        err, bound = np.abs(Ks - ref), br.gram_bound(family, kind, Xs, X, th, ref)
+        ref = _cov(family, kind).gram_cross(Xs, X, th)
+        err, bound = np.abs(Ks - ref), _cov(family, kind).gram_bound(Xs, X, th, ref)
         print('bias cross-gram {0}: max error / bound = {1:.3f}'.format(
             (family, kind, m, n, d, log_beta), float((err / bound).max())))
         assert np.all(err <= bound)
@@ -148,18 +148,6 @@ def test_gram_cross_vs_restatement(nat, family, kind, m, n, d):
 
 
 # ------------------------------------------------------------------ 2. theta-calls
-
-
-def _oracle_moves(X, y, ns, K, seed=1):
-    """|change| of the oracle's IS log-estimate under 1-ulp symmetric relative noise in K."""
-    def fixed(Kx):
-        def fn(Kw, X_, theta_):
-            Kw[...] = Kx
-        return fn
-    th = np.zeros(1)
-    v0, _, _ = orc.is_estimate(X, y, fixed(K), ns, th)
-    v1, _, _ = orc.is_estimate(X, y, fixed(br.symmetric_ulp_noise(K, seed)), ns, th)
-    return abs(v1 - v0)
 
 
 CALL_CASES = [('se', 130, 5, 'ard'), ('32', 200, 3, 'iso'), ('se', 65, 4, 'ard'),
@@ -174,7 +162,7 @@ def test_estimators_vs_oracle(nat, family, n, d, kind):
     oracle's own IS value moves by less than 5e-5 nats under 1-ulp noise in K."""
     c = _case('call', family, n, d, kind)
     X, y = c['X'], c['y']
-    kf = br.kernel_func(family, kind, EPS)
+    kf = _cov(family, kind).kernel_func(EPS)
     rng = np.random.RandomState(17)
     ns1, ns2 = rng.normal(size=(n, 8)), rng.normal(size=(n, 8))
     ctx = _ctx(nat, c, n_imp=8, max_batch=1, n_slots=2, n_ubufs=2)
@@ -182,8 +170,8 @@ def test_estimators_vs_oracle(nat, family, n, d, kind):
         ctx.u_upload(0, ns1)
         ctx.u_upload(1, ns2)
         for th in c['thetas'][[1, 3]]:
-            K = br.gram(family, kind, X, th, EPS)
-            moves = _oracle_moves(X, y, ns1, K)
+            K = _cov(family, kind).gram(X, th, EPS)
+            moves = cc.oracle_moves(X, y, ns1, K)
             assert moves < 5e-5, moves
             r1, rc, rops = orc.is_estimate(X, y, kf, ns1, th)
             r2, _, _ = orc.is_estimate(X, y, kf, ns2, None, rc)
@@ -227,9 +215,9 @@ def test_large_beta_without_inverse_panels(nat):
     assert th_big[0] == 0.3 and th_mid[-1] == 1.5
     assert 1.0 + math.exp(0.3) + math.exp(10.6) >= 2.0 ** 15
     ns = np.random.RandomState(23).normal(size=(n, 8))
-    moves = _oracle_moves(X, y, ns, br.gram('se', 'ard', X, th_big, EPS))
+    moves = cc.oracle_moves(X, y, ns, _cov('se', 'ard').gram(X, th_big, EPS))
     assert moves < 5e-5, moves
-    ref, _, rops = orc.is_estimate(X, y, br.kernel_func('se', 'ard', EPS), ns, th_big)
+    ref, _, rops = orc.is_estimate(X, y, _cov('se', 'ard').kernel_func(EPS), ns, th_big)
     ctx = _ctx(nat, c, n_imp=8, max_batch=2, n_slots=2, n_ubufs=2)
     try:
         ctx.u_upload(0, ns)
@@ -256,9 +244,9 @@ def test_huge_beta_takes_fp32_operands(nat):
     X, y, n = c['X'], c['y'], c['n']
     th = np.r_[c['thetas'][1][:-1], 19.5]
     ns = np.random.RandomState(23).normal(size=(n, 8))
-    K = br.gram('se', 'ard', X, th, EPS)
-    spread = max(_oracle_moves(X, y, ns, K, seed) for seed in range(1, 9))
-    ref, _, _ = orc.is_estimate(X, y, br.kernel_func('se', 'ard', EPS), ns, th)
+    K = _cov('se', 'ard').gram(X, th, EPS)
+    spread = max(cc.oracle_moves(X, y, ns, K, seed) for seed in range(1, 9))
+    ref, _, _ = orc.is_estimate(X, y, _cov('se', 'ard').kernel_func(EPS), ns, th)
     ctx = _ctx(nat, c, n_imp=8, max_batch=1, n_slots=1, n_ubufs=1)
     try:
         ctx.u_upload(0, ns)
@@ -277,14 +265,6 @@ def test_huge_beta_takes_fp32_operands(nat):
 PREDICT_CASES = [('se', 130, 5, 'ard'), ('se', 577, 4, 'ard')]
 
 
-def _worst(dev, ref):
-    worst = 0.0
-    for key, d in zip(('mean', 'var', 'prob'), dev):
-        scale = 1.0 if key == 'prob' else max(1.0, np.abs(ref[key]).max())
-        worst = max(worst, np.abs(d - ref[key]).max() / scale)
-    return worst
-
-
 def _far_row(c, th, ref, mean_far, prob_far):
     """The far test row is not the prior: k* = beta there, so the restatement's mean is
     beta sum(a) (the device's is within the parity tolerance of it), and the class probability is
@@ -301,7 +281,7 @@ def test_laplace_and_ep_predict_vs_restatement(nat, family, n, d, kind):
     absolute, at 1e-9, equal iteration / sweep counts; the far test row equals the restatement and
     is not the prior."""
     c = _case('call', family, n, d, kind)
-    Xs = _test_inputs(c, 70)
+    Xs = cc.far_test_inputs(c, 70, FAR)
     ctx = _ctx(nat, c)
     try:
         lp = ctx.predict(c['thetas'], Xs)
@@ -310,9 +290,9 @@ def test_laplace_and_ep_predict_vs_restatement(nat, family, n, d, kind):
         ctx.close()
     assert not lp[3].any() and not epd[3].any()
     for t, th in enumerate(c['thetas']):
-        ref = br.predictive(family, kind, c['X'], c['y'], Xs, th, EPS)
-        eref = br.ep_predictive(family, kind, c['X'], c['y'], Xs, th, EPS)
-        w_l, w_e = _worst([x[t] for x in lp[:3]], ref), _worst([x[t] for x in epd[:3]], eref)
+        ref = cr.predictive(_cov(family, kind), c['X'], c['y'], Xs, th, EPS)
+        eref = cr.ep_predictive(_cov(family, kind), c['X'], c['y'], Xs, th, EPS)
+        w_l, w_e = cc.worst([x[t] for x in lp[:3]], ref), cc.worst([x[t] for x in epd[:3]], eref)
         print('bias predict {0} theta {1}: Laplace {2:.2e} EP {3:.2e} (tol {4:.0e}), far prob '
               '{5:.4f}'.format((family, n, d, kind), (th[0], th[-1]), w_l, w_e, TOL, lp[2][t, -1]))
         assert int(lp[4][t]) == ref['n_iter'] and int(epd[4][t]) == eref['n_sweeps']
@@ -332,11 +312,11 @@ def test_is_predict_vs_restatement(nat, family, n, d, kind, proposal, monkeypatc
     discrepancy, floored at 1e-12, the discrepancy capped at 1e-6; prob, mean, var and ess of the
     default path at 1e-3. The far test row's mean is beta sum(a)-sized, not 0."""
     c = _case('call', family, n, d, kind)
-    Xs = _test_inputs(c, 70)
+    Xs = cc.far_test_inputs(c, 70, FAR)
     th = c['thetas'][1]
-    K = br.gram(family, kind, c['X'], th, EPS)
-    Ks = br.gram_cross(family, kind, Xs, c['X'], th)
-    kss = br.prior_var(kind, th, d)
+    K = _cov(family, kind).gram(c['X'], th, EPS)
+    Ks = _cov(family, kind).gram_cross(Xs, c['X'], th)
+    kss = _cov(family, kind).prior_var(Xs, th)
     U = np.random.RandomState(107).normal(size=(n, 64)).astype(np.float32).astype(np.float64)
     fit = eis.state(K, c['y']) if proposal == 'ep' else eis.laplace_state(K, c['y'])
     ref = ipr.predictive(K, Ks, kss, c['y'], U, fit, 'probit')
@@ -381,8 +361,8 @@ def test_is_predict_vs_restatement(nat, family, n, d, kind, proposal, monkeypatc
 # ------------------------------------------------------------------ 5. gradients
 
 
-GRAD_CASES = [(f, 1, 1, 'ard') for f in br.FAMILIES] + [(f, 64, 33, 'ard') for f in br.FAMILIES] + \
-             [(f, 130, 5, 'ard') for f in br.FAMILIES] + [(f, 200, 3, 'iso') for f in br.FAMILIES] + \
+GRAD_CASES = [(f, 1, 1, 'ard') for f in cr.FAMILIES] + [(f, 64, 33, 'ard') for f in cr.FAMILIES] + \
+             [(f, 130, 5, 'ard') for f in cr.FAMILIES] + [(f, 200, 3, 'iso') for f in cr.FAMILIES] + \
              [('se', 600, 4, 'ard'), ('52', 600, 4, 'ard')]
 
 
@@ -394,7 +374,7 @@ def test_laplace_grad_vs_restatement_and_central_differences(nat, family, n, d, 
     (n = 600: the first theta);
     lml bitwise the Laplace theta-call's at the same Newton settings."""
     c = _case('grad', family, n, d, kind)
-    refs = [br.laplace_grad(family, kind, c['X'], c['y'], th, EPS, tol=NEWTON_TOL)
+    refs = [cr.laplace_grad(_cov(family, kind), c['X'], c['y'], th, EPS, tol=NEWTON_TOL)
             for th in c['thetas']]
     for ref in refs:
         assert ref['diffs'][-1] <= NEWTON_TOL / 100.0
@@ -416,7 +396,7 @@ def test_laplace_grad_vs_restatement_and_central_differences(nat, family, n, d, 
         worst = max(worst, err)
         if t < (1 if n >= 600 else 2):
             fd = gr.central_differences(
-                lambda x: br.lml(family, kind, c['X'], c['y'], x, EPS, tol=1e-24), th)
+                lambda x: cr.lml(_cov(family, kind), c['X'], c['y'], x, EPS, tol=1e-24), th)
             worst_fd = max(worst_fd, np.abs(grad[t] - fd).max() / max(1.0, np.abs(fd).max()))
         assert grad[t, -1] != 0.0
     print('bias grad parity {0}: worst {1:.3e} (tol {2:.0e}), vs fd {3:.3e} (tol 1e-06)'
@@ -436,7 +416,7 @@ def test_ep_grad_vs_restatement_and_central_differences(nat, family, n, d, kind)
     central differences (h = 1e-5) of log Z_EP fitted to diff_tol = 1e-16 at 1e-6, for one theta
     of each beta (n = 600: the first theta) with the device fitted as tightly."""
     c = _case('epgrad', family, n, d, kind)
-    refs = [br.ep_grad(family, kind, c['X'], c['y'], th, EPS) for th in c['thetas']]
+    refs = [cr.ep_grad(_cov(family, kind), c['X'], c['y'], th, EPS) for th in c['thetas']]
     for ref in refs:
         m = ref['fit']['m_hist']
         assert m[-1] < 0.99e-8 and (len(m) < 2 or m[-2] > 1.01e-8)
@@ -456,7 +436,7 @@ def test_ep_grad_vs_restatement_and_central_differences(nat, family, n, d, kind)
         worst = max(worst, err)
         if t < (1 if n >= 600 else 2):
             fd = gr.central_differences(
-                lambda x: br.ep_logz(family, kind, c['X'], c['y'], x, EPS, diff_tol=1e-16,
+                lambda x: cr.ep_logz(_cov(family, kind), c['X'], c['y'], x, EPS, diff_tol=1e-16,
                                      max_sweeps=1000), th)
             worst_fd = max(worst_fd, np.abs(tight[t] - fd).max() / max(1.0, np.abs(fd).max()))
     print('bias EP grad parity {0}: worst {1:.3e} (tol {2:.0e}), vs fd {3:.3e} (tol 1e-06)'
@@ -468,7 +448,7 @@ def test_ep_grad_vs_restatement_and_central_differences(nat, family, n, d, kind)
 # ------------------------------------------------------------------ 6. beta = 0
 
 
-@pytest.mark.parametrize('family,kind', br.FAMILY_KINDS)
+@pytest.mark.parametrize('family,kind', cr.FAMILY_KINDS)
 def test_beta_zero_is_the_base_kind(nat, family, kind):
     """theta_b = -800 (exp gives exactly 0): Gram, cross-Gram, the IS / PriorMC / Laplace
     theta-calls, the cached u-call and apm_predict are bitwise the base kind's on the same data;
@@ -478,10 +458,10 @@ def test_beta_zero_is_the_base_kind(nat, family, kind):
     c = _case('call', 'se', 130, 5, 'ard') if kind == 'ard' else _case('call', '32', 200, 3, 'iso')
     c = dict(c, family=family)
     X, y = c['X'], c['y']
-    Xs = _test_inputs(c, 70)
+    Xs = cc.far_test_inputs(c, 70, FAR)
     th0 = c['thetas'][1][:-1]
     thb = np.r_[th0, -800.0]
-    nk, nk0 = br.native_kind(family, kind), br.native_kind(family, kind, bias=False)
+    nk, nk0 = _cov(family, kind).native_kind, _cov(family, kind, False).native_kind
     K, K0 = np.empty((n, n)), np.empty((n, n))
     nat.gram(nk, K, X, thb, EPS)
     nat.gram(nk0, K0, X, th0, EPS)
@@ -520,7 +500,7 @@ def test_batches_are_bitwise_neutral(nat):
     """A biased Matern 5/2 ARD context (130, 5), max_batch = 4: a chain's IS theta-call, gradient
     and predictive outputs are bitwise the same alone, first of 3 and last of 4."""
     c = _case('grad', '52', 130, 5, 'ard')
-    Xs = _test_inputs(c, 70)
+    Xs = cc.far_test_inputs(c, 70, FAR)
     n = c['n']
     rng = np.random.RandomState(5)
     other = c['thetas'][rng.randint(0, 4, size=3)] + rng.uniform(-0.2, 0.2, size=(3, 7))
@@ -556,7 +536,7 @@ def test_base_kind_context_is_unchanged_by_a_biased_one(nat):
     slot read-back are bitwise the same before and after a biased context on the same data is
     created and used in the same process."""
     c = _case('call', 'se', 130, 5, 'ard')
-    Xs = _test_inputs(c, 70)
+    Xs = cc.far_test_inputs(c, 70, FAR)
     n = c['n']
     th0 = c['thetas'][:, :-1]
     U = np.random.RandomState(31).normal(size=(n, 8))
@@ -595,7 +575,7 @@ def test_batched_ess_mh_with_bias(nat, tmp_path):
     from auxpm.batched import BatchedAPMEllSSPlusMHSampler as S
     c = _case('call', 'se', 130, 5, 'ard')
     X, y, d = c['X'], c['y'], c['d']
-    Xs = _test_inputs(c, 70)
+    Xs = cc.far_test_inputs(c, 70, FAR)
     prior = dict(a_tau=1., b_tau=1. / d ** 0.5, a_sigma=1.1, b_sigma=0.1)
     th0 = np.tile(np.r_[0.0, np.full(d, np.log(2.)), 0.5], (4, 1))
 

@@ -9,7 +9,7 @@ import pytest
 
 import apm_oracle as orc
 import ep_restatement as ep
-import matern_restatement as mr
+from cov_restatement import Cov
 from test_gpu_predict import I_EQ, SHAPES, _make_case
 
 pytestmark = pytest.mark.gpu
@@ -118,7 +118,7 @@ def test_panel_edges(nat, n):
 def test_panel_edge_matern52(nat):
     c = _make_case(513, 4, 3, 'ard', 300 + 513)
     th = c['thetas'][0]
-    fit = ep.ep_fit(mr.gram('52', 'ard', c['X'], th, EPS), c['y'])
+    fit = ep.ep_fit(Cov('52', 'ard').gram(c['X'], th, EPS), c['y'])
     assert_stop_margin(fit)
     ctx = nat.Context(c['X'], c['y'], nat.KERNEL_M52_ARD, EPS, 1, max_batch=1, n_slots=1,
                       n_ubufs=1)

@@ -8,7 +8,8 @@ import math
 import numpy as np
 import pytest
 
-import ep_grad_restatement as eg
+import cov_restatement as cr
+from cov_restatement import Cov
 from test_gpu_ep import EDGE_N, assert_stop_margin
 from test_gpu_predict import SHAPES, _make_case
 
@@ -41,7 +42,7 @@ def cases():
     out = []
     for i, (n, d, m, kind) in enumerate(SHAPES):
         c = _make_case(n, d, m, kind, 100 + i)
-        c['ref'] = [eg.ep_grad(kind, c['X'], c['y'], th, EPS) for th in c['thetas']]
+        c['ref'] = [cr.ep_grad(Cov('se', kind), c['X'], c['y'], th, EPS) for th in c['thetas']]
         out.append(c)
     return out
 
@@ -95,7 +96,7 @@ def test_panel_edges(nat, n):
     """d = 4, ARD, theta_0 = 0.3 at the tile and outer-panel boundaries (nb = 2, 8, 9, 10)."""
     c = _make_case(n, 4, 3, 'ard', 300 + n)
     th = c['thetas'][0]
-    ref = eg.ep_grad('ard', c['X'], c['y'], th, EPS)
+    ref = cr.ep_grad(Cov('se', 'ard'), c['X'], c['y'], th, EPS)
     err = _parity(_device(nat, c, th), 0, ref)
     print('EP grad parity N = {0}: {1:.3e}'.format(n, err))
     assert err <= TOL
@@ -104,11 +105,11 @@ def test_panel_edges(nat, n):
 @pytest.mark.parametrize('family,kind,n,d,seed', [('52', 'ard', 513, 4, 300 + 513),
                                                   ('32', 'iso', 130, 3, 501)])
 def test_matern(nat, family, kind, n, d, seed):
-    """The Matern families on matern_restatement's own Gram (the C oracle builds SE only): the
+    """The Matern families on cov_restatement's own Gram (the C oracle builds SE only): the
     two-pass instantiation of the contraction kernel, ARD at a panel edge and iso."""
     c = _make_case(n, d, 3, kind, seed)
     th = c['thetas'][0]
-    ref = eg.ep_grad(kind, c['X'], c['y'], th, EPS, family=family)
+    ref = cr.ep_grad(Cov(family, kind), c['X'], c['y'], th, EPS)
     err = _parity(_device(nat, c, th, family), 0, ref)
     print('EP grad parity Matern {0} {1} N = {2}: {3:.3e}'.format(family, kind, n, err))
     assert err <= TOL
@@ -180,7 +181,7 @@ def test_failures_and_refusals(nat, cases, device):
     P = c['thetas'].shape[1]
     easy = c['thetas'][0].copy()
     easy[0] = -16.0  # mu ~ n e^-16: the second sweep already moves it by less than the tolerance
-    assert ep.ep_fit(eg.gram('ard', c['X'], easy, EPS), c['y'])['n_sweeps'] == 2
+    assert ep.ep_fit(Cov('se', 'ard').gram(c['X'], easy, EPS), c['y'])['n_sweeps'] == 2
     thetas = np.array([easy, c['thetas'][0]])
     ctx = _context(nat, c, max_batch=2)
     alone = ctx.ep_grad(easy)
@@ -234,8 +235,8 @@ def test_epsilon_rule(nat, cases):
     thetas = c['thetas'][[0, 2]]
     dev = _device(nat, c, thetas, eps=1e-2)
     for t, th in enumerate(thetas):
-        ref = eg.ep_grad('ard', c['X'], c['y'], th, 1e-2)
-        wrong = eg.ep_grad('ard', c['X'], c['y'], th, 1e-2, eps_in_dk0=True)
+        ref = cr.ep_grad(Cov('se', 'ard'), c['X'], c['y'], th, 1e-2)
+        wrong = cr.ep_grad(Cov('se', 'ard'), c['X'], c['y'], th, 1e-2, wrong='eps_in_dk0')
         err = _parity(dev, t, ref)
         off = np.abs(dev[1][t] - wrong['grad']).max() / max(1.0, np.abs(ref['grad']).max())
         print('epsilon rule theta_0 {0}: parity {1:.3e}, wrong reading off by {2:.3e}'

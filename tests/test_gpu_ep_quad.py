@@ -16,6 +16,7 @@ import ep_restatement as ep
 import grad_restatement as gr
 import logit_restatement as lr
 import apm_oracle as orc
+from cov_restatement import Cov
 from test_gpu_ep import KEYS, assert_stop_margin, kind_code, oracle_K, parity
 from test_gpu_predict import I_EQ, SHAPES, _make_case
 
@@ -179,12 +180,9 @@ def test_ep_predict_under_the_logit(nat, cases):
 
 
 def _restated_grad(c, th, K, **settings):
-    """R&W 5.27 on the restatement's logit fit (ep_grad_restatement.ep_grad's lines)."""
-    import scipy.linalg as la
+    """R&W 5.27 on the restatement's logit fit (ep_grad_restatement's contraction)."""
     fit = eq.ep_fit(K, c['y'], eq.LOGIT, **settings)
-    Z = la.solve_triangular(fit['L'], np.diag(fit['s']), lower=True)
-    M = 0.5 * np.outer(fit['a'], fit['a']) - 0.5 * Z.T.dot(Z)
-    fit['grad'] = np.array([float((M * D).sum()) for D in eg.dK(c['kind'], c['X'], th, K, EPS)])
+    fit['grad'] = eg.grad_of_fit(fit, Cov('se', c['kind']).dK(c['X'], th, EPS, K=K))
     return fit
 
 

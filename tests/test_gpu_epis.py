@@ -10,7 +10,7 @@ import pytest
 
 import ep_restatement as ep
 import epis_restatement as eis
-import matern_restatement as mr
+from cov_restatement import Cov
 from test_gpu_ep import _other_paths, assert_stop_margin, kind_code, oracle_K
 from test_gpu_predict import SHAPES, _make_case
 
@@ -119,7 +119,7 @@ def test_panel_edges(nat, n):
 
 def test_panel_edge_matern52(nat):
     c = _make_case(513, 4, 3, 'ard', 300 + 513)
-    _with_refs(c, [mr.gram('52', 'ard', c['X'], c['thetas'][0], EPS)], 300 + 513)
+    _with_refs(c, [Cov('52', 'ard').gram(c['X'], c['thetas'][0], EPS)], 300 + 513)
     r = _calls(nat, c, nat.KERNEL_M52_ARD, c['thetas'][:1])
     _assert_parity(c, r, [0], 'Matern 5/2 N = 513')
 

@@ -9,7 +9,9 @@ import numpy as np
 import pytest
 
 import apm_oracle as orc
+import cov_restatement as cr
 import grad_restatement as gr
+from cov_restatement import Cov
 
 pytestmark = pytest.mark.gpu
 
@@ -37,7 +39,7 @@ def cases():
     out = []
     for n, d, kind, seed in SHAPES:
         c = gr.make_case(n, d, kind, seed)
-        c['ref'] = [gr.laplace_grad(kind, c['X'], c['y'], th, EPS, tol=NEWTON_TOL)
+        c['ref'] = [cr.laplace_grad(Cov('se', kind), c['X'], c['y'], th, EPS, tol=NEWTON_TOL)
                     for th in c['thetas']]
         out.append(c)
     return out
@@ -114,7 +116,7 @@ def test_grad_vs_central_differences_of_the_oracle(cases, device, ci):
     c = cases[ci]
 
     def lml(th):
-        K = gr.gram(c['kind'], c['X'], th, EPS)
+        K = Cov('se', c['kind']).gram(c['X'], th, EPS)
         return orc.laplace_approximation(K, c['y'], calc_cov=False, calc_lml=True,
                                          diff_f_tol=1e-24)[1]
     for t, th in enumerate(c['thetas']):
@@ -166,9 +168,9 @@ def test_epsilon_rule(cases, ci):
     nit = p.n_iter.copy()
     p.close()
     for t, th in enumerate(c['thetas']):
-        ref = gr.laplace_grad(c['kind'], c['X'], c['y'], th, 1e-2, tol=NEWTON_TOL)
-        wrong = gr.laplace_grad(c['kind'], c['X'], c['y'], th, 1e-2, tol=NEWTON_TOL,
-                                eps_in_dk0=True)
+        ref = cr.laplace_grad(Cov('se', c['kind']), c['X'], c['y'], th, 1e-2, tol=NEWTON_TOL)
+        wrong = cr.laplace_grad(Cov('se', c['kind']), c['X'], c['y'], th, 1e-2, tol=NEWTON_TOL,
+                                wrong='eps_in_dk0')
         assert int(nit[t]) == ref['n_iter']
         err = _parity(lml[t], grad[t], ref)
         off = np.abs(grad[t] - wrong['grad']).max() / max(1.0, np.abs(ref['grad']).max())

@@ -11,7 +11,7 @@ import pytest
 import epis_restatement as eis
 import is_predict_restatement as ipr
 import logit_restatement as lr
-import matern_restatement as mr
+from cov_restatement import Cov
 from test_gpu_ep import _other_paths, kind_code
 from test_gpu_predict import _make_case
 
@@ -52,8 +52,8 @@ def _grams(c, family, th):
     import apm_oracle as orc
     n, m = c['n'], c['m']
     if family:
-        return (mr.gram(family, c['kind'], c['X'], th, EPS),
-                mr.gram_cross(family, c['kind'], c['Xs'], c['X'], th))
+        return (Cov(family, c['kind']).gram(c['X'], th, EPS),
+                Cov(family, c['kind']).gram_cross(c['Xs'], c['X'], th))
     G = np.empty((n + m, n + m))
     orc.c_gram(c['kind'], G, np.concatenate([c['X'], c['Xs']]), th, EPS)
     return G[:n, :n].copy(), G[n:, :n].copy()

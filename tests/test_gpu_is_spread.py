@@ -11,6 +11,7 @@ import pytest
 import epis_restatement as eis
 import grad_restatement as gr
 import is_spread_restatement as sr
+from cov_restatement import Cov
 
 pytestmark = pytest.mark.gpu
 
@@ -35,7 +36,7 @@ def nat(gpu_available):
 
 
 def _case(n, d):
-    return gr.make_case(n, d, 'ard', 9000 + n, sigmas=SIGMAS)
+    return gr.make_case(n, d, 'ard', 9000 + n, rows=SIGMAS)
 
 
 def _context(nat, c, S, likelihood='probit', max_batch=2, n_slots=2, n_ubufs=4):
@@ -110,7 +111,7 @@ def test_sub_blocks_vs_restatement(nat, S, B, proposal):
     assert logf.shape == (2, 2, nblk) and not st.any()
     worst = [0.0, 0.0, 0.0]
     for t in range(2):
-        ref_st = _state(proposal, gr.gram('ard', c['X'], c['thetas'][t], EPS), c['y'])
+        ref_st = _state(proposal, Cov('se', 'ard').gram(c['X'], c['thetas'][t], EPS), c['y'])
         for r in range(2):
             lw = sr.log_weights(c['y'], ref_st, U[r][t])
             rl, re, rw = sr.blocks(lw, B)

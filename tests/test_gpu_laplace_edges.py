@@ -3,7 +3,7 @@ solve-only form (host_chol64.cpp chol_solve_rows, row_start = nb), which predict
 and augmented() run the work matrix through: N = 65, 128, 512, 513, 1024, 1025, 1089 (nb = 2, 2,
 8, 9, 16, 17, 18; tests/edge_cases.py says what each size reaches), test-row counts mb = 1, 2, 3,
 nb and a second block of one row, against the numpy/scipy restatements (grad_restatement,
-matern_restatement, predict_restatement) and the oracle's laplace_approximation. Then the order
+cov_restatement, predict_restatement) and the oracle's laplace_approximation. Then the order
 of calls on one context (predict and gradient write the bottom rows of the work matrix the IS
 theta-call also uses) and the reuse of apm_laplace's cached context.
 
@@ -18,9 +18,10 @@ import pytest
 
 import apm_oracle as orc
 import edge_cases as ec
+import cov_restatement as cr
 import grad_restatement as gr
-import matern_restatement as mr
 import predict_restatement as pr
+from cov_restatement import Cov
 
 pytestmark = pytest.mark.gpu
 
@@ -58,12 +59,8 @@ def _grad_ref(family, kind, n):
     key = (family, kind, n)
     if key not in _GRAD_REF:
         c = ec.case(n, family, kind)
-        if family is None:
-            _GRAD_REF[key] = [gr.laplace_grad(kind, c['X'], c['y'], th, EPS, tol=ec.GRAD_TOL)
-                              for th in c['thetas']]
-        else:
-            _GRAD_REF[key] = [mr.laplace_grad(family, kind, c['X'], c['y'], th, EPS,
-                                              tol=ec.GRAD_TOL) for th in c['thetas']]
+        _GRAD_REF[key] = [cr.laplace_grad(ec.cov(c), c['X'], c['y'], th, EPS, tol=ec.GRAD_TOL)
+                          for th in c['thetas']]
     return _GRAD_REF[key]
 
 
@@ -213,8 +210,8 @@ def test_laplace_cached_context_reuse(nat):
     at max_iters = 1 with STATUS_MAXITER."""
     n = 131
     p1, p2 = (gr.make_case(n, ec.D, 'ard', seed) for seed in (1311, 1312))
-    K1 = gr.gram('ard', p1['X'], p1['thetas'][0], EPS)
-    K2 = gr.gram('ard', p2['X'], p2['thetas'][1], EPS)
+    K1 = Cov('se', 'ard').gram(p1['X'], p1['thetas'][0], EPS)
+    K2 = Cov('se', 'ard').gram(p2['X'], p2['thetas'][1], EPS)
     y1, y2 = p1['y'], p2['y']
     assert not np.array_equal(y1, y2)
     first = nat.laplace(K1, y1, True, True, ec.FIT_TOL, 1000)

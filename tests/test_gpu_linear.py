@@ -2,7 +2,7 @@
 cross-Gram, the four estimators' theta-calls, the three predictives with their per-row prior
 variance, the leave-one-out densities, the Laplace and EP gradients, lambda = 0 against the kind
 without the flag, batch neutrality, two other contexts beside a linear one, the range flags at a
-large lambda and the Python layer - against tests/linear_restatement.py and the oracle's
+large lambda and the Python layer - against tests/cov_restatement.py and the oracle's
 estimators run with its kernel_func. The maxima measured on an MI355X are in DESIGN.md §25's
 parity table."""
 import math
@@ -11,13 +11,14 @@ import numpy as np
 import pytest
 
 import apm_oracle as orc
-import bias_restatement as br
+import cov_checks as cc
+import cov_restatement as cr
 import ep_restatement as ep
 import epis_restatement as eis
 import grad_restatement as gr
 import is_loo_restatement as ilr
 import is_predict_restatement as ipr
-import linear_restatement as lr
+from cov_restatement import Cov
 
 pytestmark = pytest.mark.gpu
 
@@ -29,8 +30,10 @@ PROB_TOL = 1e-3     # the IS predictive's averages
 FLOOR, CAP = 1e-12, 1e-6  # §19's yardstick rule for its fp64 quantities
 W_TOL = 1e-3        # test_gpu_is_loo's bound on loo, lpd and log ess_loo (plus 10 Y)
 G_FLOOR, G_REL = 1e-9, 2.4e-7  # and on gauss
-# linear_restatement.make_case's thetas are (theta_0, log lambda) = (0.3, -2), (0.3, 1), (3, 1),
-# (-1, -2), with log beta = 1.5 where biased.
+# the thetas are (theta_0, log lambda) = (0.3, -2), (0.3, 1), (3, 1), (-1, -2), with
+# log beta = 1.5 where biased.
+PAIRS = ((0.3, -2.0), (0.3, 1.0), (3.0, 1.0), (-1.0, -2.0))
+FAR = 50.0  # the far test row: the SE part of k* underflows to exactly 0
 # (purpose, n, d, kind, bias) -> data seed, the first one from 1300 on whose labels are 30-70 %
 # positive and for which, at all four thetas, the restatement cannot disagree with the device on
 # an iteration or sweep count (DESIGN.md §16's margins, asserted again before each comparison):
@@ -60,22 +63,17 @@ def _case(what, n, d, kind, bias):
     """Data of one (purpose, shape, kind), drawn once and left unchanged."""
     key = (what, n, d, kind, bias)
     if key not in _CASES:
-        _CASES[key] = lr.make_case(n, d, kind, bias, SEEDS[key])
+        _CASES[key] = _make_case(n, d, kind, bias, SEEDS[key])
     return _CASES[key]
 
 
-def _newton_margins(K, y, tol, n=2):
-    """The restatement's Newton loop cannot stop one iteration away from the device's."""
-    df = gr.newton(K, y, tol)['diffs']
-    if tol == NEWTON_TOL:
-        assert df[-1] <= tol / 100.0 and df[-2] >= (1.5 if n == 1 else 100.0) * tol, df[-2:]
-    else:
-        assert df[-1] <= tol / 3.0 and (len(df) < 2 or df[-2] >= 3.0 * tol), df[-2:]
+def _make_case(n, d, kind, bias, seed):
+    rows = [(s0, 1.5, ll) if bias else (s0, ll) for s0, ll in PAIRS]
+    return dict(gr.make_case(n, d, kind, seed, rows=rows), bias=bias)
 
 
-def _ep_margins(fit):
-    m = fit['m_hist']
-    assert m[-1] < 0.99e-8 and (len(m) < 2 or m[-2] > 1.01e-8), m[-2:]
+def _cov(kind, bias, linear=True):
+    return Cov('se', kind, bias=bias, linear=linear)
 
 
 @pytest.fixture(scope='module')
@@ -86,82 +84,62 @@ def nat(gpu_available):
 
 
 def _ctx(nat, c, n_imp=1, max_batch=4, n_slots=4, n_ubufs=4, linear=True, kind=None):
-    nk = lr.native_kind(c['kind'], c['bias'], linear) if kind is None else kind
+    nk = _cov(c['kind'], c['bias'], linear).native_kind if kind is None else kind
     return nat.Context(c['X'], c['y'], nk, EPS, n_imp, max_batch=max_batch, n_slots=n_slots,
                        n_ubufs=n_ubufs)
-
-
-def _test_inputs(c, m):
-    rng = np.random.RandomState(1000 + c['n'])
-    Xs = rng.normal(size=(m, c['d']))
-    Xs[0] = c['X'][7 % c['n']]          # coincides with a training point
-    Xs[-1] = c['X'][3 % c['n']] + 50.0  # so far away that S* underflows to exactly 0
-    return Xs
 
 
 # ------------------------------------------------------------------ 1. Gram and cross-Gram
 
 
-GRAM_CASES = ([(k, b, n, d) for k, b in lr.KINDS for n, d in ((1, 1), (129, 64))] +
+GRAM_CASES = ([(k, b, n, d) for k, b in cr.LINEAR_KINDS for n, d in ((1, 1), (129, 64))] +
               [('ard', True, 300, 7)])
 
 
 @pytest.mark.parametrize('kind,bias,n,d', GRAM_CASES)
 def test_gram_vs_restatement(nat, kind, bias, n, d):
-    """Entry by entry within lr.gram_bound (the base kind's bound on S plus 3u |K_ref| plus the
+    """Entry by entry within Cov.gram_bound (the base kind's bound on S plus 3u |K_ref| plus the
     fma chain's (d + 2) u lambda sum_k |x_ik x_jk|) at the four (theta_0, log lambda); K exactly
     symmetric, every entry of the caller's (n, n) array written. (129, 64) takes two LDS chunks
     of features in both sweeps. Measured on an MI355X: at most 0.74 of the bound."""
     import gpdemo.kernels as krn
-    c = lr.make_case(n, d, kind, bias, 5 + n)
+    c = _make_case(n, d, kind, bias, 5 + n)
     X = c['X']
     for th in c['thetas']:
         K = np.full((n, n), np.nan)
         krn.make_kernel_func(kind, EPS, bias=bias, linear=True)(K, X, th)
-        Kref = lr.gram(kind, bias, X, th, EPS)
-        err, bound = np.abs(K - Kref), lr.gram_bound(kind, bias, X, X, th, Kref)
+        Kref = _cov(kind, bias).gram(X, th, EPS)
+        err, bound = np.abs(K - Kref), _cov(kind, bias).gram_bound(X, X, th, Kref)
         print('linear gram {0}: max error / bound = {1:.3f}'.format(
             (kind, bias, n, d, th[0], th[-1]), float((err / bound).max())))
         assert np.all(err <= bound)
         assert np.array_equal(K, K.T)
         with pytest.raises(IndexError):
-            nat.gram(lr.native_kind(kind, bias), K, X, th[:-1], EPS)
+            nat.gram(_cov(kind, bias).native_kind, K, X, th[:-1], EPS)
 
 
-@pytest.mark.parametrize('kind,bias', lr.KINDS)
+@pytest.mark.parametrize('kind,bias', cr.LINEAR_KINDS)
 @pytest.mark.parametrize('m,n,d', [(70, 130, 5), (1, 129, 40)])
 def test_gram_cross_vs_restatement(nat, kind, bias, m, n, d):
     """The same bound for k(Xs_i, X_j); no epsilon where a test point coincides with a training
     point. Measured on an MI355X: at most 0.90 of the bound."""
-    c = lr.make_case(n, d, kind, bias, m + n)
+    c = _make_case(n, d, kind, bias, m + n)
     X = c['X']
     Xs = np.random.RandomState(m + n + 1).normal(size=(m, d))
     Xs[0] = X[7]
     for th in c['thetas']:
-        Ks = nat.gram_cross(lr.native_kind(kind, bias), Xs, X, th)
+        Ks = nat.gram_cross(_cov(kind, bias).native_kind, Xs, X, th)
         assert Ks.shape == (m, n)
-        ref = lr.gram_cross(kind, bias, Xs, X, th)
-        err, bound = np.abs(Ks - ref), lr.gram_bound(kind, bias, Xs, X, th, ref)
+        ref = _cov(kind, bias).gram_cross(Xs, X, th)
+        err, bound = np.abs(Ks - ref), _cov(kind, bias).gram_bound(Xs, X, th, ref)
         print('linear cross-gram {0}: max error / bound = {1:.3f}'.format(
             (kind, bias, m, n, d, th[0], th[-1]), float((err / bound).max())))
         assert np.all(err <= bound)
-        kss = lr.prior_var(kind, bias, Xs[:1], th)[0]
+        kss = _cov(kind, bias).prior_var(Xs[:1], th)[0]
         assert abs(Ks[0, 7] - kss) <= bound[0, 7]
 
 
 # ------------------------------------------------------------------ 2. theta-calls
-
-
-def _oracle_moves(X, y, ns, K, seed=1):
-    """|change| of the oracle's IS log-estimate under 1-ulp symmetric relative noise in K."""
-    def fixed(Kx):
-        def fn(Kw, X_, theta_):
-            Kw[...] = Kx
-        return fn
-    th = np.zeros(1)
-    v0, _, _ = orc.is_estimate(X, y, fixed(K), ns, th)
-    v1, _, _ = orc.is_estimate(X, y, fixed(lr.symmetric_ulp_noise(K, seed)), ns, th)
-    return abs(v1 - v0)
 
 
 CALL_CASES = [(130, 5, 'ard', False), (200, 3, 'iso', True), (65, 4, 'ard', True),
@@ -177,7 +155,7 @@ def test_estimators_vs_oracle(nat, n, d, kind, bias):
     than 5e-5 nats under 1-ulp noise in K."""
     c = _case('call', n, d, kind, bias)
     X, y = c['X'], c['y']
-    kf = lr.kernel_func(kind, bias, EPS)
+    kf = _cov(kind, bias).kernel_func(EPS)
     rng = np.random.RandomState(17)
     ns1, ns2 = rng.normal(size=(n, 8)), rng.normal(size=(n, 8))
     ctx = _ctx(nat, c, n_imp=8, max_batch=1, n_slots=2, n_ubufs=2)
@@ -185,16 +163,16 @@ def test_estimators_vs_oracle(nat, n, d, kind, bias):
         ctx.u_upload(0, ns1)
         ctx.u_upload(1, ns2)
         for th in c['thetas'][[1, 3]]:
-            K = lr.gram(kind, bias, X, th, EPS)
-            _newton_margins(K, y, 1e-4)
-            moves = _oracle_moves(X, y, ns1, K)
+            K = _cov(kind, bias).gram(X, th, EPS)
+            cc.newton_margins(K, y, 1e-4, NEWTON_TOL)
+            moves = cc.oracle_moves(X, y, ns1, K)
             assert moves < 5e-5, moves
             r1, rc, rops = orc.is_estimate(X, y, kf, ns1, th)
             r2, _, _ = orc.is_estimate(X, y, kf, ns2, None, rc)
             p1, _, pops = orc.priormc_estimate(X, y, kf, ns1, th)
             lml, lops = orc.laplace_estimate(X, y, kf, th)
             est = eis.state(K, y)
-            _ep_margins(est)
+            cc.ep_margins(est)
             e1 = eis.is_consistent(y, est, ns1)
             out, st, nops = ctx.theta_eval(nat.EST_IS, th[None], [0], [0])
             out2, st2 = ctx.u_eval([0], [1])
@@ -223,18 +201,11 @@ def test_estimators_vs_oracle(nat, n, d, kind, bias):
 PREDICT_CASES = [(130, 5, 'ard', True), (577, 4, 'ard', True)]
 
 
-def _worst(dev, ref):
-    worst = 0.0
-    for key, d in zip(('mean', 'var', 'prob'), dev):
-        scale = 1.0 if key == 'prob' else max(1.0, np.abs(ref[key]).max())
-        worst = max(worst, np.abs(d - ref[key]).max() / scale)
-    return worst
-
-
 def _far_mean(c, th, Xs, a):
     """beta sum(a) + lambda x* . X^T a at the far test row (S* = 0 exactly there)."""
-    _, beta, lam = lr.split(c['kind'], c['bias'], th, c['d'])
-    assert np.all(br.base_cross('se', c['kind'], Xs[-1:], c['X'], th[:c['d'] + 1]) == 0.0)
+    cov = _cov(c['kind'], c['bias'])
+    _, beta, lam = cov.split(th, c['d'])
+    assert np.all(cov.base_cross(Xs[-1:], c['X'], th[:c['d'] + 1]) == 0.0)
     return beta * a.sum() + lam * Xs[-1].dot(c['X'].T.dot(a))
 
 
@@ -245,7 +216,7 @@ def test_laplace_and_ep_predict_vs_restatement(nat, n, d, kind, bias):
     test row the mean is beta sum(a) + lambda x* . X^T a and the variance starts from
     k** = s + beta + lambda |x*|^2, both at the 1e-9 yardstick."""
     c = _case('call', n, d, kind, bias)
-    Xs = _test_inputs(c, 70)
+    Xs = cc.far_test_inputs(c, 70, FAR)
     ctx = _ctx(nat, c)
     try:
         lp = ctx.predict(c['thetas'], Xs)
@@ -254,14 +225,14 @@ def test_laplace_and_ep_predict_vs_restatement(nat, n, d, kind, bias):
         ctx.close()
     assert not lp[3].any() and not epd[3].any()
     for t, th in enumerate(c['thetas']):
-        K = lr.gram(kind, bias, c['X'], th, EPS)
-        _newton_margins(K, c['y'], 1e-4)
-        ref = lr.predictive(kind, bias, c['X'], c['y'], Xs, th, EPS)
-        eref = lr.ep_predictive(kind, bias, c['X'], c['y'], Xs, th, EPS)
-        _ep_margins(ep.ep_fit(K, c['y']))
-        w_l, w_e = _worst([x[t] for x in lp[:3]], ref), _worst([x[t] for x in epd[:3]], eref)
+        K = _cov(kind, bias).gram(c['X'], th, EPS)
+        cc.newton_margins(K, c['y'], 1e-4, NEWTON_TOL)
+        ref = cr.predictive(_cov(kind, bias), c['X'], c['y'], Xs, th, EPS)
+        eref = cr.ep_predictive(_cov(kind, bias), c['X'], c['y'], Xs, th, EPS)
+        cc.ep_margins(ep.ep_fit(K, c['y']))
+        w_l, w_e = cc.worst([x[t] for x in lp[:3]], ref), cc.worst([x[t] for x in epd[:3]], eref)
         far = _far_mean(c, th, Xs, ref['a'])
-        kss = lr.prior_var(kind, bias, Xs, th)
+        kss = _cov(kind, bias).prior_var(Xs, th)
         mscale, vscale = max(1.0, np.abs(ref['mean']).max()), max(1.0, np.abs(ref['var']).max())
         d_far = abs(lp[0][t, -1] - far) / mscale
         print('linear predict {0} theta {1}: Laplace {2:.2e} EP {3:.2e} far mean {4:.2e} (tol '
@@ -284,16 +255,16 @@ def test_is_predict_vs_restatement(nat, n, d, kind, bias, proposal, monkeypatch)
     discrepancy, floored at 1e-12, the discrepancy capped at 1e-6; prob, mean, var and ess of the
     default path at 1e-3. v*_j starts from the per-row k**."""
     c = _case('call', n, d, kind, bias)
-    Xs = _test_inputs(c, 70)
+    Xs = cc.far_test_inputs(c, 70, FAR)
     th = c['thetas'][1]
-    K = lr.gram(kind, bias, c['X'], th, EPS)
-    Ks = lr.gram_cross(kind, bias, Xs, c['X'], th)
-    kss = lr.prior_var(kind, bias, Xs, th)
-    _newton_margins(K, c['y'], 1e-4)
+    K = _cov(kind, bias).gram(c['X'], th, EPS)
+    Ks = _cov(kind, bias).gram_cross(Xs, c['X'], th)
+    kss = _cov(kind, bias).prior_var(Xs, th)
+    cc.newton_margins(K, c['y'], 1e-4, NEWTON_TOL)
     U = np.random.RandomState(107).normal(size=(n, 64)).astype(np.float32).astype(np.float64)
     fit = eis.state(K, c['y']) if proposal == 'ep' else eis.laplace_state(K, c['y'])
     if proposal == 'ep':
-        _ep_margins(fit)
+        cc.ep_margins(fit)
     ref = ipr.predictive(K, Ks, kss, c['y'], U, fit, 'probit')
     hi = ipr.h_route(K, Ks, kss, fit['W'], fit['a'], U[:, :1], dtype=np.longdouble)
     est = nat.EST_IS_EP if proposal == 'ep' else nat.EST_IS
@@ -339,12 +310,12 @@ def test_is_loo_vs_restatement(nat, proposal):
     log ess_loo within 1e-3 + 10 Y (Y the restatement's fp32 yardstick), gauss within its bound."""
     c = _case('call', 130, 5, 'ard', True)
     y, th = c['y'], c['thetas'][1]
-    K = lr.gram('ard', True, c['X'], th, EPS)
-    _newton_margins(K, y, 1e-4)
+    K = _cov('ard', True).gram(c['X'], th, EPS)
+    cc.newton_margins(K, y, 1e-4, NEWTON_TOL)
     U = np.random.RandomState(107).normal(size=(130, 64)).astype(np.float32).astype(np.float64)
     fit = eis.state(K, y) if proposal == 'ep' else eis.laplace_state(K, y)
     if proposal == 'ep':
-        _ep_margins(fit)
+        cc.ep_margins(fit)
     slot = ilr.slot_of(fit)
     ref = ilr.loo_quantities(y, *slot, U, 'probit')
 
@@ -395,7 +366,7 @@ def test_laplace_grad_vs_restatement_and_central_differences(nat, n, d, kind, bi
     against central differences (h = 1e-5) of the device's own Laplace theta-call, Newton
     tolerance 1e-14, at 1e-6; lml bitwise the Laplace theta-call's at the same settings."""
     c = _case('grad', n, d, kind, bias)
-    refs = [lr.laplace_grad(kind, bias, c['X'], c['y'], th, EPS, tol=NEWTON_TOL)
+    refs = [cr.laplace_grad(_cov(kind, bias), c['X'], c['y'], th, EPS, tol=NEWTON_TOL)
             for th in c['thetas']]
     for ref in refs:
         assert ref['diffs'][-1] <= NEWTON_TOL / 100.0
@@ -435,9 +406,9 @@ def test_ep_grad_vs_restatement_and_central_differences(nat, n, d, kind, bias):
     Context.ep's; at (130, 5) against central differences (h = 1e-5) of the device's own log Z_EP
     fitted to diff_tol = 1e-16 at 1e-6."""
     c = _case('epgrad', n, d, kind, bias)
-    refs = [lr.ep_grad(kind, bias, c['X'], c['y'], th, EPS) for th in c['thetas']]
+    refs = [cr.ep_grad(_cov(kind, bias), c['X'], c['y'], th, EPS) for th in c['thetas']]
     for ref in refs:
-        _ep_margins(ref['fit'])
+        cc.ep_margins(ref['fit'])
     worst_fd = 0.0
     ctx = _ctx(nat, c)
     try:
@@ -469,7 +440,7 @@ def test_ep_grad_vs_restatement_and_central_differences(nat, n, d, kind, bias):
 # ------------------------------------------------------------------ 5. lambda = 0
 
 
-@pytest.mark.parametrize('kind,bias', lr.KINDS)
+@pytest.mark.parametrize('kind,bias', cr.LINEAR_KINDS)
 def test_lambda_zero_is_the_kind_without_the_flag(nat, kind, bias):
     """theta_lambda = -800 (exp gives exactly 0): Gram, cross-Gram, the IS / PriorMC / Laplace
     theta-calls, the cached u-call and apm_predict are bitwise those of the same kind without the
@@ -481,9 +452,9 @@ def test_lambda_zero_is_the_kind_without_the_flag(nat, kind, bias):
     th0 = full[:-1] if bias else full[:-2]  # (the cases are biased ones: drop log beta too)
     c = dict(c, kind=kind, bias=bias)
     X, y = c['X'], c['y']
-    Xs = _test_inputs(c, 70)
+    Xs = cc.far_test_inputs(c, 70, FAR)
     thl = np.r_[th0, -800.0]
-    nk, nk0 = lr.native_kind(kind, bias), lr.native_kind(kind, bias, linear=False)
+    nk, nk0 = _cov(kind, bias).native_kind, _cov(kind, bias, False).native_kind
     K, K0 = np.empty((n, n)), np.empty((n, n))
     nat.gram(nk, K, X, thl, EPS)
     nat.gram(nk0, K0, X, th0, EPS)
@@ -522,7 +493,7 @@ def test_batches_are_bitwise_neutral(nat):
     """A biased + linear SE-ARD context (130, 5), max_batch = 4: a chain's IS theta-call, gradient
     and predictive outputs are bitwise the same alone, first of 3 and last of 4."""
     c = _case('grad', 130, 5, 'ard', True)
-    Xs = _test_inputs(c, 70)
+    Xs = cc.far_test_inputs(c, 70, FAR)
     n = c['n']
     rng = np.random.RandomState(5)
     other = c['thetas'][rng.randint(0, 4, size=3)] + rng.uniform(-0.2, 0.2, size=(3, 8))
@@ -559,7 +530,7 @@ def test_other_contexts_are_unchanged_by_a_linear_one(nat):
     same before, while and after a linear context on the same data exists and has run each of its
     entry points."""
     c = _case('call', 577, 4, 'ard', True)
-    Xs = _test_inputs(c, 70)
+    Xs = cc.far_test_inputs(c, 70, FAR)
     n, d = c['n'], c['d']
     th_base = c['thetas'][:, :d + 1]
     th_m52 = c['thetas'][:, :d + 2]
@@ -622,10 +593,10 @@ def test_large_lambda_without_inverse_panels(nat):
     assert 1.0 + math.exp(3.0) + math.exp(8.0) * x2 >= 2.0 ** 15 > 1.0 + math.exp(3.0) + x2
     assert math.log(math.exp(3.0) + math.exp(8.0) * x2) < 19.0
     ns = np.random.RandomState(23).normal(size=(n, 8))
-    K = lr.gram('ard', False, X, th_big, EPS)
-    _newton_margins(K, y, 1e-4)
-    spread = max(_oracle_moves(X, y, ns, K, seed) for seed in range(1, 9))
-    ref, _, rops = orc.is_estimate(X, y, lr.kernel_func('ard', False, EPS), ns, th_big)
+    K = _cov('ard', False).gram(X, th_big, EPS)
+    cc.newton_margins(K, y, 1e-4, NEWTON_TOL)
+    spread = max(cc.oracle_moves(X, y, ns, K, seed) for seed in range(1, 9))
+    ref, _, rops = orc.is_estimate(X, y, _cov('ard', False).kernel_func(EPS), ns, th_big)
     ctx = _ctx(nat, c, n_imp=8, max_batch=2, n_slots=2, n_ubufs=2)
     try:
         ctx.u_upload(0, ns)
@@ -658,7 +629,7 @@ def test_python_classes_return_the_native_bits(nat):
     from gpdemo.predict import LaplacePredictor
     c = _case('call', 130, 5, 'ard', True)
     X, y, th = c['X'], c['y'], c['thetas'][1]
-    Xs = _test_inputs(c, 70)
+    Xs = cc.far_test_inputs(c, 70, FAR)
     kf = krn.make_kernel_func('ard', EPS, bias=True, linear=True)
     assert kf.native_kind == 81
     ns = np.random.RandomState(41).normal(size=(130, 8))

@@ -12,7 +12,7 @@ import pytest
 import edge_cases as ec
 import grad_restatement as gr
 import logit_restatement as lr
-import matern_restatement as mr
+from cov_restatement import Cov
 
 pytestmark = pytest.mark.gpu
 
@@ -37,24 +37,23 @@ I_130, I_513 = 1, 3
 I_FAR = 3  # the last test row is far from this training row
 
 
+def _cov(c):
+    return Cov(c['family'] or 'se', c['kind'])
+
+
 def _gram(c, theta, X=None):
-    X = c['X'] if X is None else X
-    if c['family'] is None:
-        return gr.gram(c['kind'], X, theta, EPS)
-    return mr.gram(c['family'], c['kind'], X, theta, EPS)
+    return _cov(c).gram(c['X'] if X is None else X, theta, EPS)
 
 
 def _gram_cross(c, theta):
     if c['family'] is not None:
-        return mr.gram_cross(c['family'], c['kind'], c['Xs'], c['X'], theta)
+        return _cov(c).gram_cross(c['Xs'], c['X'], theta)
     n = c['n']
     return _gram(c, theta, np.concatenate([c['X'], c['Xs']]))[n:, :n].copy()
 
 
 def _dK(c, theta, K):
-    if c['family'] is None:
-        return gr.dK(c['kind'], c['X'], theta, K, EPS)
-    return mr.dK(c['family'], c['kind'], c['X'], theta, EPS)
+    return _cov(c).dK(c['X'], theta, EPS, K=K)
 
 
 def _draws(n, seed):

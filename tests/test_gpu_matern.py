@@ -1,7 +1,7 @@
 """Matérn 3/2 and 5/2 covariance kinds (iso and ARD) on the device: Gram and
 cross-Gram, the three estimators' theta-calls, the Laplace predictive distribution, the gradient
 of the Laplace log marginal likelihood, batch neutrality and a batched sampler, against the numpy
-restatement of tests/matern_restatement.py (the oracle's C Gram knows the SE family only) and
+restatement of tests/cov_restatement.py (the oracle's C Gram knows the SE family only) and
 the oracle's estimators run with the restatement's kernel_func."""
 import math
 
@@ -11,8 +11,10 @@ import scipy.linalg as la
 from scipy.special import ndtr
 
 import apm_oracle as orc
+import cov_checks as cc
+import cov_restatement as cr
 import grad_restatement as gr
-import matern_restatement as mr
+from cov_restatement import Cov
 
 pytestmark = pytest.mark.gpu
 
@@ -20,7 +22,8 @@ EPS = 1e-8
 TOL_NATS = 5e-4        # estimator values, no relative term: test_gpu_kernels.py
 TOL = 1e-9             # fp64 against fp64 through the same factorisation: test_gpu_predict / _grad
 NEWTON_TOL = 1e-14     # the gradient's Newton tolerance
-FAMILY_KINDS = [(f, k) for f in mr.FAMILIES for k in ('iso', 'ard')]
+FAR = 1000.0  # the far test row: k* underflows to exactly 0
+FAMILY_KINDS = [(f, k) for f in cr.MATERN for k in ('iso', 'ard')]
 # (family, n, d, kind) -> data seed, chosen so that for all three thetas (theta_0 = 0.3, 3.0,
 # -1.0) the restatement's last Newton `diff` is at least 100x below the tolerance and the one
 # before at least 100x above it at the gradient's 1e-14 (at n = 1, where the data cannot change the
@@ -96,10 +99,10 @@ GRAM_SHAPES = ([(n, d, kind, False) for n, d in ((1, 1), (129, 64), (300, 7))
                [(130, 6, 'iso', True), (200, 3, 'ard', True), (150, 40, 'ard', True)])
 
 
-@pytest.mark.parametrize('family', mr.FAMILIES)
+@pytest.mark.parametrize('family', cr.MATERN)
 @pytest.mark.parametrize('n,d,kind,dup', GRAM_SHAPES)
 def test_gram_vs_restatement(nat, family, n, d, kind, dup):
-    """Entry by entry within the bound derived from the arithmetic (mr.gram_bound; u = 2^-53):
+    """Entry by entry within the bound derived from the arithmetic (Cov.gram_bound; u = 2^-53):
     delta(r^2) = 4u sum_k (|a_k| + |c_k|)|a_k - c_k| + (D + 2) u r^2, |K - Kref| <= |Kref| (8u +
     2 delta(r^2)). K is exactly symmetric and its diagonal is exp(theta_0) + eps within 2 ulp.
     Measured maximum over all cases: see DESIGN.md §14."""
@@ -107,8 +110,8 @@ def test_gram_vs_restatement(nat, family, n, d, kind, dup):
     X, th = _gram_inputs(n, d, kind, dup)
     K = np.full((n, n), np.nan)
     krn.make_kernel_func(_name(family, kind), EPS)(K, X, th)
-    Kref = mr.gram(family, kind, X, th, EPS)
-    _check_gram(K, Kref, mr.gram_bound(kind, X, X, th, Kref), (family, n, d, kind, dup))
+    Kref = Cov(family, kind).gram(X, th, EPS)
+    _check_gram(K, Kref, Cov(family, kind).gram_bound(X, X, th, Kref), (family, n, d, kind, dup))
     assert np.array_equal(K, K.T)
     dg = math.exp(th[0]) + EPS
     assert np.all(np.abs(K.diagonal() - dg) <= 2 * np.spacing(dg))
@@ -133,8 +136,8 @@ def test_gram_cross_vs_restatement(nat, family, kind, m, n, d):
     th = np.r_[0.3, 0.5 * math.log(d) + rng.uniform(-0.3, 0.1, size=d if kind == 'ard' else 1)]
     Ks = nat.gram_cross(_native_kind(nat, family, kind), Xs, X, th)
     assert Ks.shape == (m, n)
-    ref = mr.gram_cross(family, kind, Xs, X, th)
-    _check_gram(Ks, ref, mr.gram_bound(kind, Xs, X, th, ref), (family, kind, m, n, d))
+    ref = Cov(family, kind).gram_cross(Xs, X, th)
+    _check_gram(Ks, ref, Cov(family, kind).gram_bound(Xs, X, th, ref), (family, kind, m, n, d))
     assert Ks[0, 7] == math.exp(th[0])
 
 
@@ -149,7 +152,7 @@ def test_estimators_vs_oracle(nat, family, kind):
     n, d = (130, 5) if kind == 'ard' else (200, 3)
     c = _case(family, n, d, kind)
     X, y = c['X'], c['y']
-    kf = mr.kernel_func(family, kind, EPS)
+    kf = Cov(family, kind).kernel_func(EPS)
     rng = np.random.RandomState(17)
     ns1, ns2 = rng.normal(size=(n, 8)), rng.normal(size=(n, 8))
     ctx = nat.Context(X, y, _native_kind(nat, family, kind), EPS, 8, max_batch=1, n_slots=2,
@@ -180,26 +183,18 @@ def test_estimators_vs_oracle(nat, family, kind):
 # ------------------------------------------------------------------ 3. prediction
 
 
-def _test_inputs(c, m):
-    rng = np.random.RandomState(1000 + c['n'])
-    Xs = rng.normal(size=(m, c['d']))
-    Xs[0] = c['X'][7]             # coincides with a training point
-    Xs[-1] = c['X'][3] + 1000.0   # so far away that k* underflows to exactly 0
-    return Xs
-
-
 def _predict_restatement(family, kind, c, Xs, th):
     """gr.newton at the predictor's default tolerance, then the predictive from the last
     iteration's W, L, a: mu = Ks a, var = s - |L^-1 (W^1/2 . ks)|^2, Phi(mu / sqrt(1 + var))."""
-    nw = gr.newton(mr.gram(family, kind, c['X'], th, EPS), c['y'], 1e-4)
-    Ks = mr.gram_cross(family, kind, Xs, c['X'], th)
+    nw = gr.newton(Cov(family, kind).gram(c['X'], th, EPS), c['y'], 1e-4)
+    Ks = Cov(family, kind).gram_cross(Xs, c['X'], th)
     mu = Ks.dot(nw['a'])
     V = la.solve_triangular(nw['L'], (Ks * nw['Ws'][None, :]).T, lower=True)
     var = math.exp(th[0]) - (V * V).sum(0)
     return dict(mean=mu, var=var, prob=ndtr(mu / np.sqrt(1.0 + var)), n_iter=nw['n_iter'])
 
 
-@pytest.mark.parametrize('family', mr.FAMILIES)
+@pytest.mark.parametrize('family', cr.MATERN)
 @pytest.mark.parametrize('n,d,m,kind', PREDICT_SHAPES)
 def test_predict_vs_restatement(nat, family, n, d, m, kind):
     """mean and var relative to max(1, max|ref|), prob absolute, at 1e-9 (test_gpu_predict's
@@ -208,7 +203,7 @@ def test_predict_vs_restatement(nat, family, n, d, m, kind):
     import gpdemo.kernels as krn
     import gpdemo.predict as prd
     c = _case(family, n, d, kind)
-    Xs = _test_inputs(c, m)
+    Xs = cc.far_test_inputs(c, m, FAR)
     p = prd.LaplacePredictor(c['X'], c['y'], krn.make_kernel_func(_name(family, kind), EPS), Xs)
     mean, var, prob = p(c['thetas'])
     nit = p.n_iter.copy()
@@ -240,13 +235,13 @@ def grad_refs():
         key = (family, n, d, kind)
         if key not in cache:
             c = _case(family, n, d, kind)
-            cache[key] = [mr.laplace_grad(family, kind, c['X'], c['y'], th, EPS, tol=NEWTON_TOL)
+            cache[key] = [cr.laplace_grad(Cov(family, kind), c['X'], c['y'], th, EPS, tol=NEWTON_TOL)
                           for th in c['thetas']]
         return cache[key]
     return get
 
 
-@pytest.mark.parametrize('family', mr.FAMILIES)
+@pytest.mark.parametrize('family', cr.MATERN)
 @pytest.mark.parametrize('n,d,kind', GRAD_SHAPES)
 def test_grad_vs_restatement_and_central_differences(nat, grad_refs, family, n, d, kind):
     """lml and grad against the restatement at 1e-9 of max(1, max|ref grad|) with equal Newton
@@ -278,7 +273,7 @@ def test_grad_vs_restatement_and_central_differences(nat, grad_refs, family, n, 
         scale = max(1.0, np.abs(ref['grad']).max())
         err = max(abs(lml[t] - ref['lml']), np.abs(grad[t] - ref['grad']).max()) / scale
         fd = gr.central_differences(
-            lambda x: mr.lml(family, kind, c['X'], c['y'], x, EPS, tol=1e-24), th)
+            lambda x: cr.lml(Cov(family, kind), c['X'], c['y'], x, EPS, tol=1e-24), th)
         err_fd = np.abs(grad[t] - fd).max() / max(1.0, np.abs(fd).max())
         worst, worst_fd = max(worst, err), max(worst_fd, err_fd)
         print('matern grad parity {0} theta {1}: {2:.3e}, vs fd {3:.3e} (max|grad| {4:.3e})'
@@ -298,7 +293,7 @@ def test_batches_are_bitwise_neutral(nat):
     """One Matérn 5/2 ARD context (130, 5), max_batch = 8: a chain's gradient and predictive
     outputs are bitwise the same alone, first of 3 and last of 8."""
     c = _case('52', 130, 5, 'ard')
-    Xs = _test_inputs(c, 70)
+    Xs = cc.far_test_inputs(c, 70, FAR)
     rng = np.random.RandomState(5)
     other = c['thetas'][rng.randint(0, 3, size=7)] + rng.uniform(-0.2, 0.2, size=(7, 6))
     ctx = nat.Context(c['X'], c['y'], nat.KERNEL_M52_ARD, EPS, 1, max_batch=8, n_slots=1,
@@ -340,7 +335,7 @@ def test_batched_ess_mh_matern52_ard(nat):
     assert smp.ctx.kind == nat.KERNEL_M52_ARD
     th, nrej = smp.get_samples(4, th0)  # the start state and 3 iterations
     assert np.isfinite(th).all() and not smp.failed.any()
-    kf = mr.kernel_func('52', 'ard', EPS)
+    kf = Cov('52', 'ard').kernel_func(EPS)
     for ch in range(3):
         lp = smp.log_prior(smp.theta[ch][None])[0]
         out, st = smp.ctx.u_eval([smp.slot_cur[ch]], [smp.ub_u[ch]])

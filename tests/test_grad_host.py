@@ -9,7 +9,9 @@ import re
 import numpy as np
 import pytest
 
+import cov_restatement as cr
 import grad_restatement as gr
+from cov_restatement import Cov
 from conftest import REPO
 
 EPS = 1e-8
@@ -26,8 +28,8 @@ def test_restatement_vs_central_differences(n, d, kind, seed):
     another BLAS while a wrong sign or a factor of 2 misses it by six orders of magnitude."""
     c = gr.make_case(n, d, kind, seed)
     for th in c['thetas']:
-        ref = gr.laplace_grad(kind, c['X'], c['y'], th, EPS, tol=1e-24)
-        fd = gr.central_differences(lambda t: gr.lml(kind, c['X'], c['y'], t, EPS, tol=1e-24), th)
+        ref = cr.laplace_grad(Cov('se', kind), c['X'], c['y'], th, EPS, tol=1e-24)
+        fd = gr.central_differences(lambda t: cr.lml(Cov('se', kind), c['X'], c['y'], t, EPS, tol=1e-24), th)
         err = np.abs(ref['grad'] - fd).max() / max(1.0, np.abs(fd).max())
         print('restatement vs fd {0}: {1:.3e}'.format((n, d, kind, th[0]), err))
         assert err <= 1e-6
@@ -60,9 +62,9 @@ def test_restatement_epsilon_rule_is_visible():
     grad[0] by epsilon * trace(M), far above the central-difference error."""
     c = gr.make_case(64, 33, 'ard', 364)
     th = c['thetas'][0]
-    fd = gr.central_differences(lambda t: gr.lml('ard', c['X'], c['y'], t, 1e-2, tol=1e-24), th)
-    right = gr.laplace_grad('ard', c['X'], c['y'], th, 1e-2, tol=1e-24)['grad']
-    wrong = gr.laplace_grad('ard', c['X'], c['y'], th, 1e-2, tol=1e-24, eps_in_dk0=True)['grad']
+    fd = gr.central_differences(lambda t: cr.lml(Cov('se', 'ard'), c['X'], c['y'], t, 1e-2, tol=1e-24), th)
+    right = cr.laplace_grad(Cov('se', 'ard'), c['X'], c['y'], th, 1e-2, tol=1e-24)['grad']
+    wrong = cr.laplace_grad(Cov('se', 'ard'), c['X'], c['y'], th, 1e-2, tol=1e-24, wrong='eps_in_dk0')['grad']
     assert np.abs(right - fd).max() <= 1e-6 * max(1.0, np.abs(fd).max())
     assert abs(wrong[0] - fd[0]) > 1e-4 and np.array_equal(wrong[1:], right[1:])
 

@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 
 import epis_restatement as eis
-import grad_restatement as gr
 import is_spread_restatement as sr
+from cov_restatement import Cov
 from conftest import REPO
 
 EPS = 1e-8
@@ -32,7 +32,7 @@ def study():
     ns = np.random.RandomState(DRAW_SEED).normal(size=(130, N_REP * S))
     out = {'y': y, 'ns': ns}
     for s0 in (0.3, 3.0):
-        K = gr.gram('ard', X, np.r_[s0, np.full(5, 0.5)], EPS)
+        K = Cov('se', 'ard').gram(X, np.r_[s0, np.full(5, 0.5)], EPS)
         for name, st in (('laplace', eis.laplace_state(K, y)), ('ep', eis.state(K, y))):
             out[s0, name] = dict(st=st, lw=sr.log_weights(y, st, ns))
     return out

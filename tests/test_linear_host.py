@@ -10,26 +10,27 @@ import numpy as np
 import pytest
 from scipy.special import ndtr
 
-import bias_restatement as br
+import cov_restatement as cr
 import grad_restatement as gr
-import linear_restatement as lr
+from cov_restatement import Cov
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = 1e-8
 
 
-@pytest.mark.parametrize('kind,bias', lr.KINDS)
+@pytest.mark.parametrize('kind,bias', cr.LINEAR_KINDS)
 @pytest.mark.parametrize('log_lambda', [-2.0, 1.0])
 def test_dk_against_central_differences(kind, bias, log_lambda):
     """The restatement's gradient (M against the P matrices dK/dtheta_j, the last one
     lambda x_i . x_j) against central differences of its own converged LML: 1e-6 of
     max(1, max|grad|) (test_bias_host's bound), n = 40, d = 3."""
-    c = lr.make_case(40, 3, kind, bias, 300, pairs=((0.3, log_lambda),))
+    cov = Cov('se', kind, bias, linear=True)
+    c = gr.make_case(40, 3, kind, 300, rows=[(0.3, 1.5, log_lambda) if bias else (0.3, log_lambda)])
     th = c['thetas'][0]
-    assert th.shape[0] == lr.theta_len(kind, bias, 3) and th[-1] == log_lambda
+    assert th.shape[0] == cov.theta_len(3) and th[-1] == log_lambda
     assert (not bias) or th[-2] == 1.5
-    ref = lr.laplace_grad(kind, bias, c['X'], c['y'], th, EPS, tol=1e-24)
-    fd = gr.central_differences(lambda x: lr.lml(kind, bias, c['X'], c['y'], x, EPS), th)
+    ref = cr.laplace_grad(cov, c['X'], c['y'], th, EPS, tol=1e-24)
+    fd = gr.central_differences(lambda x: cr.lml(cov, c['X'], c['y'], x, EPS), th)
     err = np.abs(ref['grad'] - fd).max() / max(1.0, np.abs(ref['grad']).max())
     print('linear dK vs fd {0}: {1:.3e}'.format((kind, bias, log_lambda), err))
     assert err <= 1e-6
@@ -44,35 +45,36 @@ def test_restatement_definition():
     X, Xs = rng.normal(size=(7, 3)), rng.normal(size=(4, 3))
     Xs[0] = X[2]
     lam = math.exp(1.0)
-    for kind, bias in lr.KINDS:
+    for kind, bias in cr.LINEAR_KINDS:
+        cov = Cov('se', kind, bias, linear=True)
         beta = math.exp(1.5) if bias else 0.0
-        th = np.r_[0.3, rng.normal(size=br.n_base(kind, 3) - 1), [1.5] if bias else [], 1.0]
-        assert th.shape[0] == lr.theta_len(kind, bias, 3)
+        th = np.r_[0.3, rng.normal(size=cov.n_base(3) - 1), [1.5] if bias else [], 1.0]
+        assert th.shape[0] == cov.theta_len(3)
         th0 = np.r_[th[:-1], -800.0]
-        K0 = lr.gram(kind, bias, X, th0, EPS)
+        K0 = cov.gram(X, th0, EPS)
         if bias:
-            assert np.array_equal(K0, br.gram('se', kind, X, th[:-1], EPS))
+            assert np.array_equal(K0, Cov('se', kind, bias=True).gram(X, th[:-1], EPS))
         else:
-            Kb = gr.gram(kind, X, th[:-1], EPS)
+            Kb = Cov('se', kind).gram(X, th[:-1], EPS)
             off = ~np.eye(7, dtype=bool)
             assert np.array_equal(K0[off], Kb[off])
             assert np.all(K0.diagonal() == math.exp(0.3) + EPS)
-        K = lr.gram(kind, bias, X, th, EPS)
+        K = cov.gram(X, th, EPS)
         assert np.allclose(K - K0, lam * X.dot(X.T), rtol=1e-13, atol=1e-14)
         assert np.array_equal(K, K.T)
         assert np.allclose(K.diagonal(), math.exp(0.3) + beta + lam * (X * X).sum(1) + EPS,
                            rtol=1e-15, atol=0)
-        Ks = lr.gram_cross(kind, bias, Xs, X, th)
+        Ks = cov.gram_cross(Xs, X, th)
         assert abs(Ks[0, 2] - (math.exp(0.3) + beta + lam * X[2].dot(X[2]))) <= 1e-14 * Ks[0, 2]
-        kss = lr.prior_var(kind, bias, Xs, th)
+        kss = cov.prior_var(Xs, th)
         assert kss.shape == (4,) and abs(kss[0] - Ks[0, 2]) <= 1e-14 * kss[0]
-        D = lr.dK(kind, bias, X, th)
+        D = cov.dK(X, th, EPS)
         assert len(D) == th.shape[0] and np.allclose(D[-1], lam * X.dot(X.T), rtol=1e-15)
         assert np.all(D[0].diagonal() == math.exp(0.3))
         if bias:
             assert np.all(D[-2] == math.exp(1.5))
         with pytest.raises(IndexError):
-            lr.gram(kind, bias, X, th[:-1], EPS)
+            cov.gram(X, th[:-1], EPS)
 
 
 def _trend_data():
@@ -80,7 +82,7 @@ def _trend_data():
     Bernoulli(Phi(latent))."""
     rng = np.random.RandomState(5)
     X = rng.normal(size=(200, 2))
-    K = br.base_S('se', 'iso', X, np.zeros(2)) + 1e-8 * np.eye(200)
+    K = Cov('se', 'iso').base_S(X, np.zeros(2)) + 1e-8 * np.eye(200)
     f = np.linalg.cholesky(K).dot(rng.normal(size=200)) + 2.0 * X[:, 0] - X[:, 1]
     y = np.where(rng.uniform(size=200) < ndtr(f), 1.0, -1.0)
     return X, y
@@ -92,9 +94,10 @@ def test_linear_term_raises_the_evidence_of_data_with_a_trend():
     the measured gap)."""
     X, y = _trend_data()
 
+    cov = Cov('se', 'iso', linear=True)
+
     def grid_max(log_lambda):
-        return max(gr.newton(lr.gram('iso', False, X, np.r_[t0, t1, log_lambda], EPS), y,
-                             1e-10)['lml']
+        return max(gr.newton(cov.gram(X, np.r_[t0, t1, log_lambda], EPS), y, 1e-10)['lml']
                    for t0 in np.linspace(-2.0, 3.0, 6) for t1 in np.linspace(-1.0, 1.0, 5))
     with_linear, without = grid_max(1.0), grid_max(-800.0)
     print('data with a trend: grid max LML {0:.2f} with log lambda = 1, {1:.2f} with lambda = 0'
@@ -110,17 +113,18 @@ def test_python_names_and_flags():
     import gpdemo.kernels as krn
     import auxpm.batched as bt
     assert _native.COV_LINEAR == 64
-    for kind, bias in lr.KINDS:
+    for kind, bias in cr.LINEAR_KINDS:
         base = krn.make_kernel_func(kind, 1e-6, bias=bias)
         lin = krn.make_kernel_func(kind, 1e-6, bias=bias, linear=True)
-        assert lin.native_kind == lr.native_kind(kind, bias) == base.native_kind | 64
+        cov = Cov('se', kind, bias, linear=True)
+        assert lin.native_kind == cov.native_kind == base.native_kind | 64
         assert lin.native_kind in (64, 65, 80, 81)
         assert lin.linear is True and base.linear is False and lin.bias is bias
         assert 'linear' not in repr(base)
         assert repr(lin) == repr(base)[:-1] + ', linear=True)'
         for d in (1, 5):
-            assert _native.theta_len(lin.native_kind, d) == lr.theta_len(kind, bias, d)
-            assert _native.theta_len(base.native_kind, d) == lr.theta_len(kind, bias, d) - 1
+            assert _native.theta_len(lin.native_kind, d) == cov.theta_len(d)
+            assert _native.theta_len(base.native_kind, d) == cov.theta_len(d) - 1
     for name in ('matern32_iso', 'matern32_ard', 'matern52_iso', 'matern52_ard', 'nonsense'):
         with pytest.raises(ValueError):
             krn.make_kernel_func(name, 1e-8, linear=True)
@@ -164,8 +168,9 @@ def test_abi_declares_the_flag_and_refuses_what_it_should():
     # each of the four kinds: a theta of length P - 1 is too short (d = 3)
     X3 = np.zeros((2, 3))
     th6 = np.zeros(6)
-    for kind, bias in lr.KINDS:
-        nk, P = lr.native_kind(kind, bias), lr.theta_len(kind, bias, 3)
+    for kind, bias in cr.LINEAR_KINDS:
+        cov = Cov('se', kind, bias, linear=True)
+        nk, P = cov.native_kind, cov.theta_len(3)
         assert nk in (64, 65, 80, 81)
         assert lib.apm_gram(0, nk, X3.ctypes.data, 2, 3, 3, th6.ctypes.data, P - 1, 1e-8,
                             K.ctypes.data, 2) == _native.APM_E_INVALID

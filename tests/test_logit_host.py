@@ -12,6 +12,7 @@ import pytest
 
 import grad_restatement as gr
 import logit_restatement as lr
+from cov_restatement import Cov
 from conftest import REPO
 
 EPS = 1e-8
@@ -30,17 +31,17 @@ def test_restated_gradient_vs_central_differences():
     c = gr.make_case(40, 3, 'ard', 40)
     for tol, bound in ((1e-12, 1e-5), (1e-24, 1e-6)):
         for th in c['thetas']:
-            K = gr.gram('ard', c['X'], th, EPS)
-            ref = lr.laplace_grad(K, gr.dK('ard', c['X'], th, K, EPS), c['y'], tol=tol)
+            K = Cov('se', 'ard').gram(c['X'], th, EPS)
+            ref = lr.laplace_grad(K, Cov('se', 'ard').dK(c['X'], th, EPS, K=K), c['y'], tol=tol)
             fd = lr.central_differences(
-                lambda t: lr.lml(gr.gram('ard', c['X'], t, EPS), c['y'], tol=tol), th)
+                lambda t: lr.lml(Cov('se', 'ard').gram(c['X'], t, EPS), c['y'], tol=tol), th)
             err = np.abs(ref['grad'] - fd).max() / max(1.0, np.abs(fd).max())
             print('logit restatement vs fd, Newton tol {0:g}, theta_0 {1}: {2:.3e} (max|fd| '
                   '{3:.3e})'.format(tol, th[0], err, np.abs(fd).max()))
             assert err <= bound
     # (the probit's restatement at the same theta is another function altogether)
     th = c['thetas'][0]
-    K = gr.gram('ard', c['X'], th, EPS)
+    K = Cov('se', 'ard').gram(c['X'], th, EPS)
     assert abs(gr.newton(K, c['y'], 1e-12)['lml'] - lr.lml(K, c['y'], 1e-12)) > 1e-3
 
 
@@ -53,7 +54,7 @@ def test_consistent_is_form_equals_the_direct_one():
     c = gr.make_case(30, 3, 'ard', 30)
     ns = np.random.RandomState(3).normal(size=(30, 64))
     for th in c['thetas']:
-        K = gr.gram('ard', c['X'], th, 1e-4)
+        K = Cov('se', 'ard').gram(c['X'], th, 1e-4)
         st = lr.is_state(K, c['y'])
         direct, C_chol = lr.is_direct(K, c['y'], st, ns)
         cons = lr.is_consistent(c['y'], st, ns, C_chol)
@@ -64,7 +65,7 @@ def test_consistent_is_form_equals_the_direct_one():
         assert abs(direct - cons) <= 1e-9 * max(1.0, abs(direct))
         assert abs(own - cons) <= 1e-9 * max(1.0, abs(direct))
     # PriorMC is the same form with W = z = 0 and chol(K) as the factor
-    K = gr.gram('ard', c['X'], c['thetas'][0], 1e-4)
+    K = Cov('se', 'ard').gram(c['X'], c['thetas'][0], 1e-4)
     zero = dict(f=np.zeros(30), W=np.zeros(30), a=np.zeros(30), logdet_B=0.0,
                 C_chol=np.linalg.cholesky(K))
     assert abs(lr.priormc(K, c['y'], ns) - lr.is_consistent(c['y'], zero, ns)) <= 1e-12

@@ -1,5 +1,5 @@
 """Host side of the Matérn covariance kinds: the numpy restatement the device is
-compared with (tests/matern_restatement.py) agrees with central differences of its own log
+compared with (tests/cov_restatement.py) agrees with central differences of its own log
 marginal likelihood - which pins the G formulas of the length-scale derivatives before any device
 work -, make_kernel_func knows the four names, and the C-ABI declares the four kinds and refuses
 an unknown one. No device is needed."""
@@ -9,15 +9,16 @@ import re
 import numpy as np
 import pytest
 
+import cov_restatement as cr
 import grad_restatement as gr
-import matern_restatement as mr
+from cov_restatement import Cov
 from conftest import REPO
 
 EPS = 1e-8
 NAMES = {'matern32_iso': 3, 'matern32_ard': 4, 'matern52_iso': 5, 'matern52_ard': 6}
 
 
-@pytest.mark.parametrize('family', mr.FAMILIES)
+@pytest.mark.parametrize('family', cr.MATERN)
 @pytest.mark.parametrize('kind', ['iso', 'ard'])
 def test_restatement_vs_central_differences(family, kind):
     """Analytic gradient against central differences (h = 1e-5) of the restatement's own LML at
@@ -26,22 +27,27 @@ def test_restatement_vs_central_differences(family, kind):
     entries are off by order one."""
     c = gr.make_case(40, 3, kind, 700)
     for th in c['thetas']:
-        ref = mr.laplace_grad(family, kind, c['X'], c['y'], th, EPS, tol=1e-24)
+        ref = cr.laplace_grad(Cov(family, kind), c['X'], c['y'], th, EPS, tol=1e-24)
         fd = gr.central_differences(
-            lambda t: mr.lml(family, kind, c['X'], c['y'], t, EPS, tol=1e-24), th)
+            lambda t: cr.lml(Cov(family, kind), c['X'], c['y'], t, EPS, tol=1e-24), th)
         err = np.abs(ref['grad'] - fd).max() / max(1.0, np.abs(fd).max())
         print('matern {0} {1} restatement vs fd, theta_0 {2}: {3:.3e}'
               .format(family, kind, th[0], err))
-        assert ref['grad'].shape == (mr.n_theta(kind, 3),)
+        assert ref['grad'].shape == (Cov(family, kind).theta_len(3),)
         assert err <= 1e-6
 
 
 def test_restatement_leaves_grad_restatement_as_it_was():
-    """The substitution of K and dK lasts for one call only."""
-    before = gr.gram, gr.dK
+    """A Matern call leaves the SE results as they were: nothing is substituted anywhere."""
     c = gr.make_case(8, 2, 'ard', 1)
-    mr.laplace_grad('32', 'ard', c['X'], c['y'], c['thetas'][0], EPS)
-    assert (gr.gram, gr.dK) == before
+    se = Cov('se', 'ard')
+
+    def se_results():
+        ref = cr.laplace_grad(se, c['X'], c['y'], c['thetas'][0], EPS)
+        return [se.gram(c['X'], c['thetas'][0], EPS), ref['grad']] + se.dK(c['X'], c['thetas'][0], EPS)
+    before = se_results()
+    cr.laplace_grad(Cov('32', 'ard'), c['X'], c['y'], c['thetas'][0], EPS)
+    assert all(np.array_equal(a, b) for a, b in zip(before, se_results()))
 
 
 def test_restatement_values_by_hand():
@@ -50,19 +56,19 @@ def test_restatement_values_by_hand():
     th = np.array([0.5, np.log(0.5)])
     s, r = np.exp(0.5), 2.0
     for kind in ('iso', 'ard'):
-        K3 = mr.gram('32', kind, X, th, 1e-3)
-        K5 = mr.gram('52', kind, X, th, 1e-3)
+        K3 = Cov('32', kind).gram(X, th, 1e-3)
+        K5 = Cov('52', kind).gram(X, th, 1e-3)
         assert abs(K3[0, 1] - s * (1 + 3 ** 0.5 * r) * np.exp(-3 ** 0.5 * r)) <= 1e-15
         assert abs(K5[0, 1] - s * (1 + 5 ** 0.5 * r + 5.0 / 3.0 * r * r) * np.exp(-5 ** 0.5 * r)) <= 1e-15
         assert K3[0, 0] == s + 1e-3 and K5[1, 1] == s + 1e-3 and np.array_equal(K3, K3.T)
-        d3 = mr.dK('32', kind, X, th, 1e-3)
-        d5 = mr.dK('52', kind, X, th, 1e-3)
+        d3 = Cov('32', kind).dK(X, th, 1e-3)
+        d5 = Cov('52', kind).dK(X, th, 1e-3)
         assert len(d3) == 2 and d3[0][0, 0] == s and d3[1][0, 0] == 0.0
         assert abs(d3[1][0, 1] - 3 * s * np.exp(-3 ** 0.5 * r) * r * r) <= 1e-15
         assert abs(d5[1][0, 1] - 5.0 / 3.0 * s * (1 + 5 ** 0.5 * r) * np.exp(-5 ** 0.5 * r) * r * r) <= 1e-15
-    assert mr.gram_cross('32', 'iso', X[:1], X[:1], th)[0, 0] == s  # no epsilon on k*
+    assert Cov('32', 'iso').gram_cross(X[:1], X[:1], th)[0, 0] == s  # no epsilon on k*
     with pytest.raises(IndexError):
-        mr.gram('52', 'ard', np.zeros((2, 3)), np.zeros(3), EPS)
+        Cov('52', 'ard').gram(np.zeros((2, 3)), np.zeros(3), EPS)
 
 
 def test_make_kernel_func_names_and_kinds():
