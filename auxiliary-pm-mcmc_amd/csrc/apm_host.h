@@ -8,6 +8,7 @@
 //   host_theta.cpp    the theta-call: concurrent chol(K), posterior factor, guard, ICM check
 //   host_laplace.cpp  apm_laplace's fit and covariance, the predictive and gradient paths
 //   host_ep.cpp       the sweep loop of parallel expectation propagation (ep.hip)
+//   host_predict_joint.cpp  the joint Laplace / EP predictive's tail: covariance, factor, draws
 //   host_is_predict.cpp  the importance-sampling predictive's tail after an IS theta-call
 //   host_is_diag.cpp  block estimates and weight diagnostics of the IS estimate over replicates
 //   host_is_loo.cpp   leave-one-out predictive densities from the IS samples of a cached u-call
@@ -287,6 +288,14 @@ struct __attribute__((visibility("hidden"))) apm_ctx {
     // (max_batch x sp) and k_is_logw's ess (max_batch), and the outputs (loo_psis and khat:
     // 2 x max_batch x np; khat_w: max_batch)
     double *psis_w = nullptr, *psis_t = nullptr, *psis_out = nullptr;
+    // the joint predictive (apm_predict_joint), allocated at its first call that draws: the labels
+    // (np) and the chains' Philox keys ([seeds | counters], max_batch each); and, grown to the
+    // largest number of draws asked for so far (jn_cap rows, a multiple of 64), the normals Xi^T
+    // (max_batch x jn_cap x np), the tile partials of the draws' log-likelihoods (max_batch x nb x
+    // jn_cap) and, at the first call that wants them back, the draws (max_batch x jn_cap x np)
+    double *jn_ys = nullptr, *jn_xi = nullptr, *jn_part = nullptr, *jn_draws = nullptr;
+    uint64_t* jn_keys = nullptr;
+    int64_t jn_cap = 0;
 };
 
 namespace apm_host __attribute__((visibility("hidden"))) {
@@ -502,7 +511,7 @@ void laplace_on_K(apm_ctx* c, const double* K, int64_t ldk, double* f_out, doubl
 // Newton factor; returns their number
 int laplace_then_live(apm_ctx* c, int count, double* lml, int* status, int64_t* n_iter);
 void predict_buffers(apm_ctx* c);
-void predict_block(apm_ctx* c, int count, int ms);
+void predict_block(apm_ctx* c, int count, int ms, bool with_cov = false);
 // One call's test inputs Xs (m x d, row stride ldxs), a block of at most np rows at a time: the
 // constructor uploads the chains' s = exp(theta_0), s + beta and beta to psig / pkss / pbet
 // (predict_buffers() first; cov_beta) and, for a kind with the linear term, lambda to plam; upload()
@@ -534,6 +543,20 @@ void grad_buffers(apm_ctx* c);
 void grad_block(apm_ctx* c, int count);
 // grad_block's second pass for the chains left live by ep_fit: d log Z_EP / d theta into c->gout
 void ep_grad_block(apm_ctx* c, int count);
+
+// ---- host_predict_joint.cpp -----------------------------------------------------------------
+// The joint predictive's tail for the chains left live by a Laplace theta-call or
+// an EP fit (st_h their statuses) at the m <= np test inputs: mean (count x m, row stride ldo),
+// cov (count blocks of m rows, row stride ldc, both triangles), n_draws draws of the latent
+// function (count x n_draws x m) from the streams (seeds[i], counters[i]) and the joint log
+// predictive density of the labels ys under them (count); any output may be null, the last two
+// need n_draws > 0. A chain whose chol(Sigma + eps I) fails gets APM_STATUS_CHOL_C in st_h. Rows
+// of a chain that is not OK hold stale values, which the C-ABI overwrites.
+void predict_joint_tail(apm_ctx* c, int count, const double* thetas, int64_t ldt, int* st_h,
+                        const double* Xs, int64_t m, int64_t ldxs, double* mean, int64_t ldo,
+                        double* cov, int64_t ldc, int64_t n_draws, const uint64_t* seeds,
+                        const uint64_t* counters, double* draws, const double* ys,
+                        double* joint_lpd);
 
 // ---- host_is_predict.cpp --------------------------------------------------------------------
 // The predictive tail after an APM_EST_IS / APM_EST_IS_EP theta-call on the same context (its

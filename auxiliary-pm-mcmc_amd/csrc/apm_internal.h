@@ -331,6 +331,34 @@ void launch_predict_reduce(int lik, MatB A, int64_t row0, int ms, int mb, int nb
                            const double* part, int64_t pstride, double* mean, double* var,
                            double* prob, int64_t ostride, Live live, int nchains, hipStream_t s);
 
+// ---- predict_joint.hip: joint Laplace / EP predictive at test inputs --------
+// The block: chain b's A rows and columns [row0, row0 + 64 mb), the free rows behind the factor.
+// Its lower tiles <- the test-test Gram of the ms staged test inputs Xs (row-major, ld = d), k**
+// on the diagonal, no epsilon; the identity beyond ms. sig / bet / lam as launch_gram_cross.
+void launch_gram_test(MatB A, int64_t row0, const double* Xs, int ms, int mb, int d,
+                      const double* theta, int64_t tstride, const double* sig, const double* bet,
+                      const double* lam, int kind, Live live, int nchains, hipStream_t s);
+// eps onto the block's ms real diagonal entries
+void launch_joint_eps(MatB A, int64_t row0, int ms, double eps, Live live, int nchains,
+                      hipStream_t s);
+// xi[b * xstride + r * ldx + j] <- element j S + r of the normal stream (seeds[b], counters[b]),
+// r < S, j < ms (philox.h); nothing else is written
+void launch_joint_normal(double* xi, int64_t xstride, int64_t ldx, const uint64_t* seeds,
+                         const uint64_t* counters, int ms, int S, Live live, int nchains,
+                         hipStream_t s);
+// f[r][j] = mean[b * mstride + j] + sum_k xi[r][k] L[j][k], L the block's lower factor (zeros above
+// the diagonal), xi sp = 64 ceil(S / 64) rows of ldx >= 64 mb doubles with zeros beyond (S, ms):
+// draws[b * dstride + r * ms + j] <- f (r < S, j < ms) unless null; with labels ys (ms, +-1)
+// part[b * pstride + tj * sp + r] <- sum over the columns j < ms of tile tj of log p(ys_j | f[r][j])
+// (lik: APM_LIK_*), else part is not written
+void launch_joint_draw(int lik, MatB A, int64_t row0, int ms, int mb, const double* xi,
+                       int64_t xstride, int64_t ldx, int S, int sp, const double* mean,
+                       int64_t mstride, const double* ys, double* draws, int64_t dstride,
+                       double* part, int64_t pstride, Live live, int nchains, hipStream_t s);
+// out[b] = logsumexp_{r < S} sum_{tj < mb} part[b * pstride + tj * sp + r] - log S (is_lme)
+void launch_joint_lme(const double* part, int64_t pstride, int mb, int S, int sp, double* out,
+                      Live live, int nchains, hipStream_t s);
+
 // ---- gradient.hip: gradient of the Laplace LML w.r.t. theta ---------------
 // per chain and row r < 64 nb: dS = K_rr - |row np + r of A over columns [0, 64 nb)|^2,
 // g = y phi(f)/Phi(y f), s2 = 1/2 dS d3 (third derivative of log p at f); zeros for r >= n.

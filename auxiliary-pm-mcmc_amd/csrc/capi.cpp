@@ -763,6 +763,53 @@ int apm_ep_predict(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt,
     });
 }
 
+int apm_predict_joint(apm_ctx* c, int approx, int64_t count, const double* thetas, int64_t ldt,
+                      const double* Xs, int64_t m, int64_t ldxs, double* mean, int64_t ldo,
+                      double* cov, int64_t ldc, int64_t n_draws, const uint64_t* seeds,
+                      const uint64_t* counters, double* draws, const double* ys,
+                      double* joint_lpd, int* status, int64_t* n_iter) {
+    ThetaArgs a;
+    if (approx != APM_JOINT_LAPLACE && approx != APM_JOINT_EP)
+        a.early = "APM_JOINT_LAPLACE or APM_JOINT_EP only";
+    a.probit_only = approx == APM_JOINT_EP;
+    a.device_why = "needs an ISO or ARD context (the cross-covariance is built on the device)";
+    a.batch = true;
+    a.count = count;
+    a.rest_msg = "bad arguments, m outside [1, apm_padded_n] or n_draws outside [0, "
+                 "APM_JOINT_MAX_DRAWS]";
+    const int rc = check_theta_call(c, "apm_predict_joint", a, [&] {
+        const bool sampled = draws || joint_lpd;
+        return !thetas || !Xs || !status || ldt < c->P || ldxs < c->d || m < 1 || m > c->np ||
+               (mean && ldo < m) || (cov && ldc < m) || n_draws < 0 ||
+               n_draws > APM_JOINT_MAX_DRAWS || (sampled && (n_draws == 0 || !seeds || !counters)) ||
+               (joint_lpd && !ys);
+    });
+    if (rc != APM_SUCCESS) return rc;
+    return ctx_call(c, SKEW, [&] {
+        int ok = 0;
+        EpFit fit;  // (alive until the tail's synchronisation)
+        if (approx == APM_JOINT_EP) {
+            ep_gram_fit(c, count, thetas, ldt, fit);
+            sync(c);
+            ep_report(fit, count, status, n_iter);
+            ok = fit.ok;
+        } else {
+            upload_thetas(c, count, thetas, ldt);
+            std::vector<double> lml((size_t)count);
+            ok = laplace_then_live(c, (int)count, lml.data(), status, n_iter);
+        }
+        if (ok)
+            predict_joint_tail(c, (int)count, thetas, ldt, status, Xs, m, ldxs, mean, ldo, cov, ldc,
+                               n_draws, seeds, counters, draws, ys, joint_lpd);
+        finish_rows(count, status, {{mean, ldo, m}, {draws, n_draws * m, n_draws * m}},
+                    {joint_lpd});
+        for (int64_t b = 0; cov && b < count; ++b)  // (a block's rows are ldc apart, m wide)
+            for (int64_t r = 0; status[b] != APM_STATUS_OK && r < m; ++r)
+                std::fill(cov + (b * m + r) * ldc, cov + (b * m + r) * ldc + m,
+                          std::numeric_limits<double>::quiet_NaN());
+    });
+}
+
 int apm_ep_grad(apm_ctx* c, int64_t count, const double* thetas, int64_t ldt, double* logz,
                 double* grad, int64_t ldg, int* status, int64_t* n_sweeps) {
     ThetaArgs a;

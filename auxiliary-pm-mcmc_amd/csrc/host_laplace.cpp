@@ -78,6 +78,8 @@ int laplace_then_live(apm_ctx* c, int count, double* lml, int* status, int64_t* 
 // W^1/2 . k* into the free rows [np, np + 64 mb) of A and mu*'s partials, the panel solves and
 // outer updates of those rows against the last Newton factor (as augmented(), without the
 // bottom-right SYRK), the row reduction; outputs in pmean / pvar / pprob (row stride np).
+// with_cov (the joint predictive, host_predict_joint.cpp): the trailing updates also cover the
+// lower tiles of the block behind the rows, A[np.., np..] -= V V^T, as augmented()'s do.
 // predict_buffers() first.
 void predict_buffers(apm_ctx* c) {
     if (c->pxs) return;
@@ -95,14 +97,15 @@ void predict_buffers(apm_ctx* c) {
     if (lin) c->plam = c->pbet + B;
 }
 
-void predict_block(apm_ctx* c, int count, int ms) {
+void predict_block(apm_ctx* c, int count, int ms, bool with_cov) {
     const Live lv = live_of(c);
     const int nb = c->nb, mb = (ms + 63) / 64;
     const int64_t np = c->np;
     launch_gram_cross(c->A, np, c->pxs, ms, mb, c->X, c->d, c->n, c->d, nb, c->theta, c->P,
                       c->psig, c->pbet, c->plam, c->kind, c->v.Ws, c->v.a, c->v.vstride, c->ppart,
                       nb * np, lv, 0, count, c->stream);
-    chol_solve_rows(c, c->A, nb, /*row_start=*/nb, /*R=*/nb + mb, /*Cb=*/nb, count);
+    chol_solve_rows(c, c->A, nb, /*row_start=*/nb, /*R=*/nb + mb, /*Cb=*/with_cov ? nb + mb : nb,
+                    count);
     launch_predict_reduce(c->lik, c->A, np, ms, mb, nb, c->pkss, c->plam, c->pxn, c->ppart,
                           nb * np, c->pmean, c->pvar, c->pprob, np, lv, count, c->stream);
 }

@@ -12,6 +12,7 @@
 // terms (1/2 W f^2, z f, the -x^2/2 of log Phi) are formed and summed in fp64.
 #include "apm_internal.h"
 #include "is_weights.h"
+#include "philox.h"
 #include "ugemm_tile.h"
 
 // ------------------------------------------------------------------------------- U buffers
@@ -32,22 +33,6 @@ void launch_u_convert(const double* U64, int64_t ldu, int n, int S, UPool P, int
     const int64_t tot = (int64_t)np * P.sp;
     APM_LAUNCH(k_u_convert, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, U64, ldu,
                        n, S, P.base + ubuf * P.stride, P.base32 + ubuf * P.stride, P.sp, np);
-}
-
-// Philox4x32-10 (Salmon et al., SC'11) + Box-Muller: counter = (e/4, ctr_lo, ctr_hi, 0)
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0;
-        c[1] = lo1;
-        c[2] = n2;
-        c[3] = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
 }
 
 // raw Philox4x32-10 blocks (apm_selftest_philox): in = {ctr0..3, key0, key1} per block
@@ -74,20 +59,8 @@ __global__ __launch_bounds__(256) void k_u_normal(UPool P, const int64_t* __rest
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;  // group of 4 normals
     const int64_t tot = (int64_t)n * S;
     if (q * 4 >= tot) return;
-    const uint64_t sd = seeds[b], ct = counters[b];
-    uint32_t c[4] = {(uint32_t)q, (uint32_t)ct, (uint32_t)(ct >> 32), (uint32_t)(q >> 32)};
-    philox4x32_10(c, (uint32_t)sd, (uint32_t)(sd >> 32));
     float z[4];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const float u1 = ((float)c[2 * h] + 0.5f) * 2.3283064365386963e-10f;
-        const float u2 = ((float)c[2 * h + 1] + 0.5f) * 2.3283064365386963e-10f;
-        const float rr = sqrtf(-2.0f * logf(u1));
-        float sn, cs;
-        sincosf(6.283185307179586f * u2, &sn, &cs);
-        z[2 * h] = rr * cs;
-        z[2 * h + 1] = rr * sn;
-    }
+    philox_normal4(q, seeds[b], counters[b], z);
     double* dst = P.base + ubufs[b] * P.stride;
     float* dst32 = P.base32 + ubufs[b] * P.stride;
 #pragma unroll

@@ -45,6 +45,8 @@ PROF_POST32_OUTER, PROF_POST64_RERUNS, PROF_TRSV_TIMEOUTS = 8, 9, 10
 PROF_ICM_CHECKS, PROF_GUARD, PROF_GRAD_REDUCE, PROF_EP_SITES, PROF_NKINDS = 11, 12, 13, 14, 15
 SPREAD_MAX_BLOCKS = 4096  # APM_SPREAD_MAX_BLOCKS: n_rep * nblk of one apm_is_spread call
 PSIS_MAX_SAMPLES = 4096  # APM_PSIS_MAX_SAMPLES: the largest n_imp apm_is_loo_psis sorts
+JOINT_LAPLACE, JOINT_EP = 0, 1  # APM_JOINT_*: the fit behind apm_predict_joint
+JOINT_MAX_DRAWS = 4096  # APM_JOINT_MAX_DRAWS
 
 
 class NativeUnavailableError(RuntimeError):
@@ -99,6 +101,8 @@ _SIGS = {
     'apm_ep_eval': (_i, [_p, _i64, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _p]),
     'apm_ep_predict': (_i, [_p, _i64, _p, _i64, _p, _i64, _i64, _p, _p, _p, _i64, _p, _p]),
     'apm_ep_grad': (_i, [_p, _i64, _p, _i64, _p, _p, _i64, _p, _p]),
+    'apm_predict_joint': (_i, [_p, _i, _i64, _p, _i64, _p, _i64, _i64, _p, _i64, _p, _i64, _i64, _p,
+                               _p, _p, _p, _p, _p, _p]),
     'apm_ep': (_i, [_i, _p, _i64, _i64, _p, _i, _d, _d, _i64, _p, _p, _p, _p, _p, _i64, _p, _p,
                     _p]),
     'apm_ep_lik': (_i, [_i, _i, _p, _i64, _i64, _p, _i, _d, _d, _i64, _p, _p, _p, _p, _p, _i64, _p,
@@ -536,6 +540,45 @@ class Context(object):
         ``(mean, var, prob, status, n_sweeps)``, the first three (T, m) with NaN rows where
         status != 0 (include/apm.h apm_ep_predict)."""
         return self._predictive(self.lib.apm_ep_predict, thetas, X_test)
+
+    def predict_joint(self, approx, thetas, X_test, want_cov=True, n_draws=0, seeds=None,
+                      counters=None, want_draws=False, y_test=None):
+        """Joint Laplace (`approx` JOINT_LAPLACE) or EP (JOINT_EP) predictive at the block X_test
+        (m <= padded n, d) for every row of thetas, `max_batch` at a time: ``(mean (T, m), cov
+        (T, m, m), draws (T, n_draws, m), joint_lpd (T,), status, n_iter)``, NaN where status != 0
+        (include/apm.h apm_predict_joint). cov is None unless `want_cov`, draws unless
+        `want_draws`, joint_lpd unless labels `y_test` (m,) are given; the last two need
+        `n_draws` > 0 and one Philox seed per theta (`counters` default to 0)."""
+        th, Xs = self._thetas(thetas), self._test_inputs(X_test)
+        T, m, S = th.shape[0], Xs.shape[0], int(n_draws)
+        sampled = want_draws or y_test is not None
+        sd = ct = ys = None
+        if sampled:
+            if seeds is None:
+                raise ValueError('draws need one Philox seed per theta')
+            sd = np.ascontiguousarray(np.atleast_1d(seeds), dtype=np.uint64)
+            ct = (np.zeros(T, dtype=np.uint64) if counters is None
+                  else np.ascontiguousarray(np.atleast_1d(counters), dtype=np.uint64))
+            if sd.shape != (T,) or ct.shape != (T,):
+                raise ValueError('one seed and one counter per theta')
+        if y_test is not None:
+            ys = _f64(y_test)
+            if ys.shape != (m,):
+                raise ValueError('y_test has shape {0}, expected ({1},)'.format(ys.shape, m))
+        mean = np.full((T, m), np.nan)
+        cov = np.full((T, m, m), np.nan) if want_cov else None
+        draws = np.full((T, S, m), np.nan) if want_draws else None
+        lpd = np.full(T, np.nan) if ys is not None else None
+        st = np.zeros(T, dtype=np.int32)
+        cnt = np.zeros(T, dtype=np.int64)
+        off = lambda a, t0: a[t0:].ctypes.data if a is not None else None
+        for t0 in range(0, T, self.max_batch):
+            _check(self.lib.apm_predict_joint(
+                self._h, int(approx), min(self.max_batch, T - t0), off(th, t0), th.shape[1],
+                _ptr(Xs), m, self.d, off(mean, t0), m, off(cov, t0), m, S, off(sd, t0),
+                off(ct, t0), off(draws, t0), _ptr(ys), off(lpd, t0), off(st, t0), off(cnt, t0)),
+                self._h)
+        return mean, cov, draws, lpd, st, cnt
 
     def ep_grad(self, thetas):
         """log Z_EP and its gradient with respect to theta for every row of thetas, `max_batch`

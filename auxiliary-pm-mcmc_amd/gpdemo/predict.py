@@ -138,6 +138,58 @@ class LaplacePredictor(object):
         mean, var, prob = self(th, on_error)
         return log_predictive_density(mean, var, y_test, likelihood=self.likelihood, prob=prob)
 
+    _joint_approx = _native.JOINT_LAPLACE
+
+    def _joint(self, thetas, on_error, **what):
+        if on_error not in ('raise', 'nan'):
+            raise ValueError("on_error must be 'raise' or 'nan'")
+        th = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
+        mean, cov, draws, lpd, st, nit = self._ctx.predict_joint(
+            self._joint_approx, th, self.X_test, **what)
+        self.n_iter, self.status = nit, st
+        if on_error == 'raise':
+            for s in st:
+                self._raise_joint(int(s))
+        return mean, cov, draws, lpd
+
+    def _raise_joint(self, status):
+        # (STATUS_CHOL_C, the factor of the joint covariance: InvalidCovarianceMatrixError)
+        _raise_for_status(status, self._ctx, self.max_iters)
+
+    @staticmethod
+    def _seeds(seed, T):
+        """One Philox seed per theta: an array of T seeds as it is, a scalar s as s, s + 1, ..."""
+        sd = np.asarray(seed, dtype=np.uint64)
+        return sd if sd.ndim else sd + np.arange(T, dtype=np.uint64)
+
+    def joint(self, thetas, on_error='raise'):
+        """``(mean, cov)``: the latent mean (T, M) and the full latent covariance (T, M, M) across
+        the test inputs, ``K** - V V^T`` without jitter, for thetas (T, P) or (P,). The M test
+        inputs are one block: M must not exceed the training set's padded size. Failures as in
+        ``__call__``."""
+        return self._joint(thetas, on_error, want_cov=True)[:2]
+
+    def sample_latent(self, thetas, n_draws, seed, on_error='raise'):
+        """``draws`` (T, n_draws, M) of the latent function at the test inputs from N(mean, cov +
+        epsilon I), drawn on the device from the Philox stream ``(seed_t, 0)``; ``seed`` is one
+        seed per theta or a scalar s for s, s + 1, ... The same seeds give the same draws. A
+        covariance whose factor fails raises ``InvalidCovarianceMatrixError``."""
+        th = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
+        return self._joint(th, on_error, want_cov=False, n_draws=int(n_draws),
+                           seeds=self._seeds(seed, th.shape[0]), want_draws=True)[2]
+
+    def joint_log_predictive_density(self, thetas, y_test, n_draws, seed, burn=0, thin=1,
+                                     on_error='raise'):
+        """Joint log predictive density of the labels ``y_test`` (M,) in {-1, +1}: the log of the
+        average over the kept thetas ``burn::thin`` of the per-theta joint density, itself a
+        Monte-Carlo average over ``n_draws`` draws of the latent function taken on the device in log
+        space. It does not factorise over the test points. ``seed`` as in ``sample_latent``, one
+        per kept theta."""
+        th = np.atleast_2d(np.asarray(thetas, dtype=np.float64))[int(burn)::int(thin)]
+        lpd = self._joint(th, on_error, want_cov=False, n_draws=int(n_draws),
+                          seeds=self._seeds(seed, th.shape[0]), y_test=y_test)[3]
+        return _log_mean_exp_density(_keep(lpd[:, None], 0, 1))
+
     def close(self):
         self._ctx.close()
 
@@ -176,6 +228,13 @@ class EPPredictor(LaplacePredictor):
             for s in st:
                 raise_for_ep_status(int(s), self.max_sweeps)
         return mean, var, prob
+
+    _joint_approx = _native.JOINT_EP
+
+    def _raise_joint(self, status):
+        if status == _native.STATUS_CHOL_C:
+            _raise_for_status(status, self._ctx, self.max_sweeps)
+        raise_for_ep_status(status, self.max_sweeps)
 
 
 class ISPredictor(object):

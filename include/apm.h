@@ -346,6 +346,51 @@ int apm_ep_predict(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ld
  * detects this entry point by its symbol. */
 int apm_ep_grad(apm_ctx *ctx, int64_t count, const double *thetas, int64_t ldt, double *logz,
                 double *grad, int64_t ldg, int *status, int64_t *n_sweeps);
+/* ---- joint Laplace / EP predictive at test inputs (no reference counterpart) --
+ * The fit of apm_predict (approx = APM_JOINT_LAPLACE) or apm_ep_predict (APM_JOINT_EP) with its
+ * settings, statuses and refusals, then for each chain that is OK, at the m test inputs Xs (m x d,
+ * ldxs) taken as ONE block, 1 <= m <= apm_padded_n (a joint covariance cannot be split):
+ *   mean_j = k*_j^T a                       bitwise apm_predict's / apm_ep_predict's mean
+ *   Sigma  = K**(Xs, Xs) - V V^T,  V_j = L^-1 (W^1/2 . k*_j)   (S^1/2 for EP)
+ * K** the context's covariance function between the test points with its bias and linear terms and
+ * no epsilon (as k* and k** carry none). cov: count blocks of m rows, row stride ldc >= m, both
+ * triangles, one the exact mirror of the other; nothing is clamped. mean: count x m, row stride
+ * ldo >= m.
+ * n_draws > 0: L_S = chol(Sigma + epsilon I) with the context's epsilon (the reference's rule of
+ * adding epsilon to one point set's own Gram; cov stays Sigma without it); a factor that fails
+ * gives that chain APM_STATUS_CHOL_C. Then
+ *   f*_r = mean + L_S xi_r,  r < n_draws,
+ * xi_r column r of the m x n_draws matrix that the Philox normal stream of apm_u_normal fills in
+ * row-major order from (seeds[i], counters[i]): xi_rj is element j n_draws + r of the stream, so
+ * every draw can be reproduced on the host. draws: count x n_draws x m. And with labels ys (m
+ * values in {-1, +1}, the same for every chain)
+ *   joint_lpd[i] = logsumexp_r sum_j log p(ys_j | f*_rj) - log n_draws
+ * under the context's likelihood, in log space throughout: the joint log predictive density of the
+ * labels, which does not factorise over the test points.
+ * Any of mean, cov, draws and joint_lpd may be NULL; n_draws = 0 asks for neither of the last two
+ * (seeds, counters and ys may then be NULL too). The outputs of a chain that is not OK are NaN.
+ * n_iter[i] (may be NULL): the fit's Newton iterations or EP sweeps. APM_E_INVALID for another
+ * approx, a PRECOMPUTED context, APM_JOINT_EP on an APM_LIK_LOGIT context without
+ * apm_set_ep_quadrature, count > max_batch, m outside [1, apm_padded_n], n_draws outside [0,
+ * APM_JOINT_MAX_DRAWS], and draws or joint_lpd asked for with n_draws = 0. A chain's outputs do
+ * not depend on its position in the batch nor on the other chains. Uses the context's work matrix
+ * like every theta-call; cache slots and U buffers are not touched. The first call that draws
+ * allocates device scratch that grows with the largest n_draws asked for so far and is kept for
+ * the context's lifetime: max_batch x 64 ceil(n_draws / 64) x apm_padded_n doubles for the normals
+ * and as many again at the first call that wants the draws back (about 1 GiB each at max_batch
+ * 8, apm_padded_n 4096 and 4096 draws). apm_version() is unchanged: a caller detects this entry
+ * point by its symbol. */
+#define APM_JOINT_LAPLACE 0
+#define APM_JOINT_EP 1
+#define APM_JOINT_MAX_DRAWS 4096
+int apm_predict_joint(apm_ctx *ctx, int approx, int64_t count, const double *thetas, int64_t ldt,
+                      const double *Xs, int64_t m, int64_t ldxs,
+                      double *mean, int64_t ldo,            /* count x m, may be NULL */
+                      double *cov, int64_t ldc,             /* count blocks of m x ldc, may be NULL */
+                      int64_t n_draws, const uint64_t *seeds, const uint64_t *counters,
+                      double *draws,                        /* count x n_draws x m, may be NULL */
+                      const double *ys, double *joint_lpd,  /* m labels in {-1,+1}; count; may be NULL */
+                      int *status, int64_t *n_iter);
 /* cached u-call: reuse slots[i]'s per-theta state with draws ubufs[i]; out_logf[i] is NaN where
  * status[i] != 0 or the slot's last theta-call failed (such a slot holds no state) */
 int apm_u_eval(apm_ctx *ctx, int64_t count, const int64_t *slots, const int64_t *ubufs,
